@@ -2,6 +2,7 @@
 """bench.py — headline benchmark of the yolo3_darknet53 hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W [--mode train|detect] [--batch B] [--size S] [--classes C]
+                  [--dump-outputs DIR] [--full]
 
 mode train  (default; BASELINE.json configs[2]): yolo3_darknet53_coco, per-GPU batch 64, 416x416, fp32,
             one step = forward + 4 losses + backward + gradient all-reduce (N>1) + SGD-momentum update.
@@ -9,6 +10,9 @@ mode detect (BASELINE.json configs[1] shape): forward + decode + NMS at 608x608.
 Inputs are synthetic, resident in HBM before the timed region; weights random-init (He).
 For N>1 the driver launches one rank per GPU with torch.distributed.run; ranks shard frames (weak scaling).
 Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).  --full adds
+the diagnostics that take runs of their own: the phase split, the per-kernel roofline replay, the native-fp32, detect and
+608x608 sub-lines and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -51,9 +55,14 @@ def parse():
     ap.add_argument("--k-join-type", default="max", choices=["max", "mean", "cat"])
     ap.add_argument("--k-join-pos", default="late", choices=["early", "late"])
     ap.add_argument("--block-conv-type", default="2", choices=["2", "3", "21"])
-    ap.add_argument("--detail", default=None, help="write a per-launch conv table (JSON) to this path")
+    ap.add_argument("--detail", default=None, help="write a per-launch conv table (JSON) to this path (implies --full)")
     ap.add_argument("--obj-bias", type=float, default=None,
                     help="objectness bias of the random-init heads (default: calibrated so ~2%% of score rows pass)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the diagnostics beside the headline: phase split, per-kernel roofline replay, "
+                         "native-fp32 / detect / 608x608 sub-lines, CPU baseline (each switchable with the --no-* flags)")
     return ap.parse_args()
 
 
@@ -77,8 +86,33 @@ def cpu_baseline(mode, size, classes):
     return out
 
 
+DUMP_SAMPLE = 1 << 21      # elements of the seeded sample taken from all parameters (and from all gradients): 8 MB each
+
+
+def dump_outputs(d, net, train, out):
+    """What the timed path computed in its last step, as d/<name>.npy (float32).  detect: what net(x) returns (class ids,
+    scores, boxes).  train: the four per-image losses net(x, gt, *targets) returns and, after backward, all-reduce and the
+    SGD update, a fixed seeded sample (DUMP_SAMPLE elements, the same for the same arguments) of all parameters and of all
+    gradients, each flattened in the reference layout and concatenated in collect_params() order."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {}
+    if train:
+        arrs.update(zip(("obj_loss", "center_loss", "scale_loss", "cls_loss"), out))
+        params = list(net.collect_params().values())
+        for name, flat in (("params_sample", [p.data().reshape(-1) for p in params]),
+                           ("grads_sample", [p.grad().reshape(-1) for p in params if p.grad_storage is not None])):
+            flat = torch.cat([t.float() for t in flat])
+            idx = np.sort(np.random.default_rng(20240).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+            arrs[name] = flat[torch.from_numpy(idx).to(flat.device)]
+    else:
+        arrs.update(zip(("ids", "scores", "bboxes"), out))
+    for name, t in arrs.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     a = parse()
+    a.full = a.full or bool(a.detail)            # the per-launch table comes from the roofline replay
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -128,6 +162,7 @@ def main():
         x_np = x_np.reshape(B, K, 3, S, S)
         gt_np, ids_np = gt_np.reshape(B, K, -1, 4)[:, K // 2], ids_np.reshape(B, K, -1, 1)[:, K // 2]
     x = torch.from_numpy(x_np).cuda()
+    last = [None]                  # what the latest step's call returned (--dump-outputs)
     if train:
         tg = prefetch_targets(S, S, gt_np, ids_np, C)
         gt = torch.from_numpy(gt_np).cuda()
@@ -135,7 +170,7 @@ def main():
         lr, mom, wd = 1e-3, 0.9, 5e-4      # train_yolov3.py:78,91-94 defaults
 
         def step():
-            net(x, gt, *tgd)
+            last[0] = net(x, gt, *tgd)
             net.backward()
             net.allreduce_grads()
             net.sgd_step(lr, mom, wd, batch_size=B * world)
@@ -165,7 +200,7 @@ def main():
         net.use_graphs = bool(a.graphs)
 
         def step():
-            net(x)
+            last[0] = net(x)
 
     def sync():
         torch.cuda.synchronize()
@@ -190,10 +225,13 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     fps = world * B * K * a.steps / dt            # frames (a window of k frames counts k; windows/s is in config)
+    if a.dump_outputs and rank == 0:              # before any diagnostic below runs the network again
+        dump_outputs(a.dump_outputs, net, train, last[0])
 
+    # ---- everything below up to the result line runs with --full only
     # ---- phase split (one extra step with device syncs between phases; not part of the timed region)
     phases = None
-    if train:      # every rank runs it (allreduce_grads is a collective); rank 0 reports
+    if train and a.full:      # every rank runs it (allreduce_grads is a collective); rank 0 reports
         def timed(fn):
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -242,8 +280,9 @@ def main():
     # ---- roofline of the dominant kernel (k_conv_igemm: forward + data-gradient convs), measured live with
     # events on the launch stream over one more step
     roof = None
-    extra = {}
-    if True:       # every rank replays (keeps ranks in lock-step if SyncBN collectives are in the programs)
+    extra = None
+    if a.full:       # every rank replays (keeps ranks in lock-step if SyncBN collectives are in the programs)
+        extra = {}
         recs = []
         if train:
             net(x, gt, *tgd)
@@ -423,7 +462,7 @@ def main():
 
     # ---- the strict reading of "fp32": the same step with every product on the fp32 MFMA (v_mfma_f32_32x32x2_f32, an exact
     # fma chain; VD_FP32_MATH=native), a few steps, beside the headline - which runs the fp32-grade split arithmetics
-    if roof is not None and train and a.dtype == "f32" and world == 1 and not force_dist and K == 1 and not a.no_native \
+    if a.full and roof is not None and train and a.dtype == "f32" and world == 1 and not force_dist and K == 1 and not a.no_native \
             and os.environ.get("VD_FP32_MATH", "auto") == "auto":
         from viddet_amd.model import set_conv_math
         del net
@@ -452,12 +491,12 @@ def main():
     # training number of the default run: the same script as a child process (its own plans and calibration), its line
     # embedded here - frames/s and the decode / NMS kernels' ms and GB/s at the calibrated pass fraction
     detect = None
-    if train and rank == 0 and world == 1 and not force_dist and not a.no_detect and K == 1 and a.dtype == "f32" \
+    if a.full and train and rank == 0 and world == 1 and not force_dist and not a.no_detect and K == 1 and a.dtype == "f32" \
             and a.batch == 0 and a.size == 0:
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", "detect", "--dtype", "bf16", "--steps", "20",
-                                "--warmup", "5", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                                "--warmup", "5", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
             dj = json.loads(r.stdout.strip().splitlines()[-1])
             detect = {"metric": dj["metric"], "value": dj["value"], "unit": dj["unit"], "ms_per_step": dj["ms_per_step"],
                       "dtype": dj["dtype"], "config": dj["config"]["workload"], "score_filter": dj["config"]["score_filter"],
@@ -470,12 +509,12 @@ def main():
     # ---- north_star's second training size ("synthetic 416x416 and 608x608"): fp32, 80 classes, 608x608, batch 32 - the same
     # script as a child process (its own plans), frames/s and the dominant kernel's rate embedded here
     train_608 = None
-    if train and rank == 0 and world == 1 and not force_dist and not a.no_detect and K == 1 and a.dtype == "f32" \
+    if a.full and train and rank == 0 and world == 1 and not force_dist and not a.no_detect and K == 1 and a.dtype == "f32" \
             and a.batch == 0 and a.size == 0:
         import subprocess
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--size", "608", "--batch", "32", "--steps", "10", "--warmup", "3",
-                                "--no-cpu-baseline", "--no-native", "--no-detect"], capture_output=True, text=True, timeout=900)
+                                "--full", "--no-cpu-baseline", "--no-native", "--no-detect"], capture_output=True, text=True, timeout=900)
             tj = json.loads(r.stdout.strip().splitlines()[-1])
             train_608 = {"metric": tj["metric"], "value": tj["value"], "unit": tj["unit"], "ms_per_step": tj["ms_per_step"],
                          "dtype": tj["dtype"], "config": tj["config"]["workload"],
@@ -488,7 +527,7 @@ def main():
             train_608 = {"error": repr(e)[:200]}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.mode, S, C)
 
     if world > 1 or force_dist:

@@ -354,7 +354,7 @@ def test_single_rank_rccl_path_and_exchange_diagnostics():
     env = dict(os.environ, VD_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", VD_BUCKET_MB="8")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--size", "64", "--classes", "4", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
+                        "--size", "64", "--classes", "4", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900,
                        env=env)
     assert r.returncode == 0, r.stderr[-1500:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
@@ -378,7 +378,7 @@ def test_bench_two_ranks_launched_the_drivers_way():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29571", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "2", "--size", "64", "--classes", "4"]
+           "--batch", "2", "--size", "64", "--classes", "4", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -389,6 +389,38 @@ def test_bench_two_ranks_launched_the_drivers_way():
     assert abs(out["value"] - 4 / (out["ms_per_step"] * 1e-3)) < 0.02 * out["value"]
     assert out["cpu_baseline"] is None and out["roofline"]["frac"] > 0
     assert out["phases"]["allreduce"]["buckets_per_step"] >= 4 and out["phases"]["allreduce_exposed_ms"] >= 0
+
+
+@pytest.mark.parametrize("mode", ["train", "detect"])
+def test_bench_plain_run_dumps_the_last_step(mode, tmp_path):
+    """bench.py without --full: exactly --steps timed steps, the headline fields and none of the --full diagnostics; with
+    --dump-outputs the arrays of the last timed step as float32 .npy files (detect: what net(x) returns; train: the four
+    losses and the seeded samples of the updated parameters and of the gradients), well under 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", mode, "--steps", "3", "--warmup", "1",
+                        "--batch", "2", "--size", "64", "--classes", "4", "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-1500:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "frames/s" and out["higher_is_better"] is True
+    assert abs(out["value"] - 2 / (out["ms_per_step"] * 1e-3)) < 0.02 * out["value"]
+    assert out["roofline"] is None and out["phases"] is None and out["kernels"] is None and out["cpu_baseline"] is None
+    names = (["obj_loss", "center_loss", "scale_loss", "cls_loss", "params_sample", "grads_sample"] if mode == "train" else
+             ["ids", "scores", "bboxes"])
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+    arrs = {n: np.load(str(d / (n + ".npy"))) for n in names}
+    assert all(v.dtype == np.float32 and np.all(np.isfinite(v)) for v in arrs.values())
+    if mode == "train":
+        assert arrs["obj_loss"].shape == (2,) and arrs["params_sample"].shape == arrs["grads_sample"].shape == (1 << 21,)
+        assert np.any(arrs["grads_sample"] != 0) and np.all(arrs["obj_loss"] > 0)
+    else:
+        assert arrs["scores"].shape[:2] == arrs["bboxes"].shape[:2] == arrs["ids"].shape[:2] and arrs["bboxes"].shape[0] == 2
+    assert sum(os.path.getsize(str(d / (n + ".npy"))) for n in names) <= 64 << 20
 
 
 @pytest.mark.parametrize("cfg", [(2, 4, 64, 3), (1, 20, 416, 6)])

@@ -5,7 +5,8 @@
 set -e
 B=${1:-32}
 cd "$(dirname "$0")/.."
-mkdir -p build_dbg gpurun_out/nms_probe
+O=build_dbg/nms_probe            # the probe libraries and the bench lines (git-ignored)
+mkdir -p build_dbg $O
 F="-O3 -fPIC --offload-arch=gfx950 -std=c++17 -Wall -Wno-unused-function -fno-slp-vectorize -Iinclude"
 for n in 1 2 3 4 5; do
   /opt/rocm/bin/hipcc $F -DVD_NMS_PROBE=$n -c viddet_amd/csrc/vd_yolo.hip -o build_dbg/vd_yolo_p$n.o
@@ -14,8 +15,8 @@ for n in 1 2 3 4 5; do
 done
 for n in 0 1 2 3 4 5; do
   if [ $n = 0 ]; then L=""; else L="build_dbg/libviddet_nmsp$n.so"; fi
-  VD_LIB=$L python bench.py --mode detect --dtype bf16 --batch $B --no-cpu-baseline > gpurun_out/nms_probe/b${B}_p$n.json 2> gpurun_out/nms_probe/b${B}_p$n.err
-  python - "$n" gpurun_out/nms_probe/b${B}_p$n.json <<'PY'
+  VD_LIB=$L python bench.py --full --mode detect --dtype bf16 --batch $B --no-cpu-baseline > $O/b${B}_p$n.json 2> $O/b${B}_p$n.err
+  python - "$n" $O/b${B}_p$n.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[2]) if l.startswith("{")][-1])
 print("probe %s: nms %.4f ms  decode %.4f ms" % (sys.argv[1], d["kernels"]["nms"]["ms"], d["kernels"]["decode_filter"]["ms"]), flush=True)

@@ -153,7 +153,7 @@ def main(argv=None):
         FLAGS.k_join_type = FLAGS.k_join_pos = None
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
-    for flag in ("temp", "mult_out", "new_model", "motion_stream", "rnn_pos", "corr_pos", "visualise", "model_agnostic",
+    for flag in ("temp", "mult_out", "new_model", "motion_stream", "rnn_pos", "visualise", "model_agnostic",
                  "metric_agnostic", "offset", "per_frame_metric", "worst_video_path", "trained_on"):
         v = getattr(FLAGS, flag)
         if v and not (isinstance(v, str) and not v.strip()):
@@ -166,13 +166,15 @@ def main(argv=None):
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
     else:
-        dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples)
+        # --window k: a sample is the k-frame window around the frame the rows belong to (as train_yolov3.py's sets)
+        dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples, window=FLAGS.window[0])
     # frames travel as uint8 and are normalised on the device (vd_preprocess_u8_nchw: the transform's own arithmetic)
     loader = Loader(dataset, YOLO3VideoInferenceTransform(FLAGS.data_shape, FLAGS.data_shape, device_normalize=True),
                     FLAGS.batch_size, train=False, last_batch="keep", rank=rank, world=world)
     # detect_yolo3.py:871-892
     net = yolo3_darknet53(dataset.classes, pretrained_base=False, k=FLAGS.window[0], k_join_type=FLAGS.k_join_type,
-                          k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type)
+                          k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type,
+                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d)
     if FLAGS.random_init:
         net.initialize(init="he", obj_bias=-2.0)
     else:

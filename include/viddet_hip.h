@@ -111,7 +111,7 @@ int vd_version(void);
  * header would have passed its stream handle as amax_out).  A binding checks vd_abi_version() == VD_ABI_VERSION and
  * vd_sizeof_desc(i) == sizeof(its mirror of the descriptor) at load, before the first compute call: viddet_amd/lib.py
  * does, INTEGRATION.md shows it.  i: 0 = vd_conv_desc, 1 = vd_wgrad_desc, 2 = vd_head_desc; unknown i -> -1. */
-#define VD_ABI_VERSION 6
+#define VD_ABI_VERSION 7
 int vd_abi_version(void);
 int64_t vd_sizeof_desc(int which);
 
@@ -396,6 +396,21 @@ int vd_frame_slice(const float* x, float* y, int B, int K, int k0, int kc, int64
 /* 'cat' join (yolo3.py:1108,1136 reshape (B,K,C,h,w)->(B,K*C,h,w)): NHWC [B*K,hw,C] -> [B,hw,K*C];
  * backward=1 runs the inverse (x = stacked gradient, y = per-frame gradient) */
 int vd_temporal_cat(const float* x, float* y, int B, int K, int64_t hw, int C, int backward, void* stream);
+/* Correlation join (Corr(d, K, kernal_size=1, stride=1, keep='all'), layers.py:93-132): x [B*K, H, W, C] fp32 NHWC
+ * (frame b*K + k) -> y [B, H, W, ldy], mid = K/2, D = 2d+1, Cc = K*C + (K-1)*D*D:
+ *   y[b, p, k*C + c]                          = x[b*K + k, p, c]                              (the 'cat' join)
+ *   y[b, p, K*C + tt*D*D + (dy+d)*D + (dx+d)] = (1/C) sum_c x[b*K+t, p, c] * x[b*K+mid, p + (dy, dx), c]
+ *                                               for every t != mid (tt = t - (t > mid)); 0 where p + (dy, dx) leaves the map
+ *   y[b, p, Cc .. ldy)                        = 0
+ * i.e. mx.sym.Correlation(x_t, x_mid, kernel_size=1, max_displacement=d, pad_size=d, stride1=stride2=1, is_multiply=1),
+ * whose divisor is kernel_size^2 * C.  Requires C % 32 == 0, 0 <= d <= 5, ldy >= Cc, ldy % 8 == 0.  One launch.
+ * vd_corr_bwd: dx [B*K, H, W, C] from dy [B, H, W, ldy] and x, two gathers in a fixed order (bit-reproducible):
+ *   dx[t != mid][p] = dy_cat[t][p] + (1/C) sum_disp dy_t[p, disp] * x_mid[p + disp]
+ *   dx[mid][q]      = dy_cat[mid][q] + (1/C) sum_{t != mid} sum_disp dy_t[q - disp, disp] * x_t[q - disp]
+ * vd_corr_fwd_bf16: the forward on bf16 tensors (fp32 sums, bf16 output). */
+int vd_corr_fwd(const float* x, float* y, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
+int vd_corr_bwd(const float* dy, const float* x, float* dx, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
+int vd_corr_fwd_bf16(const void* x, void* y, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * YOLO head: decode / filter / NMS / targets / loss

@@ -618,11 +618,20 @@ class Parameter:
             self._net._grad_req_changed()
 
     # reference layout <-> device layout (conv weights are kept fwd-packed [Co_pad][T*Ci])
+    def _dev_shape(self):
+        """shape of the packed image's OIHW form: a consumer of a correlation join reads its input with zero channels
+        appended (CorrNode), so its device rows are longer than the reference's by that padding"""
+        n = self.node
+        if n is None or n.cin == n.ref_cin:
+            return self.shape
+        return (self.shape[0], n.cin) + self.shape[2:]
+
     def data(self):
         if self.kind == 'conv_weight':
-            out = torch.empty(self.shape, device=self.storage.device)
+            shp = self._dev_shape()
+            out = torch.empty(shp, device=self.storage.device)
             ops.unpack_weight(self.storage, out)
-            return out
+            return out if shp == self.shape else out[:, :self.shape[1]].contiguous()
         if self.kind == 'stem_weight':
             co = self.shape[0]
             return self.storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
@@ -630,9 +639,10 @@ class Parameter:
 
     def grad(self):
         if self.kind == 'conv_weight':
-            out = torch.empty(self.shape, device=self.grad_storage.device)
+            shp = self._dev_shape()
+            out = torch.empty(shp, device=self.grad_storage.device)
             ops.unpack_weight(self.grad_storage, out)
-            return out
+            return out if shp == self.shape else out[:, :self.shape[1]].contiguous()
         if self.kind == 'stem_weight':
             co = self.shape[0]
             return self.grad_storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
@@ -643,7 +653,12 @@ class Parameter:
         assert tuple(v.shape) == self.shape, "%s: shape %s != %s" % (self.name, tuple(v.shape), self.shape)
         v = v.to(self.storage.device).contiguous()
         if self.kind == 'conv_weight':
-            co_pad = self.storage.numel() // (int(np.prod(self.shape[1:])))
+            shp = self._dev_shape()
+            if shp != self.shape:                  # the padded input channels get zero weights
+                vp = torch.zeros(shp, device=v.device)
+                vp[:, :self.shape[1]] = v
+                v = vp
+            co_pad = self.storage.numel() // (int(np.prod(shp[1:])))
             ops.pack_weight_fwd(v, self.storage, co_pad)
         elif self.kind == 'stem_weight':
             co = self.shape[0]
@@ -674,6 +689,7 @@ class ConvNode:
                  kd=1, fr=1):
         self.name, self.src, self.dst = name, src, dst
         self.cin, self.cout, self.k, self.stride = cin, cout, k, stride
+        self.ref_cin = cin                         # input channels of the reference's weight (< cin behind a CorrNode)
         self.pad = k // 2
         self.kd, self.pad_d = kd, kd // 2          # temporal kernel depth (Conv3D over the K frames of a window)
         self.fr = fr                               # frames per sample carried by this node's tensors (K or 1)
@@ -689,8 +705,8 @@ class ConvNode:
 
     def weight_shape(self):
         if self.kd > 1 or getattr(self, 'conv3d', False):
-            return (self.cout, self.cin, self.kd, self.k, self.k)
-        return (self.cout, self.cin, self.k, self.k)
+            return (self.cout, self.ref_cin, self.kd, self.k, self.k)
+        return (self.cout, self.ref_cin, self.k, self.k)
 
 
 class UpcatNode:
@@ -706,6 +722,18 @@ class PoolNode:
         # type 0 = max, 1 = mean, 2 = 'cat' (channel stacking: dst has K * C channels)
         self.name, self.src, self.dst, self.K = name, src, dst, K
         self.type = {'max': 0, 'mean': 1, 'cat': 2}[type_]
+
+
+class CorrNode:
+    """Corr(d, K, kernal_size=1, stride=1, keep='all') over the K frames of a window (layers.py:93-132): (B*K, h, w, C) ->
+    (B, h, w, ldy) = [the K frames' channels stacked | one (2d+1)^2-channel correlation map per frame t != K/2 against the
+    centre frame | zeros up to ldy = round_up(Cc, 64)] (vd_corr.hip).  The zero tail keeps the channel count of the
+    consumers' operand a multiple of 64; their weights carry zero rows there (Parameter._dev_shape)."""
+
+    def __init__(self, name, src, dst, K, d, C_):
+        self.name, self.src, self.dst, self.K, self.d, self.C = name, src, dst, K, d, C_
+        self.Cc = K * C_ + (K - 1) * (2 * d + 1) ** 2
+        self.ldy = round_up(self.Cc, 64)
 
 
 class SelNode:
@@ -735,7 +763,7 @@ ROUTE_TENSORS = (('f14', 256, 8), ('f23', 512, 16), ('f28', 1024, 32))   # featu
 
 
 def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_type='2', noback=False,
-                temporal_out=False, temporal_side=False):
+                temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0):
     """Node list of YOLOV3T over Darknet-53 (wrappers.py:54-58,101-103; three_darknet.py:252-258;
     yolo3.py:1003-1054 wiring, :1095-1177 forward).  k>1: the backbone is TimeDistributed (K frames folded
     into the batch, layers.py:241-250); 'early' joins pool each stage output over K, 'late' joins keep K frames
@@ -751,8 +779,21 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
     # 5, 3 and 1 frames of the window; strided 2+1-D side branches (convs1 / convs2: a per-frame 3x3 stride-2 conv, then a
     # (3,1,1) conv WITHOUT temporal padding, 5 -> 3 and 3 -> 1 frames) carry the neighbours' features down and are added to
     # the stage outputs; the routes are the centre frames and the neck / heads are the plain single-frame ones.
+    # corr_pos (yolo3.py:1112-1113,1139-1140): the reference's `elif` - a correlation join replaces the pooling / stacking
+    # at the same place when no k_join_pos is given
+    corr = K > 1 and k_join_pos is None and corr_pos is not None and not temporal_out and not temporal_side
+    if corr:
+        k_join_pos = corr_pos
     late = K > 1 and (k_join_pos == 'late' or temporal_out)
     td_names = K > 1 and not temporal_out and not temporal_side
+    pad_of = {}                            # zero channels at the end of a tensor built from a correlation join
+
+    def corr_join(name, src, c_, d_):
+        n_ = CorrNode('corr.' + name, src, name + '.corr', K, corr_d, c_)
+        dst = T(n_.dst, n_.ldy, d_)
+        nodes.append(n_)
+        pad_of[dst] = n_.ldy - n_.Cc
+        return dst, n_.ldy
 
     def T(name, c, div, ld=None, fr=1):
         tensors[name] = (c, div, c if ld is None else ld, fr)
@@ -831,6 +872,9 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
         pooled = []
         for i, r in enumerate(routes):
             c_, d_ = tensors[r][0], tensors[r][1]
+            if corr:
+                pooled.append(corr_join('route%d' % i, r, c_, d_)[0])
+                continue
             pr = T('route%d.pool' % i, c_ * (K if k_join_type == 'cat' else 1), d_)
             nodes.append(PoolNode('pool.route%d' % i, r, pr, K, k_join_type))
             pooled.append(pr)
@@ -878,7 +922,9 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
         route = x
         tip = add_cell(pre + ".tip", route, 'n%d.tip' % i, c, 2 * c, 3)
         tipc = 2 * c
-        if late and not temporal_out:                           # yolo3.py:1134-1138: join the tip over K
+        if late and not temporal_out and corr:                  # yolo3.py:1139-1140: correlation join of the tip
+            tip, tipc = corr_join('n%d.tip' % i, tip, 2 * c, d)
+        elif late and not temporal_out:                         # yolo3.py:1134-1138: join the tip over K
             tipc = 2 * c * (K if k_join_type == 'cat' else 1)
             ptip = T('n%d.tip.pool' % i, tipc, d)
             nodes.append(PoolNode('pool.tip%d' % i, tip, ptip, K, k_join_type))
@@ -894,8 +940,14 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
             rt = routes[1 - i]
             rc = tensors[rt][0]
             cat = T('n%d.cat' % i, c // 2 + rc, d // 2, fr=nfr)
+            if rt in pad_of:                                    # [upsampled transition | route], padding stays at the end
+                pad_of[cat] = pad_of[rt]
             nodes.append(UpcatNode("upcat.%d" % i, tr, rt, cat, c // 2, rc, d // 2, fr=nfr))
             x, xc = cat, c // 2 + rc
+    for n in nodes:
+        if isinstance(n, ConvNode) and n.src in pad_of:        # every consumer of a correlation join is a 1x1 cell
+            assert n.k == 1 and n.kd == 1 and not getattr(n, 'conv3d', False), n.name
+            n.ref_cin = n.cin - pad_of[n.src]
     return nodes, tensors, heads
 
 
@@ -905,8 +957,9 @@ class YOLOV3(object):
 
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, ignore_iou_thresh=0.7,
                  device="cuda", syncbn_scope=None, process_group=None, k=1, k_join_type=None, k_join_pos=None,
-                 block_conv_type='2', noback=False, temporal_out=False, temporal_side=False):
+                 block_conv_type='2', noback=False, temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0):
         self._classes = list(classes)
+        self._corr_pos, self._corr_d = corr_pos, int(corr_d or 0)   # correlation join (Corr, layers.py:93-132)
         self.temporal_side = bool(temporal_side)  # YOLOV3Temporal(t_out=False): strided 2+1-D side branches, one output
         self.temporal_out = bool(temporal_out)   # YOLOV3Temporal(t_out=True): per-frame detections / losses
         self._grad_scale = 1.0                   # d(reported loss)/d(sum of per-sample losses), see _forward_train
@@ -955,7 +1008,8 @@ class YOLOV3(object):
         self.nodes, self.tensors, self.head_names = build_graph(num_class, self._k, self._k_join_type,
                                                                 self._k_join_pos, self._block_conv_type,
                                                                 noback=self.noback, temporal_out=self.temporal_out,
-                                                                temporal_side=self.temporal_side)
+                                                                temporal_side=self.temporal_side, corr_pos=self._corr_pos,
+                                                                corr_d=self._corr_d)
         self._head_frames = self._k if self.temporal_out else 1
         self.input_tensors = [nm for nm, _, _ in ROUTE_TENSORS] if self.noback else ['in']
         self.conv_nodes = [n for n in self.nodes if isinstance(n, ConvNode)]
@@ -966,6 +1020,13 @@ class YOLOV3(object):
         # therefore range-exact BY CONSTRUCTION (3-way bf16 split / fp32 MFMA), never chosen by timing.  Every other operand
         # tensor is dense; those join this set through check_operand_ranges() when their channel scales spread too far.
         self._range_exact = set('dz:' + n.name for n in self.conv_nodes if n.head)
+        # A correlation join's output mixes frame features with cost-volume maps (products of two features / C): no single
+        # BatchNorm bounds its channel scales, and the guard does not follow derived tensors.  So the convs that read it -
+        # directly or through the concatenation behind a transition - are range-exact by construction as well (forward and
+        # weight gradient: both take it as their operand).
+        corr_t = {n.dst for n in self.nodes if isinstance(n, CorrNode)}
+        corr_t |= {n.dst for n in self.nodes if isinstance(n, UpcatNode) and n.route in corr_t}
+        self._range_exact |= corr_t
         self._guard = None
         # arena layout: [conv weights (fwd-packed) | bn gamma, beta, head bias]  -> wd / no_wd ranges
         off = 0
@@ -1033,7 +1094,7 @@ class YOLOV3(object):
             gv = self.grads[n.w_off:n.w_off + n.w_numel]
             n.wp, n.gwp = wv, gv
             if n.head:
-                reg(n.name + ".weight", (n.cout, n.cin, 1, 1), 'conv_weight', n, wv, gv, off=n.w_off)
+                reg(n.name + ".weight", (n.cout, n.ref_cin, 1, 1), 'conv_weight', n, wv, gv, off=n.w_off)
                 n.bias = self.weights[n.bias_off:n.bias_off + n.co_pad]
                 n.gbias = self.grads[n.bias_off:n.bias_off + n.co_pad]
                 reg(n.name + ".bias", (n.cout,), 'vector', n, n.bias, n.gbias, off=n.bias_off)
@@ -1406,6 +1467,11 @@ class YOLOV3(object):
                     prog.add('vd_temporal_pool', xs.data_ptr(), o.data_ptr(), None, B, n.K, o[0].numel(), n.type)
                 prog.add('vd_amax_merge', am(n.src), None, am(n.dst))             # max / mean / stacking: bounded by the source's
                 continue
+            if isinstance(n, CorrNode):                 # its readers are range-exact (_build): no max-abs slots needed
+                xs = bufs[n.src]
+                prog.add('vd_corr_fwd', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
+                         meta=self._corr_meta(n, B, xs, 'fwd'))
+                continue
             if isinstance(n, (SelNode, AddNode)):
                 self._add_sel_add_fwd(prog, n, bufs, B)
                 continue
@@ -1518,6 +1584,12 @@ class YOLOV3(object):
                     prog.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3] // 2, 0)
                 else:
                     prog.add('vd_temporal_pool_bf16', xs.data_ptr(), o.data_ptr(), B, n.K, o[0].numel(), n.type)
+                continue
+            if isinstance(n, CorrNode):
+                xs = bufs[n.src]
+                assert xs.shape[3] == n.C and bufs[n.dst].shape[3] == n.ldy
+                prog.add('vd_corr_fwd_bf16', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d,
+                         n.ldy, meta=self._corr_meta(n, B, xs, 'fwd'))
                 continue
             if isinstance(n, SelNode):
                 xs, o = bufs[n.src], bufs[n.dst]
@@ -1801,6 +1873,11 @@ class YOLOV3(object):
                     seg.add('vd_temporal_pool', xs.data_ptr(), o.data_ptr(), am, B, n.K, o[0].numel(), n.type)
                 seg.add('vd_amax_merge', amx(n.src), None, amx(n.dst))
                 continue
+            if isinstance(n, CorrNode):
+                xs = bufs[n.src]
+                seg.add('vd_corr_fwd', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
+                        meta=self._corr_meta(n, B, xs, 'fwd'))
+                continue
             if isinstance(n, (SelNode, AddNode)):
                 self._add_sel_add_fwd(seg, n, bufs, B)
                 continue
@@ -2022,6 +2099,19 @@ class YOLOV3(object):
                             dsrc.shape[3], 1)
                 else:
                     seg.add('vd_temporal_pool_bwd', dout.data_ptr(), am, target.data_ptr(), B, n.K, dout[0].numel(), n.type)
+                if acc:
+                    seg.add('vd_add', dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
+                continue
+            if isinstance(n, CorrNode):
+                if not tgrad[n.src]:
+                    continue
+                assert n.dst in written, n.name
+                materialize(n.dst)
+                dout, xs = bufs['d:' + n.dst], bufs[n.src]
+                dsrc, acc = grad_into(n.src, 0)
+                target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
+                seg.add('vd_corr_bwd', dout.data_ptr(), xs.data_ptr(), target.data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C,
+                        n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd'))
                 if acc:
                     seg.add('vd_add', dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
                 continue
@@ -2688,6 +2778,16 @@ class YOLOV3(object):
                     # algorithmic bytes: every operand tensor once (input, output/gradient, weights), fp32
                     bytes=4.0 * (px_in * n.cin + px_out * n.cout + n.cout * n.cin * n.kd * n.k * n.k))
 
+    @staticmethod
+    def _corr_meta(n, B, xs, kind):
+        """roofline record of a correlation launch: 2 flops per (pixel, displacement, channel) and side frame (x2 backward:
+        both operands' gradients); bytes = the operands read once and the result written once"""
+        px = B * xs.shape[1] * xs.shape[2]
+        D2 = (2 * n.d + 1) ** 2
+        flops = 2.0 * px * (n.K - 1) * D2 * n.C * (2 if kind == 'bwd' else 1)
+        byt = 4.0 * px * (n.K * n.C + n.ldy) * (2 if kind == 'bwd' else 1)
+        return dict(kind='corr_' + kind, flops=flops, bytes=byt)
+
     def _ones(self, c):
         if not hasattr(self, '_const'):
             self._const = (torch.ones(1024, device=self.device), torch.zeros(1024, device=self.device))
@@ -2934,7 +3034,7 @@ class YOLOV3(object):
 
 def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs=None, freeze_base=False,
                     k=None, k_join_type=None, k_join_pos=None, block_conv_type='2', temporal=False, t_out=False,
-                    corr_d=None, **kwargs):
+                    corr_d=None, corr_pos=None, **kwargs):
     """wrappers.py:9-110 -> YOLOV3T (yolo3.py:959-1054).  norm_layer='syncbn' (the reference passes
     SyncBatchNorm) selects the SyncBN collective.  k>1 builds the temporal-window variants; `t_out=True`
     (--temp --mult_out) builds YOLOV3Temporal with per-frame outputs (yolo3_temporal.py:286-555, t = k = 5)."""
@@ -2967,14 +3067,24 @@ def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs
     assert block_conv_type in ('2', '3', '21')
     assert k_join_type in [None, 'max', 'mean', 'cat']
     assert k_join_pos in [None, 'early', 'late']
+    assert corr_pos in [None, 'early', 'late']
+    corr = {}
     if k > 1:
-        if k_join_type is None or k_join_pos is None:
-            raise NotImplementedError("k>1 needs k_join_type (max|mean|cat) and k_join_pos (early|late)")
+        # yolo3.py:1106-1113,1134-1140: `if k_join_pos == pos: join  elif corr_pos == pos: Corr` at each position
+        if k_join_pos is None and corr_pos is not None:
+            corr = dict(corr_pos=corr_pos, corr_d=int(corr_d or 0))    # k_join_type is not read on this path
+            k_join_type = None
+        elif k_join_pos is not None and corr_pos is not None and corr_pos != k_join_pos:
+            # the join of one position would hand a (B, K*C | C, h, w) tensor to the TimeDistributed blocks of the other
+            raise NotImplementedError("k_join_pos %r with corr_pos %r: the reference feeds a 4-D tensor to a TimeDistributed "
+                                      "block" % (k_join_pos, corr_pos))
+        elif k_join_type is None or k_join_pos is None:
+            raise NotImplementedError("k>1 needs k_join_type (max|mean|cat) and k_join_pos (early|late), or corr_pos")
     scope = None
     if norm_layer == 'syncbn':
         scope = (norm_kwargs or {}).get('scope', 'all')
     net = YOLOV3(classes, syncbn_scope=scope, k=k, k_join_type=k_join_type, k_join_pos=k_join_pos,
-                 block_conv_type=block_conv_type, **kwargs)
+                 block_conv_type=block_conv_type, **corr, **kwargs)
     if freeze_base:                          # wrappers.py:55-57: every Darknet parameter leaves the gradient / update
         for name, p in net.collect_params('stages.*').items():
             p.grad_req = 'null'

@@ -1,0 +1,160 @@
+#!/usr/bin/env python
+"""The launch records of one training plan as canonical JSON, to show that a change to the plan builder
+(YOLOV3._build_train) leaves every launch as it was: build with one revision, then with the other, compare the files.
+
+usage: python tools/plan_dump.py ROOT OUT.json [--storage bf16] [--k 3 --join max --pos late] [...]
+
+ROOT is the directory that holds the `viddet_amd` package to import: this tree, or another revision's package staged
+beside it (VD_LIB names the kernel library when that copy has none).  Needs the GPU: the builder allocates its buffers
+there and the autotuner times launch records the tuning table does not hold.
+
+Every record of every segment is written with its entry point, its arguments (scalars as they are, descriptor structs
+field by field), its `meta` and the stream it runs on (main, side or parity i); a python record as `py` or `collective`
+with what its closure holds (events by first appearance, a gradient bucket's lo / hi).  Which arguments are pointers comes
+from lib.SIGNATURES.  A pointer is written as a named tensor plus a byte offset (the plan's buffers, the weight and gradient
+arenas, the nodes' tensors), any other pointer as a label given at its first appearance.  Run both revisions under one
+copy of the tuning table (VD_TUNE_CACHE): `--expect-tuned 0` on the second run fails when its build added table entries,
+i.e. timed a descriptor the first run did not have."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("root")
+    ap.add_argument("out")
+    ap.add_argument("--storage", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--size", type=int, default=64)
+    ap.add_argument("--classes", type=int, default=4)
+    ap.add_argument("--k", type=int, default=None)
+    ap.add_argument("--join", default=None, help="k_join_type")
+    ap.add_argument("--pos", default=None, help="k_join_pos")
+    ap.add_argument("--block", default="2", help="block_conv_type")
+    ap.add_argument("--corr-pos", default=None)
+    ap.add_argument("--corr-d", type=int, default=None)
+    ap.add_argument("--t-out", action="store_true", help="per-frame outputs (k = 5)")
+    ap.add_argument("--noback", action="store_true")
+    ap.add_argument("--freeze-base", action="store_true")
+    ap.add_argument("--range-exact", action="store_true", help="two tensors in net._range_exact")
+    ap.add_argument("--syncbn", default=None, choices=["all", "reference"],
+                    help="SyncBN on a one-rank gloo group (VD_FORCE_DIST=1 puts the exchanges in the plan)")
+    ap.add_argument("--expect-tuned", type=int, default=None)
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    import torch
+    from viddet_amd import lib as L
+    from viddet_amd import model as M
+
+    if a.syncbn:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", "29563")
+        torch.distributed.init_process_group("gloo", rank=0, world_size=1)
+    classes = ["c%d" % i for i in range(a.classes)]
+    norm = dict(norm_layer="syncbn", norm_kwargs=dict(scope=a.syncbn)) if a.syncbn else {}
+    if a.noback:
+        net = M.yolo3_no_backbone(classes, **norm)
+    else:
+        net = M.yolo3_darknet53(classes, freeze_base=a.freeze_base, k=a.k, k_join_type=a.join, k_join_pos=a.pos,
+                                block_conv_type=a.block, t_out=a.t_out, corr_pos=a.corr_pos, corr_d=a.corr_d, **norm)
+    if a.range_exact:
+        bn = [n for n in net.conv_nodes if n.bn]
+        net._range_exact.update([bn[3].dst, "dz:" + bn[6].name])
+    if a.storage == "bf16":
+        net.set_storage("bf16")
+    # (revisions before the two storages shared one builder have _build_train_bf16)
+    build = getattr(net, "_build_train_bf16", None) if a.storage == "bf16" else None
+    tp = (build or net._build_train)(a.batch, a.size, a.size)
+    torch.cuda.synchronize()
+
+    named = []                      # (base, bytes, name)
+    def name(label, t):
+        if torch.is_tensor(t) and t.is_cuda and t.numel():
+            named.append((t.data_ptr(), t.numel() * t.element_size(), label))
+    for k, t in tp["bufs"].items():
+        name(k, t)
+    for k in ("weights", "grads"):
+        name(k, getattr(net, k))
+    for k in ("ws", "losses"):
+        name(k, tp[k])
+    for n in net.nodes:
+        for k, t in vars(n).items():
+            name(n.name + "." + k, t)
+    labels = {}
+
+    def ptr(p):
+        if not p:
+            return None
+        hits = [(-base, nb, label) for base, nb, label in named if base <= p < base + nb]
+        if hits:                    # the innermost view: the highest base, then the smallest extent
+            nbase, _, label = min(hits)
+            return "%s+%d" % (label, p + nbase)
+        return labels.setdefault(("ptr", p), "ptr%d" % len(labels))
+
+    par = list(getattr(net, "_par_streams", None) or [])
+
+    def role(st):
+        if st is None:
+            return "main"
+        return next(("parity%d" % (i + 1) for i, s in enumerate(par) if s is st), "side")
+
+    def val(v, ty):
+        if isinstance(v, M.Slot):
+            return "slot:" + slot_of[id(v)]
+        if ty is C.c_void_p:
+            return ptr(v)
+        if hasattr(v, "_obj"):      # C.byref(...)
+            return val(v._obj, type(v._obj))
+        if isinstance(ty, type) and issubclass(ty, C.Array):
+            return [val(x, ty._type_) for x in v]
+        if isinstance(ty, type) and issubclass(ty, C.Structure):
+            return {f: val(getattr(v, f), t) for f, t in ty._fields_}
+        return v
+
+    def py(fn, kind):
+        code = fn.__code__
+        held = dict(zip(code.co_freevars, [c.cell_contents for c in fn.__closure__ or ()]))
+        if fn.__defaults__:
+            held.update(zip(code.co_varnames[code.co_argcount - len(fn.__defaults__):code.co_argcount], fn.__defaults__))
+        out = {kind: "record" if "record" in code.co_names else "wait" if "wait_event" in code.co_names else "call"}
+        for k in sorted(held):
+            v = held[k]
+            if isinstance(v, torch.cuda.Event):
+                out[k] = labels.setdefault(("event", id(v)), "event%d" % len(labels))
+            elif isinstance(v, torch.cuda.Stream):
+                out[k] = role(v)
+            elif torch.is_tensor(v):
+                out[k] = ptr(v.data_ptr())
+            elif isinstance(v, (bool, int, float)):
+                out[k] = v
+        return out
+
+    slot_of = {id(s): k for k, s in tp["slots"].items()}
+    doc, nrec = [], 0
+    for phase in ("fwd", "bwd"):
+        for seg in tp[phase]:
+            if not isinstance(seg, M.Program):
+                doc.append({"phase": phase, "segment": py(seg, "py")})
+                continue
+            recs = []
+            for (fname, fn, args), meta, st in zip(seg.recs, seg.meta, seg.streams):
+                if fname is None:
+                    recs.append(py(fn, "collective" if (meta or {}).get("kind") == "collective" else "py"))
+                else:
+                    sig = L.SIGNATURES[fname][1]
+                    recs.append({"fn": fname, "args": [val(v, t) for v, t in zip(args, sig)], "meta": meta, "stream": role(st)})
+            nrec += len(recs)
+            doc.append({"phase": phase, "records": recs})
+    with open(a.out, "w") as f:
+        json.dump(doc, f, sort_keys=True, indent=0)
+    tuned = M._TUNE_CACHE.tuned
+    print("%s: %d records, %d new tuning-table entries" % (a.out, nrec, tuned))
+    if a.expect_tuned is not None and tuned != a.expect_tuned:
+        sys.exit("expected %d new tuning-table entries" % a.expect_tuned)
+
+
+if __name__ == "__main__":
+    main()

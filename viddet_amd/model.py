@@ -291,6 +291,11 @@ def _fuse_bwd_s2():
     return __import__('os').environ.get('VD_FUSE_BWD_S2', '1') == '1'
 
 
+def _bf16_pitch(c):
+    """row pitch of a head tensor in bf16-storage training: the K dimension of its data gradient (32 or runs of 64)"""
+    return c if (c == 32 or c % 64 == 0) else round_up(c, 64)
+
+
 
 def fp32_math():
     """Arithmetic of the fp32 convolution products (include/viddet_hip.h VD_MATH_SPLIT): 'native' = fp32 MFMA,
@@ -1254,26 +1259,34 @@ class YOLOV3(object):
             self._wamax_dirty = False
 
     # ------------------------------------------------------------------ buffers
-    def _buffers(self, key, B, H, W, train):
-        ck = ('buf', B, H, W, train)
+    def _buffers(self, key, B, H, W, train, bf16=False):
+        """Activation (and in training gradient) tensors of one input shape.  bf16: the tensors of bf16-storage training -
+        bf16 activations and gradients, no max-abs slots; the head logits stay fp32 and the heads take the bf16 pitch
+        (_bf16_pitch), zero-filled so that the logits' pad columns stay 0."""
+        ck = ('buf', B, H, W, train) + (('bf16',) if bf16 else ())
         if ck in self._programs:
             return self._programs[ck]
         dev = self.device
+        dt = torch.bfloat16 if bf16 else torch.float32
+        zeroed = set(self.head_names) | {'d:' + h for h in self.head_names} if bf16 else set()
         bufs = {}
         for name, (c, div, ld, fr) in self.tensors.items():
             if name == 'in':
                 bufs['in'] = torch.empty(B * fr, 3, H, W, device=dev)      # (B,K,3,H,W) folded: frame n = b*K + k
-                continue
-            bufs[name] = torch.empty(B * fr, H // div, W // div, ld, device=dev)
+            elif name in zeroed:
+                bufs[name] = torch.zeros(B * fr, H // div, W // div, _bf16_pitch(ld), device=dev)
+            else:
+                bufs[name] = torch.empty(B * fr, H // div, W // div, ld, dtype=dt, device=dev)
         if self.noback:
             for nm, c_, d_ in ROUTE_TENSORS:                                   # NCHW staging of the three inputs
                 bufs['in:' + nm] = torch.empty(B, c_, H // d_, W // d_, device=dev)
         # max-abs slots (operand scales of the fp16-split arithmetic): one set per activation tensor, and in training
         # per conv node for the gradient dz it consumes; zeroed by the first record of every forward program
-        names = [nm for nm in self.tensors if nm != 'in'] + (['dz:' + n.name for n in self.conv_nodes] if train else [])
-        bufs['amax'] = torch.zeros(len(names) * L.AMAX_FLOATS, device=dev)
-        for i, nm in enumerate(names):
-            bufs['amax:' + nm] = bufs['amax'][i * L.AMAX_FLOATS:(i + 1) * L.AMAX_FLOATS]
+        if not bf16:
+            names = [nm for nm in self.tensors if nm != 'in'] + (['dz:' + n.name for n in self.conv_nodes] if train else [])
+            bufs['amax'] = torch.zeros(len(names) * L.AMAX_FLOATS, device=dev)
+            for i, nm in enumerate(names):
+                bufs['amax:' + nm] = bufs['amax'][i * L.AMAX_FLOATS:(i + 1) * L.AMAX_FLOATS]
         for n in self.conv_nodes:
             if getattr(n, 'tvalid', False):        # the 'same'-padded temporal conv output the valid frames are taken from
                 bufs['zf:' + n.dst] = torch.empty(B * n.fr, H // n.div_out, W // n.div_out, n.cout, device=dev)
@@ -1290,16 +1303,16 @@ class YOLOV3(object):
                     bufs['z:' + n.dst] = torch.empty_like(bufs[n.dst])
             for name in self.tensors:
                 if name != 'in':
-                    bufs['d:' + name] = torch.empty_like(bufs[name])
+                    bufs['d:' + name] = (torch.zeros_like if 'd:' + name in zeroed else torch.empty_like)(bufs[name], dtype=dt)
             mx = max(bufs[n.dst].numel() for n in self.conv_nodes)
-            bufs['dz'] = torch.empty(mx, device=dev)
-            bufs['dz2'] = torch.empty(mx, device=dev)
-            bufs['tmp'] = torch.empty(mx, device=dev)
+            bufs['dz'] = torch.empty(mx, dtype=dt, device=dev)
+            bufs['dz2'] = torch.empty(mx, dtype=dt, device=dev)
+            bufs['tmp'] = torch.empty(mx, dtype=dt, device=dev)
         # The plan-time autotuner times candidate kernels in place on these buffers.  Fresh allocations are zero pages, and on
         # all-zero operands the chip holds a ~20 % higher clock - for every candidate, but not equally: stand-alone the 256x128
         # tiles on the two MFMA shapes tie at 310 TF on zeros and differ by 8 % (255 vs 275) on real data.  Tune on noise.
         for nm, t in bufs.items():
-            if torch.is_tensor(t) and t.dtype == torch.float32 and not nm.startswith('amax'):
+            if torch.is_tensor(t) and t.dtype == dt and not nm.startswith('amax') and nm not in zeroed:
                 t.normal_()
         self._programs[ck] = bufs
         return bufs
@@ -1821,18 +1834,35 @@ class YOLOV3(object):
         return n.stem or n.stride == 2
 
     def _build_train(self, B, H, W):
-        bufs = self._buffers('train', B, H, W, True)
-        dev = self.device
+        """The training plan: forward with the BatchNorm statistics, the loss, then the fixed reverse pass with the
+        weight-gradient GEMMs on a side stream and the bucketed gradient all-reduce queued behind them.  The storage of the
+        activations and their gradients (set_storage) changes the leaves of the schedule only: bf16 storage runs the `_bf16`
+        twins of the elementwise kernels, has no max-abs slots (the fp16-split arithmetic is fp32's) and runs every
+        convolution as vd_conv_igemm_bf16 on bf16 weight images (packed by _refresh_dgrad)."""
+        bf16 = getattr(self, 'storage', 'fp32') == 'bf16'
+        sfx, esz = ('_bf16', 2) if bf16 else ('', 4)
+        dt = torch.bfloat16 if bf16 else torch.float32
+        bufs = self._buffers('train', B, H, W, True, bf16=bf16)
+        dev, lib = self.device, L.load()
+        amx = lambda t: bufs['amax:' + t].data_ptr()
+        amx_arg = lambda t: () if bf16 else (None if t is None else amx(t),)   # the fp32 kernels' trailing max-abs slots
         ws_bytes = 1 << 20
         for n in self.conv_nodes:
             Hi, Wi = H // n.div_in, W // n.div_in
             Ho, Wo = H // n.div_out, W // n.div_out
             if n.stem:
-                ws_bytes = max(ws_bytes, int(L.load().vd_stem_wgrad_ws_bytes(B * n.fr, Hi, Wi)))
+                ws_bytes = max(ws_bytes, int(lib.vd_stem_wgrad_ws_bytes(B * n.fr, Hi, Wi)))
+            elif bf16:
+                wd_ = WgradDesc()
+                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci, wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = B, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.co_pad
+                ops._set_taps(wd_, n.taps())
+                for fl_ in (0, L.WGRAD_HALO):          # the halo-ring kernel picks its own split count
+                    wd_.in_stride, wd_.Kfr, wd_.flags = n.stride, 1, L.STORE_BF16 | L.MATH_BF16 | fl_
+                    ws_bytes = max(ws_bytes, int(lib.vd_conv_wgrad_ws_bytes(C.byref(wd_))))
             else:
                 ws_bytes = max(ws_bytes, ops.wgrad_ws_bytes(B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.k, n.stride,
                                                             n.pad, n.kd, n.pad_d))
-            ws_bytes = max(ws_bytes, ops.bn_stats_ws_bytes(B * n.fr * Ho * Wo, n.co_pad))
+            ws_bytes = max(ws_bytes, ops.bn_stats_ws_bytes(B * n.fr * Ho * Wo, _bf16_pitch(n.co_pad) if bf16 else n.co_pad))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -1852,18 +1882,61 @@ class YOLOV3(object):
                 # (+ 8 + 4 x 64 rows: every parity launch of every frame chunk rounds its tile count up separately)
                 smax = max(smax, ((B * n.fr * (H // n.div_out) * (W // n.div_out) + 63) // 64 + 8 + 256) * 2 * n.cout)
         stats_ws = torch.empty(smax, device=dev)
+        # bf16 storage: the forward weight images.  The conv weights live fwd-packed [co_pad][T * Ci] in the arena and need
+        # no padding here (every Ci is 32 or a multiple of 64), so ONE conversion of the arena's weight range makes all of them
+        wb_arena = torch.empty(self.n_weight, dtype=dt, device=dev) if bf16 else None
+
+        def tune(d, of32=0):
+            """fix the tile (and arithmetic) of a conv record, hence its number of M tiles"""
+            if bf16:
+                self._tune_bf16_desc(d, of32)
+            else:
+                autotune_desc(d)
+        mtiles = lib.vd_conv_igemm_bf16_mtiles if bf16 else lib.vd_conv_igemm_mtiles
+
+        def add_conv(d, of32=0, **kw):
+            if bf16:
+                seg.add('vd_conv_igemm_bf16', C.byref(d), of32, **kw)
+            else:
+                seg.add('vd_conv_igemm', C.byref(d), **kw)
+
+        def fwd_desc(n, out):
+            """the forward conv record of node n into `out`"""
+            if not bf16:
+                d = self._conv_desc(n, bufs, B, H, W, out, shift=n.bias if n.head else None)
+                seg.hold(d)
+                return d
+            wb = wb_arena[n.w_off:n.w_off + n.w_numel]
+            assert n.w_numel == n.co_pad * n.T * n.cin and n.w_off % 8 == 0
+            Ho, Wo = H // n.div_out, W // n.div_out
+            d = ConvDesc()
+            self._set_streamk(d, 0)
+            d.in_, d.wp, d.out = bufs[n.src].data_ptr(), wb.data_ptr(), out.data_ptr()
+            d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = B, H // n.div_in, W // n.div_in, n.cin, Ho, Wo, n.stride
+            ops._set_taps(d, n.taps())
+            d.Kfr, d.Ho, d.Wo, d.Co = 1, Ho, Wo, n.co_pad
+            d.out_stride, d.out_oy, d.out_ox, d.slope = 1, 0, 0, LEAKY_SLOPE
+            d.ldo = d.ldr = out.shape[-1]                  # (the head: its bf16 pitch)
+            if n.head:
+                d.flags, d.shift = EPI_AFFINE, n.bias.data_ptr()
+            seg.hold(d, wb)
+            return d
+
         # ---- forward: list of segments; a segment is a Program or a python callable (collectives)
         fwd, seg = [], Program()
-        self._add_input_stage(seg, bufs, B, H, W)
-
-        amx = lambda t: bufs['amax:' + t].data_ptr()
+        if not bf16:
+            self._add_input_stage(seg, bufs, B, H, W)
         for n in self.nodes:
             if isinstance(n, UpcatNode):
                 o = bufs[n.dst]
+                cw = 2 if bf16 else 1                      # bf16: a copy of 4-byte words, two channels each
                 seg.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
-                        o.shape[1], o.shape[2], n.cu, n.cr)
-                seg.add('vd_amax_merge', amx(n.up), amx(n.route), amx(n.dst))
+                        o.shape[1], o.shape[2], n.cu // cw, n.cr // cw)
+                if not bf16:
+                    seg.add('vd_amax_merge', amx(n.up), amx(n.route), amx(n.dst))
                 continue
+            if bf16 and not isinstance(n, ConvNode):
+                raise NotImplementedError("bf16-storage training: node type %s" % type(n).__name__)
             if isinstance(n, PoolNode):
                 o, xs = bufs[n.dst], bufs[n.src]
                 if n.type == 2:
@@ -1884,42 +1957,36 @@ class YOLOV3(object):
             Ho, Wo = H // n.div_out, W // n.div_out
             tvalid = getattr(n, 'tvalid', False)
             M = B * (n.fr - 2 if tvalid else n.fr) * Ho * Wo
+            meta = self._flops(n, B, H, W, 'fwd', esz)
             if n.head:
-                d = self._conv_desc(n, bufs, B, H, W, bufs[n.dst], shift=n.bias)
-                seg.hold(d)
-                seg.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
+                d = fwd_desc(n, bufs[n.dst])
+                if bf16:
+                    tune(d, 1)
+                add_conv(d, 1, meta=meta)
                 continue
             z = bufs['z:' + n.dst]
             if n.stem:
                 # raw conv output + one row of BatchNorm partial sums per 256-pixel block (vd_stem.hip)
-                nb = L.load().vd_stem_conv_blocks(B * n.fr, H, W)
-                assert nb * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
-                self._add_stem(seg, n, bufs, B, H, W, z, stats=stats_ws.data_ptr())
-                table_rows = nb
-                d = None
-            else:
-                d = self._conv_desc(n, bufs, B, H, W, bufs['zf:' + n.dst] if tvalid else z)
-                seg.hold(d)
-            if d is None:
-                pass
+                table_rows = lib.vd_stem_conv_blocks(B * n.fr, H, W)
+                assert table_rows * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
+                self._add_stem(seg, n, bufs, B, H, W, z, bf16=bf16, stats=stats_ws.data_ptr())
             elif tvalid:
                 # 'same'-padded temporal conv on all frames, the valid ones sliced out, statistics over those
                 zf = bufs['zf:' + n.dst]
-                seg.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
+                add_conv(fwd_desc(n, zf), meta=meta)
                 seg.add('vd_frame_slice', zf.data_ptr(), z.data_ptr(), B, n.fr, 1, n.fr - 2, zf[0].numel(), 0)
                 seg.add('vd_bn_stats', z.data_ptr(), M, n.cout, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
                 table_rows = None
-            elif self.fuse_bn_stats:
-                table_rows = None
+            elif bf16 or self.fuse_bn_stats:
                 # BN statistics ride in the conv epilogue: one row of partial sums per M tile, reduced in fp64
+                d = fwd_desc(n, z)
                 d.stats_part = stats_ws.data_ptr()
-                autotune_desc(d)                                   # fixes the tile, hence the number of M tiles
-                mt = L.load().vd_conv_igemm_mtiles(C.byref(d))
-                assert mt * 2 * n.cout * 4 <= stats_ws.numel() * 4, "stats workspace too small"
-                seg.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
-                table_rows = mt
+                tune(d)
+                table_rows = mtiles(C.byref(d))
+                assert table_rows * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
+                add_conv(d, meta=meta)
             else:
-                seg.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
+                add_conv(fwd_desc(n, z), meta=meta)
                 seg.add('vd_bn_stats', z.data_ptr(), M, n.cout, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
                 table_rows = None
             count = float(M)
@@ -1934,28 +2001,30 @@ class YOLOV3(object):
                     seg.add('vd_bn_sum_partials', stats_ws.data_ptr(), table_rows, n.cout, n.sums.data_ptr(), ws.data_ptr(),
                             ws_bytes)
                 if self._syncbn(n):
+                    # SyncBN (train_yolov3.py:347-354): the fp64 [sum x, sum x^2] summed over the ranks, then one finalize
+                    # on the global count
                     seg.add_coll(self._syncbn_exchange(n.sums))
                     count = float(M * world)
                 seg.add('vd_bn_finalize', n.sums.data_ptr(), count, n.cout, *fin)
             res = bufs[n.residual].data_ptr() if n.residual else None
-            seg.add('vd_bn_apply_leaky', z.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(), res,
-                    bufs[n.dst].data_ptr(), M, n.cout, LEAKY_SLOPE, amx(n.dst),
-                    meta=dict(node=n.name, bytes=4.0 * M * n.cout * (3 if n.residual else 2),
-                              single_conv_consumer=n.dst in self.single_conv_consumer_tensors()))
+            seg.add('vd_bn_apply_leaky' + sfx, z.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(), res,
+                    bufs[n.dst].data_ptr(), M, n.cout, LEAKY_SLOPE, *amx_arg(n.dst),
+                    meta=dict(node=n.name, bytes=float(esz) * M * n.cout * (3 if n.residual else 2),
+                              single_conv_consumer=not bf16 and n.dst in self.single_conv_consumer_tensors()))
         # loss (targets are late-bound)
         grids = self._grid(H, W)
-        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
+        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, bufs[self.head_names[0]].shape[-1],
                                 STRIDES[::-1], ANCHORS[::-1], B * self._head_frames, self.num_class)
         slots = dict(gt=Slot(), M=Slot(), obj=Slot(), ctr=Slot(), scl=Slot(), wgt=Slot(), cls=Slot(), smooth=Slot())
         losses = torch.zeros(B * self._head_frames, 4, device=dev)
         dh = (C.c_void_p * 3)(*[bufs['d:' + h].data_ptr() for h in self.head_names])
         head_node = {m.dst: m for m in self.conv_nodes if m.head}
-        dha = (C.c_void_p * 3)(*[amx('dz:' + head_node[h].name) for h in self.head_names])   # max-abs of the three dhead
+        dha = None if bf16 else (C.c_void_p * 3)(*[amx('dz:' + head_node[h].name) for h in self.head_names])   # max-abs of the three dhead
         lws = torch.empty(max(16, ops.yolo_loss_ws_bytes(hd)), dtype=torch.uint8, device=dev)
         seg.hold(hd, dh, dha, lws)
-        seg.add('vd_yolo_loss_fwd_bwd', C.byref(hd), slots['gt'], slots['M'], slots['obj'], slots['ctr'], slots['scl'],
+        seg.add('vd_yolo_loss_fwd_bwd' + sfx, C.byref(hd), slots['gt'], slots['M'], slots['obj'], slots['ctr'], slots['scl'],
                 slots['wgt'], slots['cls'], float(self._ignore_iou_thresh), slots['smooth'], losses.data_ptr(),
-                C.byref(dh), None, C.byref(dha), lws.data_ptr(), lws.numel())
+                C.byref(dh), None, *([] if bf16 else [C.byref(dha)]), lws.data_ptr(), lws.numel())
         fwd.append(seg)
 
         # ---- backward
@@ -2018,14 +2087,17 @@ class YOLOV3(object):
         wtrain = [m for m in self.conv_nodes if self._node_trainable(m)[0]]
         first_wtrain = wtrain[0] if wtrain else None       # its weight gradient is the last one backward produces
 
+        def copy_grad(src, dst):
+            """dst = src (the identity form of the BatchNorm apply kernel)"""
+            seg.add('vd_bn_apply_leaky' + sfx, src.data_ptr(), self._ones(src.shape[-1]).data_ptr(),
+                    self._zeros(src.shape[-1]).data_ptr(), None, dst.data_ptr(), src.numel() // src.shape[-1], src.shape[-1],
+                    1.0, *amx_arg(None))
+
         def materialize(name):
             if name in alias:
-                src = alias.pop(name)
-                seg.add('vd_bn_apply_leaky', src.data_ptr(), self._ones(src.shape[-1]).data_ptr(),
-                        self._zeros(src.shape[-1]).data_ptr(), None, bufs['d:' + name].data_ptr(),
-                        src.numel() // src.shape[-1], src.shape[-1], 1.0, None)
+                copy_grad(alias.pop(name), bufs['d:' + name])
 
-        def grad_into(name, numel, can_alias=False):
+        def grad_into(name, can_alias=False):
             """Return (dst_ptr, accumulate?) for a producer of d:name."""
             if name in written:
                 if not can_alias:
@@ -2034,28 +2106,36 @@ class YOLOV3(object):
             written.add(name)
             return bufs['d:' + name], False
 
+        def add_grad(dsrc, acc, launch):
+            """launch(ptr) writes a gradient contribution to d:src: straight into dsrc, or into tmp then added to dsrc"""
+            target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
+            launch(target.data_ptr())
+            if acc:
+                seg.add('vd_add' + sfx, dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
+
+        def fuse_bn_bwd(d, m, z_off, part_off):
+            """the BatchNorm-backward reductions of node m in the epilogue of data-gradient record d"""
+            d.bs_z = bufs['z:' + m.dst].data_ptr() + z_off
+            d.bs_scale, d.bs_shift = m.b_scale.data_ptr(), m.b_shift.data_ptr()
+            d.bs_mean, d.bs_invstd = m.b_mean.data_ptr(), m.b_invstd.data_ptr()
+            d.bs_part, d.bs_slope = stats_ws.data_ptr() + part_off, LEAKY_SLOPE
+
         for n in reversed(self.nodes):
             if isinstance(n, UpcatNode):
                 if not tgrad[n.dst]:
                     continue
                 dout = bufs['d:' + n.dst]
-                dup_p = drt_p = None                       # NULL = that half is not needed (frozen upstream)
-                acc_r = False
+                dup_p = None                               # NULL = that half is not needed (frozen upstream)
                 if tgrad[n.up]:
-                    dup, acc_u = grad_into(n.up, 0)
+                    dup, acc_u = grad_into(n.up)
                     assert not acc_u
                     dup_p = dup.data_ptr()
+                launch = lambda p: seg.add('vd_upsample2x_concat_bwd' + sfx, dout.data_ptr(), dup_p, p, B * n.fr,
+                                           dout.shape[1], dout.shape[2], n.cu, n.cr)
                 if tgrad[n.route]:
-                    drt, acc_r = grad_into(n.route, 0)
-                    drt_p = drt.data_ptr()
-                if acc_r:
-                    tmp = bufs['tmp'][:drt.numel()]
-                    seg.add('vd_upsample2x_concat_bwd', dout.data_ptr(), dup_p, tmp.data_ptr(), B * n.fr,
-                            dout.shape[1], dout.shape[2], n.cu, n.cr)
-                    seg.add('vd_add', drt.data_ptr(), tmp.data_ptr(), drt.data_ptr(), drt.numel())
-                elif dup_p or drt_p:
-                    seg.add('vd_upsample2x_concat_bwd', dout.data_ptr(), dup_p, drt_p, B * n.fr,
-                            dout.shape[1], dout.shape[2], n.cu, n.cr)
+                    add_grad(*grad_into(n.route), launch)
+                elif dup_p:
+                    launch(None)
                 continue
             if isinstance(n, SelNode):
                 if not tgrad[n.src]:
@@ -2063,11 +2143,9 @@ class YOLOV3(object):
                 assert n.dst in written, n.name
                 materialize(n.dst)
                 dout = bufs['d:' + n.dst]
-                dsrc, acc = grad_into(n.src, 0)
-                target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
-                seg.add('vd_frame_slice', dout.data_ptr(), target.data_ptr(), B, n.K, n.k0, n.kc, dsrc[0].numel(), 1)
-                if acc:
-                    seg.add('vd_add', dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
+                dsrc, acc = grad_into(n.src)
+                add_grad(dsrc, acc, lambda p: seg.add('vd_frame_slice', dout.data_ptr(), p, B, n.K, n.k0, n.kc,
+                                                      dsrc[0].numel(), 1))
                 continue
             if isinstance(n, AddNode):
                 if not tgrad[n.dst]:
@@ -2078,29 +2156,25 @@ class YOLOV3(object):
                 for t_ in (n.a, n.b):
                     if not tgrad[t_]:
                         continue
-                    dsrc, acc = grad_into(t_, 0)
+                    dsrc, acc = grad_into(t_)
                     if acc:
                         seg.add('vd_add', dsrc.data_ptr(), dout.data_ptr(), dsrc.data_ptr(), dsrc.numel())
-                    else:                      # a copy (the identity form of the BatchNorm apply kernel)
-                        seg.add('vd_bn_apply_leaky', dout.data_ptr(), self._ones(dout.shape[-1]).data_ptr(),
-                                self._zeros(dout.shape[-1]).data_ptr(), None, dsrc.data_ptr(),
-                                dout.numel() // dout.shape[-1], dout.shape[-1], 1.0, None)
+                    else:
+                        copy_grad(dout, dsrc)
                 continue
             if isinstance(n, PoolNode):
                 if not tgrad[n.src]:
                     continue
                 dout = bufs['d:' + n.dst]
                 assert n.dst in written, n.name
-                dsrc, acc = grad_into(n.src, 0)
+                dsrc, acc = grad_into(n.src)
                 am = bufs['am:' + n.dst].data_ptr() if n.type == 0 else None
-                target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
                 if n.type == 2:
-                    seg.add('vd_temporal_cat', dout.data_ptr(), target.data_ptr(), B, n.K, dsrc.shape[1] * dsrc.shape[2],
-                            dsrc.shape[3], 1)
+                    launch = lambda p: seg.add('vd_temporal_cat', dout.data_ptr(), p, B, n.K, dsrc.shape[1] * dsrc.shape[2],
+                                               dsrc.shape[3], 1)
                 else:
-                    seg.add('vd_temporal_pool_bwd', dout.data_ptr(), am, target.data_ptr(), B, n.K, dout[0].numel(), n.type)
-                if acc:
-                    seg.add('vd_add', dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
+                    launch = lambda p: seg.add('vd_temporal_pool_bwd', dout.data_ptr(), am, p, B, n.K, dout[0].numel(), n.type)
+                add_grad(dsrc, acc, launch)
                 continue
             if isinstance(n, CorrNode):
                 if not tgrad[n.src]:
@@ -2108,12 +2182,9 @@ class YOLOV3(object):
                 assert n.dst in written, n.name
                 materialize(n.dst)
                 dout, xs = bufs['d:' + n.dst], bufs[n.src]
-                dsrc, acc = grad_into(n.src, 0)
-                target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
-                seg.add('vd_corr_bwd', dout.data_ptr(), xs.data_ptr(), target.data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C,
-                        n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd'))
-                if acc:
-                    seg.add('vd_add', dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
+                dsrc, acc = grad_into(n.src)
+                add_grad(dsrc, acc, lambda p: seg.add('vd_corr_bwd', dout.data_ptr(), xs.data_ptr(), p, B, n.K, xs.shape[1],
+                                                      xs.shape[2], n.C, n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd')))
                 continue
             Hi, Wi = H // n.div_in, W // n.div_in
             Ho, Wo = H // n.div_out, W // n.div_out
@@ -2127,14 +2198,20 @@ class YOLOV3(object):
             materialize(n.dst)
             if n.head:
                 dz = dy
-                # bias gradient = per-channel sum of dz (reuses the BN column-sum kernels)
-                seg.add('vd_bn_stats', dz.data_ptr(), M, n.co_pad, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                seg.add('vd_bn_param_grads', n.sums.data_ptr(), n.co_pad, bufs['tmp'].data_ptr(), n.gbias.data_ptr())
+                # bias gradient = per-channel sum of dz over its row pitch (reuses the BN column-sum kernels); the dgamma
+                # slot of the parameter-gradient kernel is scratch
+                sums = n.sums
+                if bf16:                   # (the bf16 pitch may be wider than n.sums)
+                    if getattr(n, 'sums_b', None) is None or n.sums_b.numel() != 2 * dz.shape[-1]:
+                        n.sums_b = torch.zeros(2 * dz.shape[-1], dtype=torch.float64, device=dev)
+                    sums = n.sums_b
+                seg.add('vd_bn_stats' + sfx, dz.data_ptr(), M, dz.shape[-1], sums.data_ptr(), ws.data_ptr(), ws_bytes)
+                seg.add('vd_bn_param_grads', sums.data_ptr(), n.co_pad, bufs['tmp'].data_ptr(), n.gbias.data_ptr())
             else:
                 if n.residual and tgrad[n.residual]:
-                    dres, acc = grad_into(n.residual, 0)
+                    dres, acc = grad_into(n.residual)
                     if acc:
-                        seg.add('vd_add', dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
+                        seg.add('vd_add' + sfx, dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
                     else:
                         alias[n.residual] = dy     # first producer of the skip gradient: it IS dy (no copy, see alias)
                         if not self.alias_skip_grad:
@@ -2143,21 +2220,20 @@ class YOLOV3(object):
                 slot = n_dz[0] % 2
                 n_dz[0] += 1
                 dz = dz_bufs[slot][:M * n.cout].view(-1, Ho, Wo, n.cout)
-                if n.name not in fused_bwd:
-                    seg.add('vd_bn_bwd_reduce', z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
+                if n.name not in fused_bwd:      # (fused: sums and gamma / beta gradients came with the table reduction)
+                    seg.add('vd_bn_bwd_reduce' + sfx, z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
                             n.b_mean.data_ptr(), n.b_invstd.data_ptr(), M, n.cout, LEAKY_SLOPE, n.sums2.data_ptr(),
                             ws.data_ptr(), ws_bytes)
-                if n.name not in fused_bwd:      # (fused: the gamma/beta gradients came with the table reduction)
                     seg.add('vd_bn_param_grads', n.sums2.data_ptr(), n.cout, n.ggamma.data_ptr(), n.gbeta.data_ptr())
                 count = float(M)
-                if self._syncbn(n):
+                if self._syncbn(n):          # [sum g, sum g xhat] over the ranks (the local gamma / beta gradients came first)
                     seg.add_coll(self._syncbn_exchange(n.sums2))
                     count = float(M * world)
                 if side is not None and dz_free[slot] is not None:
                     seg.add_py(ev_wait(dz_free[slot], False))       # the wgrad that read this scratch has finished
-                seg.add('vd_bn_bwd_apply', z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
+                seg.add('vd_bn_bwd_apply' + sfx, z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
                         n.b_mean.data_ptr(), n.b_invstd.data_ptr(), n.sums2.data_ptr(), count, M, n.cout, LEAKY_SLOPE,
-                        dz.data_ptr(), amx('dz:' + n.name))
+                        dz.data_ptr(), *amx_arg('dz:' + n.name))
                 if tvalid:
                     # the gradient of the frame slice: dz of the valid frames, zeros on the two border frames; the conv's
                     # weight / data gradients then are those of the 'same'-padded conv
@@ -2165,80 +2241,73 @@ class YOLOV3(object):
                     seg.add('vd_frame_slice', dz.data_ptr(), dzf.data_ptr(), B, n.fr, 1, n.fr - 2, dzf[0].numel(), 1)
                     dz = dzf
             # weight gradient straight into the gradient arena (same fwd-packed layout as the weights)
-            if n.stem and w_train:
-                # both operands straight from global memory: the NCHW batch and dz (vd_stem.hip)
-                wargs = ('vd_stem_wgrad', bufs['in'].data_ptr(), dz.data_ptr(), n.co_pad, n.gwp.data_ptr(), B * n.fr, Hi, Wi)
-                if side is not None:
-                    e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
-                    seg.add_py(ev_record(e_ready, False))
-                    seg.add_py(ev_wait(e_ready, True))
-                    seg.add(*wargs, ws_w.data_ptr(), ws_bytes, meta=self._flops(n, B, H, W, 'wgrad'), stream=side)
-                    seg.add_py(ev_record(e_done, True))
-                    seg.hold(e_ready, e_done)
-                    dz_free[slot] = e_done
-                    last_side[0] = e_done
-                else:
-                    seg.add(*wargs, ws.data_ptr(), ws_bytes, meta=self._flops(n, B, H, W, 'wgrad'))
-                bucket_acc[0] += n.w_numel
-                if self.bucketed_allreduce:            # the stem is the first conv: its bucket closes the arena
-                    seg.add_py(self._bucket_launcher(n.w_off, bucket_hi[0], side))
-                    bucket_hi[0], bucket_acc[0] = n.w_off, 0
-                continue
-            if n.stem:
-                continue
             if w_train:
-                wd_ = WgradDesc()
-                xin = bufs[n.src]
-                wd_.in_, wd_.dout, wd_.dwp = xin.data_ptr(), dz.data_ptr(), n.gwp.data_ptr()
-                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = B * n.fr, Hi, Wi, n.ci_eff
-                wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Ho, Wo, n.co_pad, n.co_pad
-                wd_.in_stride = n.stride
-                ops._set_taps(wd_, n.taps())
-                wd_.Kfr, wd_.splits = (n.fr if n.kd > 1 else 1), 0
-                wd_.amax_in, wd_.amax_dout = self._amax_or_none(bufs, n.src), self._amax_or_none(bufs, 'dz:' + n.name)
-                autotune_wgrad(wd_, ws.data_ptr(), ws_bytes)
-                seg.hold(wd_)
+                if n.stem:
+                    # both operands straight from global memory: the NCHW batch and dz (vd_stem.hip)
+                    wargs = ('vd_stem_wgrad' + sfx, bufs['in'].data_ptr(), dz.data_ptr(), n.co_pad, n.gwp.data_ptr(),
+                             B * n.fr, Hi, Wi)
+                else:
+                    wd_ = WgradDesc()
+                    wd_.in_, wd_.dout, wd_.dwp = bufs[n.src].data_ptr(), dz.data_ptr(), n.gwp.data_ptr()
+                    wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = B * n.fr, Hi, Wi, n.ci_eff
+                    wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Ho, Wo, n.co_pad, dz.shape[-1]
+                    wd_.in_stride = n.stride
+                    ops._set_taps(wd_, n.taps())
+                    wd_.Kfr, wd_.splits = (n.fr if n.kd > 1 else 1), 0
+                    if bf16:
+                        wd_.flags = L.STORE_BF16 | L.MATH_BF16
+                        autotune_wgrad_bf16(wd_, ws.data_ptr(), ws_bytes)
+                    else:
+                        wd_.amax_in, wd_.amax_dout = self._amax_or_none(bufs, n.src), self._amax_or_none(bufs, 'dz:' + n.name)
+                        autotune_wgrad(wd_, ws.data_ptr(), ws_bytes)
+                    seg.hold(wd_)
+                    wargs = ('vd_conv_wgrad', C.byref(wd_))
+                meta = self._flops(n, B, H, W, 'wgrad', esz)
                 if side is not None:
                     e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
                     seg.add_py(ev_record(e_ready, False))
                     seg.add_py(ev_wait(e_ready, True))
-                    seg.add('vd_conv_wgrad', C.byref(wd_), ws_w.data_ptr(), ws_bytes, meta=self._flops(n, B, H, W, 'wgrad'),
-                            stream=side)
+                    seg.add(*wargs, ws_w.data_ptr(), ws_bytes, meta=meta, stream=side)
                     seg.add_py(ev_record(e_done, True))
                     seg.hold(e_ready, e_done)
                     if not n.head:
                         dz_free[slot] = e_done
                     last_side[0] = e_done
                 else:
-                    seg.add('vd_conv_wgrad', C.byref(wd_), ws.data_ptr(), ws_bytes, meta=self._flops(n, B, H, W, 'wgrad'))
+                    seg.add(*wargs, ws.data_ptr(), ws_bytes, meta=meta)
                 # bucketed gradient all-reduce, overlapped with the rest of the backward pass: weight gradients complete
                 # in reverse arena order on the stream that runs the wgrad GEMMs, so every time a bucket (~32 MB) of the arena tail
                 # is final an async all-reduce of that contiguous range is queued behind them (RCCL syncs with that
                 # stream); allreduce_grads() later waits for the handles and reduces the small gamma/beta/bias range.
+                # The stem is the first conv: its bucket closes the arena.
                 bucket_acc[0] += n.w_numel
-                if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or n is first_wtrain):
+                if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or n is first_wtrain or n.stem):
                     lo, hi = n.w_off, bucket_hi[0]
                     seg.add_py(self._bucket_launcher(lo, hi, side))
                     bucket_hi[0], bucket_acc[0] = lo, 0
             if n.stem or n.src in self.input_tensors or not tgrad[n.src]:     # no gradient flows into the network inputs,
                 continue                                                       # nor below the last trainable parameter
             # data gradient into d:src
-            dsrc, acc = grad_into(n.src, 0, can_alias=True)
+            dsrc, acc = grad_into(n.src, can_alias=True)
             res_src = alias.pop(n.src) if n.src in alias else dsrc      # the skip gradient, still living in the block's dy
             plans = dgrad_plans(n.k, n.pad, n.stride, Hi, Wi, n.kd, n.pad_d)
             pm = producers.get(n.src)
             # the producer's BatchNorm-backward reductions ride in this data gradient's epilogue when it is the launch (or, for a
-            # stride-2 conv, the four parity launches) that completes dy of the producer's output
-            fuse_m = pm if (self.fuse_bn_bwd and pm is not None and (len(plans) == 1 or (n.kd == 1 and _fuse_bwd_s2())) and
-                            consumers[n.src][0] is n and pm.fr == n.fr) else None
+            # stride-2 conv, the four parity launches) that completes dy of the producer's output.  (bf16 storage: off by
+            # default, VD_FUSE_BWD_BF16=1: measured on one box, 416 / batch 64, 1992 frames/s with the stand-alone reduction
+            # passes against 1958 fused - the HBM-bound pass runs beside the side stream's MFMA-bound weight gradients, the
+            # fused epilogue lengthens the data gradients on the critical path)
+            fuse_m = pm if (pm is not None and consumers[n.src][0] is n and
+                            (__import__('os').environ.get('VD_FUSE_BWD_BF16', '0') == '1' if bf16 else
+                             self.fuse_bn_bwd and (len(plans) == 1 or (n.kd == 1 and _fuse_bwd_s2())) and pm.fr == n.fr)) else None
             bs_rows = 0
             # ---- a 3x3 / stride-2 data gradient as ONE launch (VD_CONV_PARITY4, vd_conv_par.hip) instead of four parity
             # launches that each gather and stage the whole dz: rows = positions of dz's grid, columns = (parity class,
             # channel), taps = the four offsets of a 2x2 window, zero (offset, class) weight blocks skipped.
             # VD_S2_FUSED=0 keeps the four launches (also: odd maps, other arithmetics, range-exact operands, pinned kernels).
             import os as _os
-            fused_s2 = (len(plans) == 4 and n.k == 3 and n.stride == 2 and n.pad == 1 and n.kd == 1 and Hi % 2 == 0 and Wi % 2 == 0 and
-                        _os.environ.get('VD_S2_FUSED', '1') == '1' and n.cin % 32 == 0 and
+            fused_s2 = (not bf16 and len(plans) == 4 and n.k == 3 and n.stride == 2 and n.pad == 1 and n.kd == 1 and
+                        Hi % 2 == 0 and Wi % 2 == 0 and _os.environ.get('VD_S2_FUSED', '1') == '1' and n.cin % 32 == 0 and
                         # (measured per layer, batch 64 / 416x416, four launches -> one: 32 channels 1.51 -> 1.12 ms, 64: 0.80 ->
                         # 0.80, 128: 0.55 -> 0.66, 256: 0.53 -> 0.59, 512: 0.47 -> 0.53 - the one launch stages all sixteen
                         # (offset, class) weight blocks for nine useful ones, which only pays where a parity launch has too few
@@ -2264,14 +2333,11 @@ class YOLOV3(object):
                     d.residual = res_src.data_ptr()
                 seg.hold(d, wp4)
                 if fuse_m is not None:
-                    d.bs_z = bufs['z:' + fuse_m.dst].data_ptr()
-                    d.bs_scale, d.bs_shift = fuse_m.b_scale.data_ptr(), fuse_m.b_shift.data_ptr()
-                    d.bs_mean, d.bs_invstd = fuse_m.b_mean.data_ptr(), fuse_m.b_invstd.data_ptr()
-                    d.bs_part, d.bs_slope = stats_ws.data_ptr(), LEAKY_SLOPE
+                    fuse_bn_bwd(d, fuse_m, 0, 0)
                 autotune_desc(d)                                   # fixes the tile, hence the rows of the partial table
                 if fuse_m is not None:
-                    mt = L.load().vd_conv_igemm_mtiles(C.byref(d))
-                    assert mt * 2 * fuse_m.cout * 4 <= stats_ws.numel() * 4, "stats workspace too small"
+                    mt = lib.vd_conv_igemm_mtiles(C.byref(d))
+                    assert mt * 2 * fuse_m.cout <= stats_ws.numel(), "stats workspace too small"
                     seg.add('vd_fill', stats_ws.data_ptr(), 0.0, mt * 2 * fuse_m.cout)     # column tiles narrower than Cin fill part of a row
                 seg.add('vd_conv_igemm', C.byref(d), meta=dict(
                     kind='dgrad', node=n.name, k=n.k, stride=n.stride, fused_s2=True,
@@ -2291,25 +2357,26 @@ class YOLOV3(object):
             # four launches already share most of dz through the L2s / Infinity Cache when they run side by side on their
             # four streams; the default stays off, the switch and its parity test stay as the record of the experiment)
             chunk_mb = float(__import__('os').environ.get('VD_S2_CHUNK_MB', '0'))
-            if len(plans) == 4 and n.kd == 1 and chunk_mb > 0:
+            if not bf16 and len(plans) == 4 and n.kd == 1 and chunk_mb > 0:
                 dz_mb = 4.0 * NF * Ho * Wo * n.co_pad / 1e6
                 nchunks = max(1, min(NF, int(math.ceil(dz_mb / chunk_mb))))
             fchunk = (NF + nchunks - 1) // nchunks
             nchunks = (NF + fchunk - 1) // fchunk
+            kp = dz.shape[-1]                                   # K dimension of the data gradient (the bf16 head: its pitch)
             wpks = []
             for plan in plans:
                 assert plan['taps'], "a parity class without taps would leave its gradient unwritten"
-                wpk = torch.empty(n.cin * len(plan['taps']) * n.co_pad, device=dev)
+                wpk = torch.empty(n.cin * len(plan['taps']) * kp, dtype=dt, device=dev)
                 dgrad_packs.append((n, plan, wpk))
                 wpks.append(wpk)
-            in_img, out_img = Ho * Wo * n.co_pad * 4, Hi * Wi * n.cin * 4          # bytes per frame of dz / of d:src
+            in_img, out_img = Ho * Wo * kp * esz, Hi * Wi * n.cin * esz        # bytes per frame of dz / of d:src
             for ch in range(nchunks):
               f0 = ch * fchunk
               fn_ = min(NF, f0 + fchunk) - f0
               # the four parity launches of a stride-2 data gradient write disjoint pixels and read the same dz: run them
               # side by side on their own streams (VD_PARITY_STREAMS=1) so that they share dz in the L2s and fill each other's tails
               par = None
-              if _parity_streams() and len(plans) == 4 and self.overlap_wgrad:
+              if not bf16 and _parity_streams() and len(plans) == 4 and self.overlap_wgrad:
                 if getattr(self, '_par_streams', None) is None:
                     self._par_streams = [torch.cuda.Stream() for _ in range(3)]
                 par = self._par_streams
@@ -2321,7 +2388,7 @@ class YOLOV3(object):
                 wpk = wpks[pi]
                 d = ConvDesc()
                 d.in_, d.wp, d.out = dz.data_ptr() + f0 * in_img, wpk.data_ptr(), dsrc.data_ptr() + f0 * out_img
-                d.N, d.Hi, d.Wi, d.Ci = fn_, Ho, Wo, n.co_pad
+                d.N, d.Hi, d.Wi, d.Ci = fn_, Ho, Wo, kp
                 d.Hg, d.Wg, d.in_stride = plan['Hg'], plan['Wg'], 1
                 ops._set_taps(d, plan['taps'])
                 d.Kfr = n.fr if n.kd > 1 else 1
@@ -2329,25 +2396,24 @@ class YOLOV3(object):
                 d.out_stride, d.out_oy, d.out_ox = n.stride, plan['py'], plan['px']
                 d.ldo = d.ldr = n.cin
                 d.flags, d.slope = (EPI_RESIDUAL if acc else 0), LEAKY_SLOPE
-                d.amax_in, d.amax_w = self._amax_or_none(bufs, 'dz:' + n.name), n.wamax.data_ptr()
+                if not bf16:
+                    d.amax_in, d.amax_w = self._amax_or_none(bufs, 'dz:' + n.name), n.wamax.data_ptr()
                 self._set_streamk(d, pi if (par is not None) else 0)
                 if acc:
                     d.residual = res_src.data_ptr() + f0 * out_img
                 seg.hold(d, wpk)
                 nplans = n.stride * n.stride
                 if fuse_m is not None:
-                    d.bs_z = bufs['z:' + fuse_m.dst].data_ptr() + f0 * out_img
-                    d.bs_scale, d.bs_shift = fuse_m.b_scale.data_ptr(), fuse_m.b_shift.data_ptr()
-                    d.bs_mean, d.bs_invstd = fuse_m.b_mean.data_ptr(), fuse_m.b_invstd.data_ptr()
-                    d.bs_part, d.bs_slope = stats_ws.data_ptr() + bs_rows * 2 * fuse_m.cout * 4, LEAKY_SLOPE
-                    autotune_desc(d)                               # fixes the tile, hence the number of M tiles
-                    bs_rows += L.load().vd_conv_igemm_mtiles(C.byref(d))
-                    mt = bs_rows
-                    assert mt * 2 * fuse_m.cout * 4 <= stats_ws.numel() * 4, "stats workspace too small"
-                seg.add('vd_conv_igemm', C.byref(d), meta=dict(
+                    fuse_bn_bwd(d, fuse_m, f0 * out_img, bs_rows * 2 * fuse_m.cout * 4)
+                if bf16 or fuse_m is not None:
+                    tune(d)
+                if fuse_m is not None:
+                    bs_rows += mtiles(C.byref(d))
+                    assert bs_rows * 2 * fuse_m.cout <= stats_ws.numel(), "stats workspace too small"
+                add_conv(d, meta=dict(
                     kind='dgrad', node=n.name, k=n.k, stride=n.stride,
                     flops=2.0 * n.cin * n.cout * len(plan['taps']) * plan['Hg'] * plan['Wg'] * fn_,
-                    bytes=self._flops(n, B, H, W, 'dgrad')['bytes'] / nplans * fn_ / NF),
+                    bytes=self._flops(n, B, H, W, 'dgrad', esz)['bytes'] / nplans * fn_ / NF),
                     stream=(par[pi - 1] if (par is not None and pi > 0) else None))
                 if par is not None and pi == len(plans) - 1:
                     for st in par:                                  # join before anything reads d:src or the partial table
@@ -2355,7 +2421,7 @@ class YOLOV3(object):
                         seg.add_py(lambda e=e_join, st=st: e.record(st))
                         seg.add_py(lambda e=e_join: torch.cuda.current_stream().wait_event(e))
                 if fuse_m is not None and pi == len(plans) - 1 and ch == nchunks - 1:
-                    seg.add('vd_bn_sum_param_grads', stats_ws.data_ptr(), mt, fuse_m.cout, fuse_m.sums2.data_ptr(),
+                    seg.add('vd_bn_sum_param_grads', stats_ws.data_ptr(), bs_rows, fuse_m.cout, fuse_m.sums2.data_ptr(),
                             fuse_m.ggamma.data_ptr(), fuse_m.gbeta.data_ptr(), ws.data_ptr(), ws_bytes)
                     fused_bwd.add(fuse_m.name)
         if side is not None and last_side[0] is not None:
@@ -2366,7 +2432,8 @@ class YOLOV3(object):
             if isinstance(sg, Program):
                 autotune_program(sg)
         _TUNE_CACHE.save()
-        return dict(fwd=fwd, bwd=bwd, bufs=bufs, slots=slots, losses=losses, dgrad_packs=dgrad_packs, ws=ws)
+        return dict(fwd=fwd, bwd=bwd, bufs=bufs, slots=slots, losses=losses, dgrad_packs=dgrad_packs, ws=ws,
+                    wb_arena=wb_arena, storage='bf16' if bf16 else 'fp32')
 
 
     # ------------------------------------------------------------------ bf16-STORAGE training (BASELINE configs[4])
@@ -2401,382 +2468,15 @@ class YOLOV3(object):
         halo_geo = d.T == 9 and d.in_stride == 1 and d.Hg == d.Hi and d.Ci % 64 == 0 and d.out_stride == 1
         _tune_bf16_record(d, of32, key, tiles, halo_geo)
 
-    def _build_train_bf16(self, B, H, W):
-        """The training plan of `_build_train` on bf16 activation / gradient tensors (set_storage('bf16')).  Same schedule:
-        forward with the BatchNorm statistics in the conv epilogues, loss, then the fixed reverse pass with the
-        weight-gradient GEMMs on a side stream and the bucketed gradient all-reduce queued behind them."""
-        dev, BFT = self.device, torch.bfloat16
-        lib = L.load()
-        world = 1
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            world = torch.distributed.get_world_size(self.process_group)
-            # (as in _build_train: the gradient buckets get their own communicator when SyncBN's statistics all-reduces sit
-            # on the critical path of backward)
-            if (world > 1 and self.syncbn_scope and self.bucketed_allreduce and self._bucket_group is None
-                    and self.process_group is None):
-                self._bucket_group = torch.distributed.new_group()
-
-        hb = lambda c: c if (c == 32 or c % 64 == 0) else round_up(c, 64)      # head pitch: the data gradient's K dimension
-        # algorithmic bytes of a launch: every operand tensor once, at 2 bytes per element
-        fl = lambda n_, kind: dict(self._flops(n_, B, H, W, kind), bytes=self._flops(n_, B, H, W, kind)['bytes'] / 2)
-        # ---- buffers
-        bufs = {'in': torch.empty(B, 3, H, W, device=dev)}
-        for name, (c, div, ld, fr) in self.tensors.items():
-            if name == 'in':
-                continue
-            if name in self.head_names:
-                bufs[name] = torch.zeros(B, H // div, W // div, hb(ld), device=dev)              # fp32 logits (pad columns stay 0)
-                bufs['d:' + name] = torch.zeros(B, H // div, W // div, hb(ld), dtype=BFT, device=dev)
-            else:
-                bufs[name] = torch.empty(B, H // div, W // div, c, dtype=BFT, device=dev)
-                bufs['d:' + name] = torch.empty(B, H // div, W // div, c, dtype=BFT, device=dev)
-        for n in self.conv_nodes:
-            if n.bn:
-                bufs['z:' + n.dst] = torch.empty_like(bufs[n.dst])
-        mx = max(bufs[n.dst].numel() for n in self.conv_nodes if not n.head)
-        mx = max([mx] + [bufs[h].numel() for h in self.head_names])
-        bufs['dz'], bufs['dz2'], bufs['tmp'] = [torch.empty(mx, dtype=BFT, device=dev) for _ in range(3)]
-        for nm, t in bufs.items():                     # tune on noise, not on zero pages (see _buffers)
-            if torch.is_tensor(t) and nm not in self.head_names and not nm.startswith('d:yolo') and t.dtype == BFT:
-                t.copy_(torch.randn(min(t.numel(), 1 << 22), device=dev).to(BFT).repeat((t.numel() >> 22) + 1)[:t.numel()].view(t.shape))
-        ws_bytes = 1 << 20
-        for n in self.conv_nodes:
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            if n.stem:
-                ws_bytes = max(ws_bytes, int(lib.vd_stem_wgrad_ws_bytes(B, Hi, Wi)))
-            else:
-                wd_ = WgradDesc()
-                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci, wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = B, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.co_pad
-                ops._set_taps(wd_, n.taps())
-                for fl_ in (0, L.WGRAD_HALO):          # the halo-ring kernel picks its own split count
-                    wd_.in_stride, wd_.Kfr, wd_.flags = n.stride, 1, L.STORE_BF16 | L.MATH_BF16 | fl_
-                    ws_bytes = max(ws_bytes, int(lib.vd_conv_wgrad_ws_bytes(C.byref(wd_))))
-            ws_bytes = max(ws_bytes, ops.bn_stats_ws_bytes(B * Ho * Wo, hb(n.co_pad)))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        smax = 16
-        for n in self.conv_nodes:
-            if n.bn:
-                smax = max(smax, ((B * (H // n.div_out) * (W // n.div_out) + 63) // 64 + 8) * 2 * n.cout)
-        stats_ws = torch.empty(smax, device=dev)
-
-        packs = []                                     # (kind, node, plan, fp32 scratch, bf16 image, rows, K, K_pad, T)
-        # forward images: the conv weights live fwd-packed [co_pad][T * Ci] in the arena and need no padding here (every Ci
-        # is 32 or a multiple of 64), so ONE conversion of the arena's weight range makes all of them
-        wb_arena = torch.empty(self.n_weight, dtype=BFT, device=dev)
-        packs.append(('arena', None, None, None, wb_arena, 1, self.n_weight, self.n_weight, 1))
-        fwd, seg = [], Program()
-        for n in self.nodes:
-            if isinstance(n, UpcatNode):
-                o = bufs[n.dst]
-                seg.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B,
-                        o.shape[1], o.shape[2], n.cu // 2, n.cr // 2)          # a copy: two bf16 = one 4-byte word
-                continue
-            if not isinstance(n, ConvNode):
-                raise NotImplementedError("bf16-storage training: node type %s" % type(n).__name__)
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            M = B * Ho * Wo
-            if n.stem:
-                z = bufs['z:' + n.dst]
-                nb = lib.vd_stem_conv_blocks(B, H, W)
-                assert nb * 2 * n.cout <= stats_ws.numel()
-                self._add_stem(seg, n, bufs, B, H, W, z, bf16=True, stats=stats_ws.data_ptr())
-                table_rows = nb
-            else:
-                wb = wb_arena[n.w_off:n.w_off + n.w_numel]
-                assert n.w_numel == n.co_pad * n.T * n.cin and n.w_off % 8 == 0
-                d = ConvDesc()
-                self._set_streamk(d, 0)
-                out = bufs[n.dst] if n.head else bufs['z:' + n.dst]
-                d.in_, d.wp, d.out = bufs[n.src].data_ptr(), wb.data_ptr(), out.data_ptr()
-                d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = B, Hi, Wi, n.cin, Ho, Wo, n.stride
-                ops._set_taps(d, n.taps())
-                d.Kfr, d.Ho, d.Wo, d.Co = 1, Ho, Wo, n.co_pad
-                d.out_stride, d.out_oy, d.out_ox, d.slope = 1, 0, 0, LEAKY_SLOPE
-                d.ldo = d.ldr = out.shape[-1]
-                seg.hold(d, wb)
-                if n.head:
-                    d.flags, d.shift = EPI_AFFINE, n.bias.data_ptr()
-                    self._tune_bf16_desc(d, 1)
-                    seg.add('vd_conv_igemm_bf16', C.byref(d), 1, meta=fl(n, 'fwd'))
-                    continue
-                d.stats_part = stats_ws.data_ptr()
-                self._tune_bf16_desc(d, 0)
-                table_rows = lib.vd_conv_igemm_bf16_mtiles(C.byref(d))
-                assert table_rows * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
-                seg.add('vd_conv_igemm_bf16', C.byref(d), 0, meta=fl(n, 'fwd'))
-                z = out
-            fin = (n.gamma.data_ptr(), n.beta.data_ptr(), BN_EPS, BN_MOMENTUM, n.rmean.data_ptr(), n.rvar.data_ptr(),
-                   n.b_scale.data_ptr(), n.b_shift.data_ptr(), n.b_mean.data_ptr(), n.b_invstd.data_ptr())
-            if self._syncbn(n):
-                # SyncBN (train_yolov3.py:347-354): the fp64 [sum x, sum x^2] of the fp32 accumulators, summed over the
-                # ranks, then one finalize on the global count - the same exchange unit as the fp32-storage plan
-                seg.add('vd_bn_sum_partials', stats_ws.data_ptr(), table_rows, n.cout, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                seg.add_coll(self._syncbn_exchange(n.sums))
-                seg.add('vd_bn_finalize', n.sums.data_ptr(), float(M * world), n.cout, *fin)
-            else:
-                seg.add('vd_bn_sum_finalize', stats_ws.data_ptr(), table_rows, n.cout, n.sums.data_ptr(), float(M), *fin,
-                        ws.data_ptr(), ws_bytes)
-            res = bufs[n.residual].data_ptr() if n.residual else None
-            seg.add('vd_bn_apply_leaky_bf16', z.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(), res,
-                    bufs[n.dst].data_ptr(), M, n.cout, LEAKY_SLOPE,
-                    meta=dict(node=n.name, bytes=2.0 * M * n.cout * (3 if n.residual else 2), single_conv_consumer=False))
-        grids = self._grid(H, W)
-        ldh = bufs[self.head_names[0]].shape[-1]
-        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, ldh, STRIDES[::-1], ANCHORS[::-1], B, self.num_class)
-        slots = dict(gt=Slot(), M=Slot(), obj=Slot(), ctr=Slot(), scl=Slot(), wgt=Slot(), cls=Slot(), smooth=Slot())
-        losses = torch.zeros(B, 4, device=dev)
-        dh = (C.c_void_p * 3)(*[bufs['d:' + h].data_ptr() for h in self.head_names])
-        lws = torch.empty(max(16, ops.yolo_loss_ws_bytes(hd)), dtype=torch.uint8, device=dev)
-        seg.hold(hd, dh, lws)
-        seg.add('vd_yolo_loss_fwd_bwd_bf16', C.byref(hd), slots['gt'], slots['M'], slots['obj'], slots['ctr'], slots['scl'],
-                slots['wgt'], slots['cls'], float(self._ignore_iou_thresh), slots['smooth'], losses.data_ptr(),
-                C.byref(dh), None, lws.data_ptr(), lws.numel())
-        fwd.append(seg)
-
-        # ---- backward (the schedule of _build_train: wgrad GEMMs on a side stream, double-buffered dz scratch, skip
-        # gradients by alias, bucketed all-reduce behind the weight gradients)
-        bwd, seg = [], Program()
-        side = torch.cuda.Stream(priority=int(__import__('os').environ.get('VD_SIDE_PRIO', '0'))) if self.overlap_wgrad else None
-        ws_w = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if side is not None else ws
-        dz_bufs, dz_free, n_dz, last_side = [bufs['dz'], bufs['dz2']], [None, None], [0], [None]
-
-        def ev_record(e, on_side):
-            return lambda: e.record(side if on_side else torch.cuda.current_stream())
-
-        def ev_wait(e, on_side):
-            return lambda: (side if on_side else torch.cuda.current_stream()).wait_event(e)
-
-        bucket_hi, bucket_acc = [self.n_weight], [0]
-        written, alias = set(self.head_names), {}
-        # BatchNorm backward reductions in the epilogue of the data gradient that completes dy of a BatchNorm output (the
-        # earliest forward consumer, processed last here), as in _build_train: the two-tensor reduction pass is skipped
-        producers = {m.dst: m for m in self.conv_nodes if m.bn}
-        consumers = {}
-        for m in self.nodes:
-            for t in ([m.src, m.residual] if isinstance(m, ConvNode) else [m.up, m.route]):
-                if t:
-                    consumers.setdefault(t, []).append(m)
-        fused_bwd = set()
-        tgrad = {t: False for t in self.tensors}
-        for m in self.nodes:
-            if isinstance(m, ConvNode):
-                tgrad[m.dst] = any(self._node_trainable(m)) or tgrad[m.src] or bool(m.residual and tgrad[m.residual])
-            else:
-                tgrad[m.dst] = tgrad[m.up] or tgrad[m.route]
-        wtrain = [m for m in self.conv_nodes if self._node_trainable(m)[0]]
-        first_wtrain = wtrain[0] if wtrain else None
-        ones = torch.ones(2048, device=dev)
-        zeros = torch.zeros(2048, device=dev)
-
-        def materialize(name):
-            if name in alias:
-                src = alias.pop(name)
-                seg.add('vd_bn_apply_leaky_bf16', src.data_ptr(), ones.data_ptr(), zeros.data_ptr(), None,
-                        bufs['d:' + name].data_ptr(), src.numel() // src.shape[-1], src.shape[-1], 1.0)
-
-        def grad_into(name, can_alias=False):
-            if name in written:
-                if not can_alias:
-                    materialize(name)
-                return bufs['d:' + name], True
-            written.add(name)
-            return bufs['d:' + name], False
-
-        for n in reversed(self.nodes):
-            if isinstance(n, UpcatNode):
-                if not tgrad[n.dst]:
-                    continue
-                dout = bufs['d:' + n.dst]
-                dup_p = drt_p = None
-                acc_r = False
-                if tgrad[n.up]:
-                    dup, acc_u = grad_into(n.up)
-                    assert not acc_u
-                    dup_p = dup.data_ptr()
-                if tgrad[n.route]:
-                    drt, acc_r = grad_into(n.route)
-                    drt_p = drt.data_ptr()
-                if acc_r:
-                    tmp = bufs['tmp'][:drt.numel()]
-                    seg.add('vd_upsample2x_concat_bwd_bf16', dout.data_ptr(), dup_p, tmp.data_ptr(), B, dout.shape[1], dout.shape[2],
-                            n.cu, n.cr)
-                    seg.add('vd_add_bf16', drt.data_ptr(), tmp.data_ptr(), drt.data_ptr(), drt.numel())
-                elif dup_p or drt_p:
-                    seg.add('vd_upsample2x_concat_bwd_bf16', dout.data_ptr(), dup_p, drt_p, B, dout.shape[1], dout.shape[2], n.cu, n.cr)
-                continue
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            M = B * Ho * Wo
-            if not tgrad[n.dst]:
-                continue
-            w_train, v_train = self._node_trainable(n)
-            dy = bufs['d:' + n.dst]
-            assert n.dst in written, n.name
-            materialize(n.dst)
-            slot = 0
-            if n.head:
-                dz, ldd = dy, dy.shape[-1]
-                if getattr(n, 'sums_b', None) is None or n.sums_b.numel() != 2 * ldd:
-                    n.sums_b = torch.zeros(2 * ldd, dtype=torch.float64, device=dev)
-                seg.add('vd_bn_stats_bf16', dz.data_ptr(), M, ldd, n.sums_b.data_ptr(), ws.data_ptr(), ws_bytes)
-                seg.add('vd_bn_param_grads', n.sums_b.data_ptr(), n.co_pad, bufs['tmp'].data_ptr(), n.gbias.data_ptr())
-                # (dgamma slot of the kernel = scratch: bufs['tmp'] is bf16 storage, n.co_pad floats fit in it)
-            else:
-                if n.residual and tgrad[n.residual]:
-                    dres, acc = grad_into(n.residual)
-                    if acc:
-                        seg.add('vd_add_bf16', dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
-                    else:
-                        alias[n.residual] = dy
-                        if not self.alias_skip_grad:
-                            materialize(n.residual)
-                z = bufs['z:' + n.dst]
-                slot = n_dz[0] % 2
-                n_dz[0] += 1
-                dz, ldd = dz_bufs[slot][:M * n.cout].view(-1, Ho, Wo, n.cout), n.cout
-                if n.name not in fused_bwd:      # (fused: sums and gamma / beta gradients came with the table reduction)
-                    seg.add('vd_bn_bwd_reduce_bf16', z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
-                            n.b_mean.data_ptr(), n.b_invstd.data_ptr(), M, n.cout, LEAKY_SLOPE, n.sums2.data_ptr(), ws.data_ptr(), ws_bytes)
-                    seg.add('vd_bn_param_grads', n.sums2.data_ptr(), n.cout, n.ggamma.data_ptr(), n.gbeta.data_ptr())
-                count = float(M)
-                if self._syncbn(n):          # [sum g, sum g xhat] over the ranks (the local gamma / beta gradients came first)
-                    seg.add_coll(self._syncbn_exchange(n.sums2))
-                    count = float(M * world)
-                if side is not None and dz_free[slot] is not None:
-                    seg.add_py(ev_wait(dz_free[slot], False))
-                seg.add('vd_bn_bwd_apply_bf16', z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
-                        n.b_mean.data_ptr(), n.b_invstd.data_ptr(), n.sums2.data_ptr(), count, M, n.cout, LEAKY_SLOPE, dz.data_ptr())
-            if w_train:
-                if n.stem:
-                    wargs = ('vd_stem_wgrad_bf16', bufs['in'].data_ptr(), dz.data_ptr(), n.co_pad, n.gwp.data_ptr(), B, Hi, Wi)
-                else:
-                    wd_ = WgradDesc()
-                    wd_.in_, wd_.dout, wd_.dwp = bufs[n.src].data_ptr(), dz.data_ptr(), n.gwp.data_ptr()
-                    wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = B, Hi, Wi, n.cin
-                    wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Ho, Wo, n.co_pad, ldd
-                    wd_.in_stride, wd_.Kfr, wd_.splits, wd_.flags = n.stride, 1, 0, L.STORE_BF16 | L.MATH_BF16
-                    ops._set_taps(wd_, n.taps())
-                    autotune_wgrad_bf16(wd_, ws.data_ptr(), ws_bytes)
-                    seg.hold(wd_)
-                    wargs = ('vd_conv_wgrad', C.byref(wd_))
-                if side is not None:
-                    e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
-                    seg.add_py(ev_record(e_ready, False))
-                    seg.add_py(ev_wait(e_ready, True))
-                    seg.add(*wargs, ws_w.data_ptr(), ws_bytes, meta=fl(n, 'wgrad'), stream=side)
-                    seg.add_py(ev_record(e_done, True))
-                    seg.hold(e_ready, e_done)
-                    if not n.head:
-                        dz_free[slot] = e_done
-                    last_side[0] = e_done
-                else:
-                    seg.add(*wargs, ws.data_ptr(), ws_bytes, meta=fl(n, 'wgrad'))
-                bucket_acc[0] += n.w_numel
-                if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or n is first_wtrain or n.stem):
-                    lo, hi = n.w_off, bucket_hi[0]
-                    seg.add_py(self._bucket_launcher(lo, hi, side))
-                    bucket_hi[0], bucket_acc[0] = lo, 0
-            if n.stem or n.src in self.input_tensors or not tgrad[n.src]:
-                continue
-            dsrc, acc = grad_into(n.src, can_alias=True)
-            res_src = alias.pop(n.src) if n.src in alias else dsrc
-            kp = dz.shape[-1]                                   # K dimension of the data gradient (head: the padded pitch)
-            pm = producers.get(n.src)
-            # (off by default in this mode, VD_FUSE_BWD_BF16=1: measured on one box, 416 / batch 64, 1992 frames/s with the
-            # stand-alone reduction passes against 1958 fused - the HBM-bound pass runs beside the side stream's MFMA-bound
-            # weight gradients, the fused epilogue lengthens the data gradients on the critical path)
-            fuse_m = pm if (__import__('os').environ.get('VD_FUSE_BWD_BF16', '0') == '1' and pm is not None and
-                            consumers[n.src][0] is n) else None
-            bs_rows = 0
-            plans = dgrad_plans(n.k, n.pad, n.stride, Hi, Wi, 1, 0)
-            for pi, plan in enumerate(plans):
-                assert plan['taps']
-                T = len(plan['taps'])
-                w32 = None
-                wbd = torch.empty(n.cin * T * kp, dtype=BFT, device=dev)
-                packs.append(('dgrad', n, plan, w32, wbd, n.cin, n.co_pad, kp, T))
-                d = ConvDesc()
-                self._set_streamk(d, 0)
-                d.in_, d.wp, d.out = dz.data_ptr(), wbd.data_ptr(), dsrc.data_ptr()
-                d.N, d.Hi, d.Wi, d.Ci = B, Ho, Wo, kp
-                d.Hg, d.Wg, d.in_stride = plan['Hg'], plan['Wg'], 1
-                ops._set_taps(d, plan['taps'])
-                d.Kfr, d.Ho, d.Wo, d.Co = 1, Hi, Wi, n.cin
-                d.out_stride, d.out_oy, d.out_ox = n.stride, plan['py'], plan['px']
-                d.ldo = d.ldr = n.cin
-                d.flags, d.slope = (EPI_RESIDUAL if acc else 0), LEAKY_SLOPE
-                if acc:
-                    d.residual = res_src.data_ptr()
-                seg.hold(d, wbd)
-                if fuse_m is not None:
-                    d.bs_z = bufs['z:' + fuse_m.dst].data_ptr()
-                    d.bs_scale, d.bs_shift = fuse_m.b_scale.data_ptr(), fuse_m.b_shift.data_ptr()
-                    d.bs_mean, d.bs_invstd = fuse_m.b_mean.data_ptr(), fuse_m.b_invstd.data_ptr()
-                    d.bs_part, d.bs_slope = stats_ws.data_ptr() + bs_rows * 2 * fuse_m.cout * 4, LEAKY_SLOPE
-                self._tune_bf16_desc(d, 0)
-                if fuse_m is not None:
-                    bs_rows += lib.vd_conv_igemm_bf16_mtiles(C.byref(d))
-                    assert bs_rows * 2 * fuse_m.cout <= stats_ws.numel(), "stats workspace too small"
-                seg.add('vd_conv_igemm_bf16', C.byref(d), 0, meta=dict(
-                    kind='dgrad', node=n.name, k=n.k, stride=n.stride,
-                    flops=2.0 * n.cin * n.cout * T * plan['Hg'] * plan['Wg'] * B,
-                    bytes=fl(n, 'dgrad')['bytes'] / (n.stride * n.stride)))
-                if fuse_m is not None and pi == len(plans) - 1:
-                    seg.add('vd_bn_sum_param_grads', stats_ws.data_ptr(), bs_rows, fuse_m.cout, fuse_m.sums2.data_ptr(),
-                            fuse_m.ggamma.data_ptr(), fuse_m.gbeta.data_ptr(), ws.data_ptr(), ws_bytes)
-                    fused_bwd.add(fuse_m.name)
-        if side is not None and last_side[0] is not None:
-            seg.add_py(ev_wait(last_side[0], False))
-        seg.hold(ws_w, side, stats_ws, ones, zeros)
-        bwd.append(seg)
-        _TUNE_CACHE.save()
-        return dict(fwd=fwd, bwd=bwd, bufs=bufs, slots=slots, losses=losses, dgrad_packs=[], packs_bf16=packs, ws=ws, storage='bf16')
-
-    def _refresh_train_bf16(self, tp, overlap=False):
-        """bf16 images of the weights (forward layout and every data-gradient tap plan) after the weights moved; on the pack
-        stream beside the forward pass when `overlap` (the forward images are needed first: they are packed first and the
-        main stream waits for them, the data-gradient images only gate backward())."""
-        if tp.get('dgrad_version') == self._weights_version:
-            return
-        lib = L.load()
-
-        def pack(kinds):
-            s_ = L.stream_ptr()
-            for kind, n, plan, w32, wb, rows, K, Kp, T in tp['packs_bf16']:
-                if kind not in kinds:
-                    continue
-                if kind == 'arena':
-                    L.check(lib.vd_pack_weight_bf16(self.weights.data_ptr(), wb.data_ptr(), rows, rows, K, Kp, T, s_), 'vd_pack_weight_bf16')
-                else:
-                    arr = (C.c_int32 * T)(*plan['tap_ids'])          # straight to bf16 [cin][T * K pitch]
-                    L.check(lib.vd_pack_weight_dgrad_bf16(n.wp.data_ptr(), wb.data_ptr(), K, Kp, n.cin, 1, n.k, n.k, arr, T, 1, s_),
-                            'vd_pack_weight_dgrad_bf16')
-        pack(('arena',))
-        ev = None
-        if overlap and self.overlap_wgrad:
-            if self._pack_stream is None:
-                self._pack_stream = torch.cuda.Stream()
-            self._pack_stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._pack_stream):
-                pack(('dgrad',))
-                ev = torch.cuda.Event()
-                ev.record(self._pack_stream)
-        else:
-            pack(('dgrad',))
-        self._pack_event = ev
-        tp['dgrad_version'] = self._weights_version
-
     @staticmethod
-    def _flops(n, B, H, W, kind):
-        """Algorithmic FLOPs of one conv launch: 2*Cin*Cout*k*k*Ho*Wo per image."""
+    def _flops(n, B, H, W, kind, esz=4):
+        """Algorithmic FLOPs of one conv launch: 2*Cin*Cout*k*k*Ho*Wo per image; `esz` = bytes per element."""
         px_in = B * n.fr * (H // n.div_in) * (W // n.div_in)
         px_out = B * n.fr * (H // n.div_out) * (W // n.div_out)
         return dict(kind=kind, node=n.name, k=n.k, stride=n.stride,
                     flops=2.0 * n.cin * n.cout * n.kd * n.k * n.k * px_out,
-                    # algorithmic bytes: every operand tensor once (input, output/gradient, weights), fp32
-                    bytes=4.0 * (px_in * n.cin + px_out * n.cout + n.cout * n.cin * n.kd * n.k * n.k))
+                    # algorithmic bytes: every operand tensor once (input, output/gradient, weights)
+                    bytes=float(esz) * (px_in * n.cin + px_out * n.cout + n.cout * n.cin * n.kd * n.k * n.k))
 
     @staticmethod
     def _corr_meta(n, B, xs, kind):
@@ -2799,11 +2499,14 @@ class YOLOV3(object):
 
     def _refresh_dgrad(self, tp, overlap=False):
         """Re-pack the data-gradient weight layout after the weights moved. With overlap=True (start of a training
-        step) the 72 small pack launches run on a side stream beside the forward pass; backward() waits on the event."""
-        if tp.get('storage') == 'bf16':
-            return self._refresh_train_bf16(tp, overlap)
+        step) the 72 small pack launches run on a side stream beside the forward pass; backward() waits on the event.
+        A bf16-storage plan first gets the bf16 image of the weight arena its forward convs read, on the main stream:
+        the forward pass needs it before anything else."""
         if tp.get('dgrad_version') == self._weights_version:
             return
+        if tp['wb_arena'] is not None:
+            L.check(L.load().vd_pack_weight_bf16(self.weights.data_ptr(), tp['wb_arena'].data_ptr(), 1, 1, self.n_weight,
+                                                 self.n_weight, 1, L.stream_ptr()), 'vd_pack_weight_bf16')
         ev = None
         if overlap and self.overlap_wgrad:
             if self._pack_stream is None:
@@ -2823,7 +2526,12 @@ class YOLOV3(object):
 
     @staticmethod
     def _pack_dgrad(n, plan, wpk):
-        if plan.get('fused_s2'):            # the one-launch form of a stride-2 data gradient (VD_CONV_PARITY4)
+        if wpk.dtype == torch.bfloat16:     # bf16 storage: straight to bf16 [cin][T * K pitch]
+            T = len(plan['taps'])
+            arr = (C.c_int32 * T)(*plan['tap_ids'])
+            L.check(L.load().vd_pack_weight_dgrad_bf16(n.wp.data_ptr(), wpk.data_ptr(), n.co_pad, wpk.numel() // (n.cin * T),
+                                                       n.cin, 1, n.k, n.k, arr, T, 1, L.stream_ptr()), 'vd_pack_weight_dgrad_bf16')
+        elif plan.get('fused_s2'):          # the one-launch form of a stride-2 data gradient (VD_CONV_PARITY4)
             ops.pack_weight_dgrad_s2(n.wp, wpk, Co=n.co_pad, Co_pad=n.co_pad, Ci=n.cin)
         else:
             ops.pack_weight_dgrad(n.wp, wpk, Co=n.co_pad, Co_pad=n.co_pad, Ci=n.cin, kd=n.kd, kh=n.k, kw=n.k,
@@ -2883,7 +2591,7 @@ class YOLOV3(object):
         if key not in self._programs:
             # every input shape owns its plan and buffers (random-shape training visits ten); when the next one does not
             # fit beside the others, drop those and build again - their kernel choices stay in the tuning cache
-            self._programs[key] = self._build_or_evict(lambda: (self._build_train_bf16 if bf16s else self._build_train)(B, H, W))
+            self._programs[key] = self._build_or_evict(lambda: self._build_train(B, H, W))
         tp = self._programs[key]
         f32 = lambda t: t.to(device=self.device, dtype=torch.float32).contiguous()
         gt, obj, ctr, scl, wgt, cls = [f32(t) for t in (gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)]

@@ -111,7 +111,7 @@ int vd_version(void);
  * header would have passed its stream handle as amax_out).  A binding checks vd_abi_version() == VD_ABI_VERSION and
  * vd_sizeof_desc(i) == sizeof(its mirror of the descriptor) at load, before the first compute call: viddet_amd/lib.py
  * does, INTEGRATION.md shows it.  i: 0 = vd_conv_desc, 1 = vd_wgrad_desc, 2 = vd_head_desc; unknown i -> -1. */
-#define VD_ABI_VERSION 7
+#define VD_ABI_VERSION 8
 int vd_abi_version(void);
 int64_t vd_sizeof_desc(int which);
 
@@ -493,6 +493,19 @@ int vd_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream
  * channel counts halved (two bf16 = one 4-byte word). */
 int vd_temporal_pool_bf16(const void* x, void* y, int B, int K, int64_t inner, int type, void* stream);
 int vd_upsample2x_concat_bwd_bf16(const void* dout, void* dup, void* droute, int N, int Ho, int Wo, int Cu, int Cr, void* stream);
+/* bf16-storage training of the k > 1 networks: the joins' training forward and backward on bf16 tensors.
+ * vd_temporal_pool_train_bf16: the values of vd_temporal_pool_bf16; type 0 also records the winning frame in argmax_u8, ONE
+ * byte per element (K < 128; NULL allowed for type 1).  Ties go to the lowest frame index (t > v, strictly: vd_temporal_pool's
+ * rule).  vd_temporal_pool_bwd_bf16: max: dx[b,k] = dy[b] where argmax == k, else 0; mean: dy / K rounded to bf16 once; every
+ * element of dx is written.  inner % 8 == 0.  The 'cat' join and the frame slice stay vd_temporal_cat / vd_frame_slice with
+ * the channel / inner count halved, in both directions (C % 8 == 0 keeps their 16-byte units). */
+int vd_temporal_pool_train_bf16(const void* x, void* y, uint8_t* argmax_u8, int B, int K, int64_t inner, int type, void* stream);
+int vd_temporal_pool_bwd_bf16(const void* dy, const uint8_t* argmax_u8, void* dx, int B, int K, int64_t inner, int type,
+                              void* stream);
+/* The gradient of the correlation join (vd_corr_bwd) on bf16 dy [B,H,W,ldy], x and dx [B*K,H,W,C]: the same definition and
+ * fixed summation order, fp32 accumulation, one rounding to bf16 at the store; no atomics, bit-reproducible; every element of
+ * dx is written.  Columns [Cc, ldy) of dy are never read.  The dy slice of a workgroup is staged in LDS (vd_corr.hip). */
+int vd_corr_bwd_bf16(const void* dy, const void* x, void* dx, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
 int vd_stem_wgrad_bf16(const float* x_nchw, const void* dz, int ldd, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes,
                        void* stream);
 int vd_yolo_loss_fwd_bwd_bf16(const vd_head_desc* h, const float* gt, int M, const float* obj_t, const float* center_t,

@@ -1,9 +1,9 @@
 """Times the correlation join's launches alone at full size (B = 16 windows, k = 3, 416 x 416, d in {0, 4}): the three
-route shapes (early) and the three tip shapes (late), forward and backward in fp32 and the bf16 forward; prints time,
+route shapes (early) and the three tip shapes (late), forward and backward in fp32 and on bf16 tensors; prints time,
 TF/s and GB/s on algorithmic bytes.  Then one early and one late d = 4 training step against the 'cat' join network of
-the same position (ms / step).
+the same position (ms / step), in fp32 or (--storage bf16) bf16 storage.
 
-  python tools/corr_bench.py [--batch 16] [--size 416] [--reps 20] [--no-steps]
+  python tools/corr_bench.py [--batch 16] [--size 416] [--reps 20] [--no-steps] [--storage bf16]
 """
 import argparse
 import json
@@ -42,6 +42,7 @@ def launches(B, K, size, reps):
             y = torch.empty(B, h, h, ldy, device='cuda')
             dx = torch.empty_like(x)
             xb, yb = x.bfloat16(), y.bfloat16()
+            dxb = torch.empty_like(xb)
             s = L.stream_ptr()
             flops = 2.0 * B * h * h * (K - 1) * D2 * C
             byt = 4.0 * B * h * h * (K * C + ldy)
@@ -50,7 +51,9 @@ def launches(B, K, size, reps):
                     ("bwd", lambda: lib.vd_corr_bwd(y.data_ptr(), x.data_ptr(), dx.data_ptr(), B, K, h, h, C, d, ldy, s),
                      2 * flops, byt + 4.0 * B * K * h * h * C),
                     ("fwd_bf16", lambda: lib.vd_corr_fwd_bf16(xb.data_ptr(), yb.data_ptr(), B, K, h, h, C, d, ldy, s), flops,
-                     byt / 2)):
+                     byt / 2),
+                    ("bwd_bf16", lambda: lib.vd_corr_bwd_bf16(yb.data_ptr(), xb.data_ptr(), dxb.data_ptr(), B, K, h, h, C, d, ldy, s),
+                     2 * flops, (byt + 4.0 * B * K * h * h * C) / 2)):
                 ms = _time(fn, reps)
                 rows.append(dict(d=d, shape=name, C=C, hw=h, kind=kind, ms=round(ms, 4), tflops=round(f / ms / 1e9, 2),
                                  gbs=round(b_ / ms / 1e6, 1)))
@@ -58,7 +61,7 @@ def launches(B, K, size, reps):
     return rows
 
 
-def steps(B, K, size, reps):
+def steps(B, K, size, reps, storage='fp32'):
     import numpy as np
     from viddet_amd.model import yolo3_darknet53
     from oracle import yolo as Y
@@ -76,6 +79,7 @@ def steps(B, K, size, reps):
         for label, kw in (("corr_d4", dict(corr_pos=pos, corr_d=4)), ("cat", dict(k_join_type="cat", k_join_pos=pos))):
             net = yolo3_darknet53(["c%d" % i for i in range(30)], k=K, **kw)
             net.initialize(init="he", seed=1)
+            net.set_storage(storage)
 
             def step():
                 net(x, gtt, *tg)
@@ -85,7 +89,7 @@ def steps(B, K, size, reps):
             for _ in range(2):
                 step()
             out["%s_%s" % (pos, label)] = round(_time(step, reps), 2)
-            print(json.dumps({"step": "%s_%s" % (pos, label), "ms": out["%s_%s" % (pos, label)]}), flush=True)
+            print(json.dumps({"step": "%s_%s" % (pos, label), "storage": storage, "ms": out["%s_%s" % (pos, label)]}), flush=True)
             del net
             torch.cuda.empty_cache()
     return out
@@ -98,10 +102,13 @@ def main():
     ap.add_argument("--k", type=int, default=3)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-steps", action="store_true")
+    ap.add_argument("--no-launches", action="store_true")
+    ap.add_argument("--storage", default="fp32", choices=["fp32", "bf16"], help="storage of the timed training steps")
     a = ap.parse_args()
-    launches(a.batch, a.k, a.size, a.reps)
+    if not a.no_launches:
+        launches(a.batch, a.k, a.size, a.reps)
     if not a.no_steps:
-        steps(a.batch, a.k, a.size, max(3, a.reps // 4))
+        steps(a.batch, a.k, a.size, max(3, a.reps // 4), a.storage)
 
 
 if __name__ == "__main__":

@@ -109,7 +109,8 @@ def parse_flags(argv=None):
     A("--synthetic_samples", type=int, default=128, help="size of the synthetic stand-in dataset")
     A("--storage", default="fp32", choices=["fp32", "bf16"],
       help="(no reference counterpart) bf16: training activations and gradients in bf16, fp32 statistics / losses / master "
-           "weights - net.set_storage('bf16'), BASELINE configs[4]; single-frame yolo3_darknet53 only")
+           "weights - net.set_storage('bf16'), BASELINE configs[4]; yolo3_darknet53 and its --window k > 1 variants (every join, neck "
+           "and --corr_pos), not --temp / --mult_out / --features_dir")
     return ap.parse_args(argv)
 
 
@@ -216,7 +217,7 @@ def get_net(classes, rank_world):
                           corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d)   # :348-360
     net.initialize(init="he", seed=FLAGS.seed)
     if FLAGS.storage == "bf16":
-        net.set_storage("bf16")                       # raises for the window / per-frame-output variants
+        net.set_storage("bf16")                       # raises for --temp / --mult_out / --features_dir
     start_epoch = FLAGS.start_epoch
     if FLAGS.resume.strip():
         start_epoch = resume(net, FLAGS.resume, FLAGS.start_epoch)

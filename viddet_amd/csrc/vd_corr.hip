@@ -17,6 +17,10 @@
 // on the vector ALU in increasing channel order, so results are reproducible bit for bit.  The operator is < 1 % of a
 // step's FLOPs; nothing here uses MFMA.  The backward is two gathers (no atomics), in a fixed summation order.
 // Every store is a plain vector store.
+//
+// bf16-storage training has its own backward (k_corr_bwd_bf16): same grid, same thread layout and the same summation order
+// as k_corr_bwd, but the (pixel, displacement) slice of `dy` a workgroup needs for the side frame at hand is gathered into
+// LDS once (64 x D^2 bf16 values, 15.5 KB at d = 5) instead of being loaded per displacement by every channel-quad lane.
 #include "vd_common.h"
 
 namespace {
@@ -201,6 +205,89 @@ __global__ __launch_bounds__(256) void k_corr_bwd(const float* __restrict__ dy, 
     }
 }
 
+// bf16 tensors, fp32 accumulation, one rounding at the store.  Grid, thread layout and summation order of k_corr_bwd.
+// Per side frame s (one for t != mid, the K - 1 side frames in increasing order for t == mid) the workgroup stages
+//   s_h : the 32-channel halo of the x operand, fp32                      (HT^2 x 36 floats: 46.6 KB at d = 5)
+//   s_g : dy of that frame's correlation map, bf16 bit patterns, [pixel of the tile][displacement j]
+//         t != mid: dy_t[p, j]            t == mid: dy_s[p - disp_j, j]   (64 x D^2 x 2 bytes: 15.5 KB at d = 5)
+// so the centre-frame pass never holds more than one side frame's gathered slice (62 KB in all at d = 5: two workgroups per
+// CU; 47 KB at d = 4: three).  Out-of-map sources are staged as zeros: their products add an exact zero.
+template <int DD>
+__global__ __launch_bounds__(256) void k_corr_bwd_bf16(const __bf16* __restrict__ dy, const __bf16* __restrict__ x,
+                                                       __bf16* __restrict__ dx, int K, int H, int W, int C, int ldy,
+                                                       int tiles_x) {
+    constexpr int D = 2 * DD + 1, D2 = D * D, HT = TS + 2 * DD;
+    __shared__ __attribute__((aligned(16))) float s_h[HT * HT * LP];
+    __shared__ __attribute__((aligned(16))) unsigned short s_g[(TP * D2 + 7) & ~7];
+    const int tid = threadIdx.x;
+    const int nchunk = C / CC;
+    const int t = blockIdx.y, b = blockIdx.z / nchunk, c0 = (blockIdx.z % nchunk) * CC, mid = K / 2;
+    const int ty0 = (blockIdx.x / tiles_x) * TS, tx0 = (blockIdx.x % tiles_x) * TS;
+    const int64_t HW = (int64_t)H * W;
+    const unsigned short* dyb = reinterpret_cast<const unsigned short*>(dy) + (int64_t)b * HW * ldy;
+    const int q = tid & 7, slot = tid >> 3;
+    const float inv = 1.0f / (float)C;
+    const int base0 = K * C;                          // first correlation channel
+    const bool centre = t == mid;                     // uniform over the workgroup
+
+    f32x4 acc[2];
+    acc[0] = acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < K; ++s) {
+        if (centre ? s == mid : s != mid) continue;   // the halo operand: x_mid for a side frame, x_s for the centre frame
+        const __bf16* src = x + ((int64_t)b * K + s) * HW * C;
+        const int map = centre ? s : t;               // whose correlation map's gradient is read
+        const int base = base0 + (map - (map > mid)) * D2;
+        __syncthreads();                              // the previous frame's reads are done
+        for (int i = tid; i < HT * HT * (CC / 4); i += 256) {
+            const int h = i / (CC / 4), qq = i % (CC / 4);
+            stage_row(s_h + h * LP, src, ty0 - DD + h / HT, tx0 - DD + h % HT, H, W, C, c0, qq);
+        }
+        for (int i = tid; i < TP * D2; i += 256) {
+            const int p = i / D2, j = i % D2;
+            int sy = ty0 + p / TS, sx = tx0 + p % TS;
+            if (centre) {                             // the side-frame pixel whose displacement j lands on pixel p
+                sy -= j / D - DD;
+                sx -= j % D - DD;
+            }
+            unsigned short v = 0;
+            if (sy >= 0 && sy < H && sx >= 0 && sx < W) v = dyb[((int64_t)sy * W + sx) * ldy + base + j];
+            s_g[i] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int p = slot + 32 * r, py = p / TS, px = p % TS;
+            if (ty0 + py >= H || tx0 + px >= W) continue;
+            f32x4 a = acc[r];
+            const unsigned short* gp = s_g + p * D2;
+            // halo pixel of displacement (jy, jx): (py + jy, px + jx) for a side frame, (py + 2d - jy, px + 2d - jx) for the centre
+            const float* hp = s_h + ((centre ? py + 2 * DD : py) * HT + (centre ? px + 2 * DD : px)) * LP + 4 * q;
+            const int step = centre ? -LP : LP;
+            for (int jy = 0; jy < D; ++jy) {
+#pragma unroll
+                for (int jx = 0; jx < D; ++jx) {
+                    const float gv = __uint_as_float((unsigned)gp[jy * D + jx] << 16);
+                    const f32x4 m = *reinterpret_cast<const f32x4*>(hp + (jy * HT + jx) * step);
+                    a[0] = fmaf(gv, m[0], a[0]);
+                    a[1] = fmaf(gv, m[1], a[1]);
+                    a[2] = fmaf(gv, m[2], a[2]);
+                    a[3] = fmaf(gv, m[3], a[3]);
+                }
+            }
+            acc[r] = a;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int p = slot + 32 * r;
+        const int gy = ty0 + p / TS, gx = tx0 + p % TS;
+        if (gy >= H || gx >= W) continue;
+        const int64_t pix = (int64_t)gy * W + gx;
+        const f32x4 dc = vd_ld4(dy + (int64_t)b * HW * ldy + pix * ldy + t * C + c0, q);
+        vd_st4(dx + ((int64_t)b * K + t) * HW * C + pix * C + c0, q, dc + acc[r] * inv);
+    }
+}
+
 template <typename T>
 int corr_fwd(const T* x, T* y, int B, int K, int H, int W, int C, int d, int ldy, void* stream, const char* name) {
     VD_REQUIRE(x && y && B > 0 && K > 1 && H > 0 && W > 0, "%s: bad args", name);
@@ -253,6 +340,31 @@ int vd_corr_bwd(const float* dy, const float* x, float* dx, int B, int K, int H,
         default: hipLaunchKernelGGL(k_corr_bwd<5>, grid, dim3(256), 0, s, dy, x, dx, K, H, W, C, ldy, tx); break;
     }
     VD_CHECK_LAUNCH("vd_corr_bwd");
+    return VD_OK;
+}
+
+int vd_corr_bwd_bf16(const void* dy, const void* x, void* dx, int B, int K, int H, int W, int C, int d, int ldy, void* stream) {
+    VD_REQUIRE(dy && x && dx && B > 0 && K > 1 && H > 0 && W > 0, "vd_corr_bwd_bf16: bad args");
+    VD_REQUIRE(C > 0 && C % 32 == 0, "vd_corr_bwd_bf16: C = %d must be a multiple of 32", C);
+    VD_REQUIRE(d >= 0 && d <= MAXD, "vd_corr_bwd_bf16: max displacement %d outside [0, %d]", d, MAXD);
+    const int Cc = K * C + (K - 1) * (2 * d + 1) * (2 * d + 1);
+    VD_REQUIRE(ldy >= Cc && ldy % 8 == 0, "vd_corr_bwd_bf16: ldy = %d (needs >= %d, a multiple of 8)", ldy, Cc);
+    VD_REQUIRE((int64_t)B * (C / CC) <= 65535, "vd_corr_bwd_bf16: B * C / 32 = %lld exceeds the grid's z extent",
+               (long long)B * (C / CC));
+    const int tx = (int)vd_cdiv(W, TS), ty = (int)vd_cdiv(H, TS);
+    const dim3 grid(tx * ty, K, B * (C / CC));
+    hipStream_t s = (hipStream_t)stream;
+    const __bf16 *g = (const __bf16*)dy, *xs = (const __bf16*)x;
+    __bf16* o = (__bf16*)dx;
+    switch (d) {
+        case 0: hipLaunchKernelGGL(k_corr_bwd_bf16<0>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+        case 1: hipLaunchKernelGGL(k_corr_bwd_bf16<1>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+        case 2: hipLaunchKernelGGL(k_corr_bwd_bf16<2>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+        case 3: hipLaunchKernelGGL(k_corr_bwd_bf16<3>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+        case 4: hipLaunchKernelGGL(k_corr_bwd_bf16<4>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+        default: hipLaunchKernelGGL(k_corr_bwd_bf16<5>, grid, dim3(256), 0, s, g, xs, o, K, H, W, C, ldy, tx); break;
+    }
+    VD_CHECK_LAUNCH("vd_corr_bwd_bf16");
     return VD_OK;
 }
 

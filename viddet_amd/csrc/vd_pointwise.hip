@@ -222,6 +222,63 @@ __global__ void k_tpool_bf16(const __bf16* __restrict__ x, __bf16* __restrict__ 
     }
 }
 
+// the training forward on bf16 tensors: the same values, and for the max the winning frame as one byte per element (K < 128).
+// Ties go to the lowest frame index (t > v, strictly: the rule of k_tpool) - bf16 values tie often.
+__global__ void k_tpool_train_bf16(const __bf16* __restrict__ x, __bf16* __restrict__ y, uint8_t* __restrict__ arg, int B, int K,
+                                   int64_t inner8, int type) {
+    const int64_t total = (int64_t)B * inner8;
+    GRID_STRIDE(i, total) {
+        const int64_t b = i / inner8, r = i % inner8;
+        f32x8 v = vd_ld8(x, b * K * inner8 + r);
+        uint32_t lo = 0, hi = 0;                       // the eight frame indices, one byte each
+        for (int k = 1; k < K; ++k) {
+            const f32x8 t = vd_ld8(x, (b * K + k) * inner8 + r);
+            if (type == 0) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    if (t[e] > v[e]) {
+                        v[e] = t[e];
+                        if (e < 4) lo = (lo & ~(0xffu << (8 * e))) | ((uint32_t)k << (8 * e));
+                        else hi = (hi & ~(0xffu << (8 * (e - 4)))) | ((uint32_t)k << (8 * (e - 4)));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] += t[e];
+            }
+        }
+        if (type != 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] /= (float)K;
+        }
+        vd_st8(y, i, v);
+        if (arg) reinterpret_cast<uint2*>(arg)[i] = make_uint2(lo, hi);
+    }
+}
+
+// max: dx[b, k] = dy[b] where the recorded frame is k, else 0; mean: dy / K rounded once.  Every element of dx is written.
+__global__ void k_tpool_bwd_bf16(const __bf16* __restrict__ dy, const uint8_t* __restrict__ arg, __bf16* __restrict__ dx, int B,
+                                 int K, int64_t inner8, int type) {
+    const int64_t total = (int64_t)B * K * inner8;
+    GRID_STRIDE(i, total) {
+        const int64_t r = i % inner8;
+        const int64_t t = i / inner8;
+        const uint32_t k = (uint32_t)(t % K);
+        const int64_t b = t / K;
+        f32x8 g = vd_ld8(dy, b * inner8 + r);
+        if (type == 0) {
+            const uint2 a = reinterpret_cast<const uint2*>(arg)[b * inner8 + r];
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                if ((((e < 4 ? a.x : a.y) >> (8 * (e & 3))) & 0xffu) != k) g[e] = 0.f;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) g[e] /= (float)K;
+        }
+        vd_st8(dx, i, g);
+    }
+}
+
 __global__ void k_tpool_bwd(const float* __restrict__ dy, const int32_t* __restrict__ arg, float* __restrict__ dx,
                             int B, int K, int64_t inner, int type) {
     const int64_t total = (int64_t)B * K * inner;
@@ -452,6 +509,24 @@ int vd_temporal_pool_bwd(const float* dy, const int32_t* argmax, float* dx, int 
     hipLaunchKernelGGL(k_tpool_bwd, dim3(sblocks((int64_t)B * K * inner)), dim3(256), 0, (hipStream_t)stream, dy, argmax,
                        dx, B, K, inner, type);
     VD_CHECK_LAUNCH("vd_temporal_pool_bwd");
+    return VD_OK;
+}
+
+int vd_temporal_pool_train_bf16(const void* x, void* y, uint8_t* argmax, int B, int K, int64_t inner, int type, void* stream) {
+    VD_REQUIRE(x && y && B > 0 && K > 0 && K < 128 && inner > 0 && inner % 8 == 0 && (type == 1 || (type == 0 && argmax)),
+               "vd_temporal_pool_train_bf16: bad args (K=%d inner=%lld type=%d)", K, (long long)inner, type);
+    hipLaunchKernelGGL(k_tpool_train_bf16, dim3(sblocks((int64_t)B * (inner / 8))), dim3(256), 0, (hipStream_t)stream,
+                       (const __bf16*)x, (__bf16*)y, argmax, B, K, inner / 8, type);
+    VD_CHECK_LAUNCH("vd_temporal_pool_train_bf16");
+    return VD_OK;
+}
+
+int vd_temporal_pool_bwd_bf16(const void* dy, const uint8_t* argmax, void* dx, int B, int K, int64_t inner, int type, void* stream) {
+    VD_REQUIRE(dy && dx && B > 0 && K > 0 && K < 128 && inner > 0 && inner % 8 == 0 && (type == 1 || (type == 0 && argmax)),
+               "vd_temporal_pool_bwd_bf16: bad args (K=%d inner=%lld type=%d)", K, (long long)inner, type);
+    hipLaunchKernelGGL(k_tpool_bwd_bf16, dim3(sblocks((int64_t)B * K * (inner / 8))), dim3(256), 0, (hipStream_t)stream,
+                       (const __bf16*)dy, argmax, (__bf16*)dx, B, K, inner / 8, type);
+    VD_CHECK_LAUNCH("vd_temporal_pool_bwd_bf16");
     return VD_OK;
 }
 

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VD_LIB: developer override for A/B-testing a differently built kernel library (tools/ only)
 LIB_PATH = os.environ.get("VD_LIB") or os.path.join(_HERE, "csrc", "libviddet_hip.so")
 
-ABI_VERSION = 7          # include/viddet_hip.h VD_ABI_VERSION
+ABI_VERSION = 8          # include/viddet_hip.h VD_ABI_VERSION
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -132,6 +132,7 @@ SIGNATURES = {
     "vd_corr_fwd": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "vd_corr_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "vd_corr_fwd_bf16": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "vd_corr_bwd_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "vd_frame_slice": (_i, [_p, _p, _i, _i, _i, _i, _i64, _i, _p]),
     "vd_yolo_decode_filter": (_i, [C.POINTER(HeadDesc), _f, _p, _p, C.c_int32, _p, _p]),
     "vd_nms_ws_bytes": (_i64, [_i, _i, _i]),
@@ -147,6 +148,8 @@ SIGNATURES = {
     "vd_bn_bwd_apply_bf16": (_i, [_p, _p, _p, _p, _p, _p, _p, _d, _i64, _i, _f, _p, _p]),
     "vd_add_bf16": (_i, [_p, _p, _p, _i64, _p]),
     "vd_temporal_pool_bf16": (_i, [_p, _p, _i, _i, _i64, _i, _p]),
+    "vd_temporal_pool_train_bf16": (_i, [_p, _p, _p, _i, _i, _i64, _i, _p]),
+    "vd_temporal_pool_bwd_bf16": (_i, [_p, _p, _p, _i, _i, _i64, _i, _p]),
     "vd_pack_weight_dgrad_bf16": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _p]),
     "vd_upsample2x_concat_bwd_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vd_stem_wgrad_bf16": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i64, _p]),

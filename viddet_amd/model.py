@@ -1297,7 +1297,8 @@ class YOLOV3(object):
         if train:
             for n in self.nodes:
                 if isinstance(n, PoolNode) and n.type == 0:
-                    bufs['am:' + n.dst] = torch.empty(bufs[n.dst].shape, dtype=torch.int32, device=dev)
+                    # the winning frame of a max join: int32 beside fp32 tensors, one byte beside bf16 ones (K < 128)
+                    bufs['am:' + n.dst] = torch.empty(bufs[n.dst].shape, dtype=torch.uint8 if bf16 else torch.int32, device=dev)
             for n in self.conv_nodes:
                 if n.bn:
                     bufs['z:' + n.dst] = torch.empty_like(bufs[n.dst])
@@ -1854,10 +1855,10 @@ class YOLOV3(object):
                 ws_bytes = max(ws_bytes, int(lib.vd_stem_wgrad_ws_bytes(B * n.fr, Hi, Wi)))
             elif bf16:
                 wd_ = WgradDesc()
-                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci, wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = B, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.co_pad
+                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci, wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.co_pad
                 ops._set_taps(wd_, n.taps())
                 for fl_ in (0, L.WGRAD_HALO):          # the halo-ring kernel picks its own split count
-                    wd_.in_stride, wd_.Kfr, wd_.flags = n.stride, 1, L.STORE_BF16 | L.MATH_BF16 | fl_
+                    wd_.in_stride, wd_.Kfr, wd_.flags = n.stride, (n.fr if n.kd > 1 else 1), L.STORE_BF16 | L.MATH_BF16 | fl_
                     ws_bytes = max(ws_bytes, int(lib.vd_conv_wgrad_ws_bytes(C.byref(wd_))))
             else:
                 ws_bytes = max(ws_bytes, ops.wgrad_ws_bytes(B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.k, n.stride,
@@ -1912,9 +1913,9 @@ class YOLOV3(object):
             d = ConvDesc()
             self._set_streamk(d, 0)
             d.in_, d.wp, d.out = bufs[n.src].data_ptr(), wb.data_ptr(), out.data_ptr()
-            d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = B, H // n.div_in, W // n.div_in, n.cin, Ho, Wo, n.stride
+            d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = B * n.fr, H // n.div_in, W // n.div_in, n.cin, Ho, Wo, n.stride
             ops._set_taps(d, n.taps())
-            d.Kfr, d.Ho, d.Wo, d.Co = 1, Ho, Wo, n.co_pad
+            d.Kfr, d.Ho, d.Wo, d.Co = (n.fr if n.kd > 1 else 1), Ho, Wo, n.co_pad
             d.out_stride, d.out_oy, d.out_ox, d.slope = 1, 0, 0, LEAKY_SLOPE
             d.ldo = d.ldr = out.shape[-1]                  # (the head: its bf16 pitch)
             if n.head:
@@ -1926,30 +1927,36 @@ class YOLOV3(object):
         fwd, seg = [], Program()
         if not bf16:
             self._add_input_stage(seg, bufs, B, H, W)
+        cw_ = 2 if bf16 else 1                             # bf16: the copy kernels move 4-byte words, two channels each
         for n in self.nodes:
             if isinstance(n, UpcatNode):
                 o = bufs[n.dst]
-                cw = 2 if bf16 else 1                      # bf16: a copy of 4-byte words, two channels each
+                cw = cw_
                 seg.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
                         o.shape[1], o.shape[2], n.cu // cw, n.cr // cw)
                 if not bf16:
                     seg.add('vd_amax_merge', amx(n.up), amx(n.route), amx(n.dst))
                 continue
-            if bf16 and not isinstance(n, ConvNode):
+            if bf16 and isinstance(n, (SelNode, AddNode)):     # (they occur in the temporal_out / temporal_side nets only)
                 raise NotImplementedError("bf16-storage training: node type %s" % type(n).__name__)
             if isinstance(n, PoolNode):
                 o, xs = bufs[n.dst], bufs[n.src]
                 if n.type == 2:
-                    seg.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3], 0)
+                    # a copy of 16-byte units: bf16 channels go as 4-byte words, two channels each
+                    assert xs.shape[3] % (4 * cw_) == 0, "cat join: C = %d must keep 16-byte units" % xs.shape[3]
+                    seg.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3] // cw_, 0)
                 else:
                     am = bufs['am:' + n.dst].data_ptr() if n.type == 0 else None
-                    seg.add('vd_temporal_pool', xs.data_ptr(), o.data_ptr(), am, B, n.K, o[0].numel(), n.type)
-                seg.add('vd_amax_merge', amx(n.src), None, amx(n.dst))
+                    seg.add('vd_temporal_pool_train_bf16' if bf16 else 'vd_temporal_pool', xs.data_ptr(), o.data_ptr(), am, B, n.K,
+                            o[0].numel(), n.type)
+                if not bf16:
+                    seg.add('vd_amax_merge', amx(n.src), None, amx(n.dst))
                 continue
             if isinstance(n, CorrNode):
                 xs = bufs[n.src]
-                seg.add('vd_corr_fwd', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
-                        meta=self._corr_meta(n, B, xs, 'fwd'))
+                assert xs.shape[3] == n.C and bufs[n.dst].shape[3] == n.ldy
+                seg.add('vd_corr_fwd' + sfx, xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
+                        meta=self._corr_meta(n, B, xs, 'fwd', esz))
                 continue
             if isinstance(n, (SelNode, AddNode)):
                 self._add_sel_add_fwd(seg, n, bufs, B)
@@ -2171,9 +2178,9 @@ class YOLOV3(object):
                 am = bufs['am:' + n.dst].data_ptr() if n.type == 0 else None
                 if n.type == 2:
                     launch = lambda p: seg.add('vd_temporal_cat', dout.data_ptr(), p, B, n.K, dsrc.shape[1] * dsrc.shape[2],
-                                               dsrc.shape[3], 1)
+                                               dsrc.shape[3] // cw_, 1)
                 else:
-                    launch = lambda p: seg.add('vd_temporal_pool_bwd', dout.data_ptr(), am, p, B, n.K, dout[0].numel(), n.type)
+                    launch = lambda p: seg.add('vd_temporal_pool_bwd' + sfx, dout.data_ptr(), am, p, B, n.K, dout[0].numel(), n.type)
                 add_grad(dsrc, acc, launch)
                 continue
             if isinstance(n, CorrNode):
@@ -2183,8 +2190,10 @@ class YOLOV3(object):
                 materialize(n.dst)
                 dout, xs = bufs['d:' + n.dst], bufs[n.src]
                 dsrc, acc = grad_into(n.src)
-                add_grad(dsrc, acc, lambda p: seg.add('vd_corr_bwd', dout.data_ptr(), xs.data_ptr(), p, B, n.K, xs.shape[1],
-                                                      xs.shape[2], n.C, n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd')))
+                # columns [Cc, ldy) of d:dst are never read (vd_corr.hip), and what writes them is an exact zero: the consumers'
+                # pad weight rows are exact zeros in fp32, so in their bf16 images, so in the data gradient made from those
+                add_grad(dsrc, acc, lambda p: seg.add('vd_corr_bwd' + sfx, dout.data_ptr(), xs.data_ptr(), p, B, n.K, xs.shape[1],
+                                                      xs.shape[2], n.C, n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd', esz)))
                 continue
             Hi, Wi = H // n.div_in, W // n.div_in
             Ho, Wo = H // n.div_out, W // n.div_out
@@ -2446,8 +2455,10 @@ class YOLOV3(object):
         bf16 tolerance (tests/test_bf16_train_gpu.py, test_model_gpu.py)."""
         if storage not in ('fp32', 'bf16'):
             raise ValueError("storage must be 'fp32' or 'bf16'")
-        if storage == 'bf16' and (self._k > 1 or self.noback or self.temporal_out or getattr(self, 'temporal_side', False)):
-            raise NotImplementedError("bf16-storage training is built for the single-frame yolo3_darknet53 network")
+        if storage == 'bf16' and (self.noback or self.temporal_out or getattr(self, 'temporal_side', False)):
+            raise NotImplementedError("bf16-storage training is built for yolo3_darknet53 and the k > 1 windows of YOLOV3T (every "
+                                      "join, neck and correlation variant), not for the noback, temporal_out and temporal_side "
+                                      "networks")
         self.storage = storage
 
     def _tune_bf16_desc(self, d, of32):
@@ -2457,7 +2468,7 @@ class YOLOV3(object):
             return
         base = d.flags & ~(L.MATH_NOHALO | L.CONV_STREAMK)
         key = ('bf16', d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride, d.T, d.Co, base, of32, d.out_stride, bool(d.stats_part),
-               bool(d.bs_part))
+               bool(d.bs_part)) + ((d.Kfr,) if d.Kfr > 1 else ())      # (frame taps: the 3-D / 2+1-D neck convs of a window)
         # 14 / 15: the small four-wave tiles (64x64 / 128x32, four or five workgroups per CU) for the HBM-bound 1x1 layers
         one = d.T == 1
         # (16: the first-stage patch kernel, forward with fused statistics; falls back to the default tile where it does not apply)
@@ -2479,13 +2490,13 @@ class YOLOV3(object):
                     bytes=float(esz) * (px_in * n.cin + px_out * n.cout + n.cout * n.cin * n.kd * n.k * n.k))
 
     @staticmethod
-    def _corr_meta(n, B, xs, kind):
+    def _corr_meta(n, B, xs, kind, esz=4):
         """roofline record of a correlation launch: 2 flops per (pixel, displacement, channel) and side frame (x2 backward:
         both operands' gradients); bytes = the operands read once and the result written once"""
         px = B * xs.shape[1] * xs.shape[2]
         D2 = (2 * n.d + 1) ** 2
         flops = 2.0 * px * (n.K - 1) * D2 * n.C * (2 if kind == 'bwd' else 1)
-        byt = 4.0 * px * (n.K * n.C + n.ldy) * (2 if kind == 'bwd' else 1)
+        byt = float(esz) * px * (n.K * n.C + n.ldy) * (2 if kind == 'bwd' else 1)
         return dict(kind='corr_' + kind, flops=flops, bytes=byt)
 
     def _ones(self, c):
@@ -2530,7 +2541,7 @@ class YOLOV3(object):
             T = len(plan['taps'])
             arr = (C.c_int32 * T)(*plan['tap_ids'])
             L.check(L.load().vd_pack_weight_dgrad_bf16(n.wp.data_ptr(), wpk.data_ptr(), n.co_pad, wpk.numel() // (n.cin * T),
-                                                       n.cin, 1, n.k, n.k, arr, T, 1, L.stream_ptr()), 'vd_pack_weight_dgrad_bf16')
+                                                       n.cin, n.kd, n.k, n.k, arr, T, 1, L.stream_ptr()), 'vd_pack_weight_dgrad_bf16')
         elif plan.get('fused_s2'):          # the one-launch form of a stride-2 data gradient (VD_CONV_PARITY4)
             ops.pack_weight_dgrad_s2(n.wp, wpk, Co=n.co_pad, Co_pad=n.co_pad, Ci=n.cin)
         else:

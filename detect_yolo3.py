@@ -153,7 +153,7 @@ def main(argv=None):
         FLAGS.k_join_type = FLAGS.k_join_pos = None
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
-    for flag in ("temp", "mult_out", "new_model", "motion_stream", "rnn_pos", "visualise", "model_agnostic",
+    for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "model_agnostic",
                  "metric_agnostic", "offset", "per_frame_metric", "worst_video_path", "trained_on"):
         v = getattr(FLAGS, flag)
         if v and not (isinstance(v, str) and not v.strip()):
@@ -174,7 +174,7 @@ def main(argv=None):
     # detect_yolo3.py:871-892
     net = yolo3_darknet53(dataset.classes, pretrained_base=False, k=FLAGS.window[0], k_join_type=FLAGS.k_join_type,
                           k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type,
-                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d)
+                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d, rnn_pos=FLAGS.rnn_pos or None)
     if FLAGS.random_init:
         net.initialize(init="he", obj_bias=-2.0)
     else:

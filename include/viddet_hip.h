@@ -412,6 +412,28 @@ int vd_corr_fwd(const float* x, float* y, int B, int K, int H, int W, int C, int
 int vd_corr_bwd(const float* dy, const float* x, float* dx, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
 int vd_corr_fwd_bf16(const void* x, void* y, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
 
+/* Bidirectional convolutional GRU over the K frames of a window (RNN(k, type='gru', bi=True), layers.py:267-306; the cell
+ * restated from MXNet's Conv2DGRUCell): the gate arithmetic between the cell's convolutions, which are
+ * vd_conv_igemm launches (i2h over all B*K folded frames, h2h on the B frames of one step, biases in the epilogue).
+ * The 3*Ch channels of I and H are three blocks of Ch in the order r, z, o; fp32, Ch % 4 == 0, 16-byte aligned pointers.
+ *   I      [B*K, HW, 3*Ch]  i2h output of the folded frames (frame b*K + t); the step reads frame t of every window
+ *   H      [B*HW, 3*Ch]     h2h output of this step, or NULL: the state is zero and H is `hbias` [3*Ch] alone
+ *   hprev  [B*HW, Ch]       the previous state, or NULL (zero)
+ *   h      [B*HW, Ch]       r = sigmoid(I_r + H_r), z = sigmoid(I_z + H_z), n = tanh(I_o + r * H_o), h = (1 - z) n + z hprev
+ * Nothing else is kept for backward: vd_gru_gate_bwd recomputes r, z, n from I and H (h_valid = 0: from hbias) and
+ * overwrites them IN PLACE with  dI = [dr', dz', da]  and  dH = [dr', dz', da * r]  (H is written at a first step too: its
+ * column sums are the h2h bias gradient), where  dh = dy_scale * dy[frame t] + (carry ? dh : 0),  dn = dh (1 - z),
+ * dz = dh (hprev - n), da = dn (1 - n^2), dr = da H_o, dr' = dr r (1 - r), dz' = dz z (1 - z); with a previous state it
+ * also writes  dh <- dh * z, to which the h2h data gradient is then added (VD_EPI_RESIDUAL).  dy [B*K, HW, Ch] is the folded
+ * gradient of the layer output y; dy_scale = 1/2 is the backward of the bidirectional average.
+ * vd_gru_avg: y[b*K + t] = (hl[t][b] + hr[K-1-t][b]) / 2 from the two directions' STEP-major states [K][B][inner] (step s
+ * of the reverse direction is frame K-1-s) into the folded output; amax_out (optional) as in vd_bn_apply_leaky. */
+int vd_gru_gate_fwd(const float* I, const float* H, const float* hbias, const float* hprev, float* h, int B, int K, int t,
+                    int64_t HW, int Ch, void* stream);
+int vd_gru_gate_bwd(float* I, float* H, int h_valid, const float* hbias, const float* hprev, const float* dy, float dy_scale,
+                    float* dh, int carry, int B, int K, int t, int64_t HW, int Ch, void* stream);
+int vd_gru_avg(const float* hl, const float* hr, float* y, int B, int K, int64_t inner, float* amax_out, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * YOLO head: decode / filter / NMS / targets / loss
  * Head tensors are the raw prediction-conv outputs, NHWC [B, g, g, ldh], channel = a*(5+C)+j,

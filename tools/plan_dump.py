@@ -36,6 +36,7 @@ def main():
     ap.add_argument("--block", default="2", help="block_conv_type")
     ap.add_argument("--corr-pos", default=None)
     ap.add_argument("--corr-d", type=int, default=None)
+    ap.add_argument("--rnn-pos", default=None, choices=["late", "out"], help="bidirectional ConvGRU over the window")
     ap.add_argument("--t-out", action="store_true", help="per-frame outputs (k = 5)")
     ap.add_argument("--noback", action="store_true")
     ap.add_argument("--freeze-base", action="store_true")
@@ -59,7 +60,8 @@ def main():
         net = M.yolo3_no_backbone(classes, **norm)
     else:
         net = M.yolo3_darknet53(classes, freeze_base=a.freeze_base, k=a.k, k_join_type=a.join, k_join_pos=a.pos,
-                                block_conv_type=a.block, t_out=a.t_out, corr_pos=a.corr_pos, corr_d=a.corr_d, **norm)
+                                block_conv_type=a.block, t_out=a.t_out, corr_pos=a.corr_pos, corr_d=a.corr_d,
+                                **(dict(rnn_pos=a.rnn_pos) if a.rnn_pos else {}), **norm)   # (only when asked: older revisions have no such argument)
     if a.range_exact:
         bn = [n for n in net.conv_nodes if n.bn]
         net._range_exact.update([bn[3].dst, "dz:" + bn[6].name])

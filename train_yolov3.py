@@ -12,9 +12,10 @@ one RCCL all-reduce and `--syncbn` becomes a SyncBN collective.
 absl is not installed here: argparse re-creates the same flag surface (list flags take comma lists).
 `--features_dir` trains the neck/heads on cached backbone features (yolo3_no_backbone; features written by
 extract_base_features.py); `--window 5 --temp --mult_out` builds YOLOV3Temporal with per-frame outputs.  Variants
-outside the built scope (--temp without --mult_out, --motion_stream, --new_model, --hier, --rnn_pos) are accepted and
+outside the built scope (--temp without --mult_out, --motion_stream, --new_model, --hier) are accepted and
 rejected with NotImplementedError like the reference's own guards.  `--window k --corr_pos early|late --corr_d d` builds
-the correlation join (Corr, layers.py:93-132).
+the correlation join (Corr, layers.py:93-132); `--window k --rnn_pos late|out` the bidirectional ConvGRU over the window
+(RNN, layers.py:267-306).
 """
 import argparse
 import logging
@@ -197,7 +198,7 @@ def get_net(classes, rank_world):
     """train_yolov3.py:332-431 ('ours' definition, darknet53 only)."""
     if FLAGS.network != "darknet53":
         raise NotImplementedError("Backbone CNN model {} not implemented.".format(FLAGS.network))
-    for flag in ("new_model", "motion_stream", "rnn_pos"):
+    for flag in ("new_model", "motion_stream"):
         if getattr(FLAGS, flag):
             raise NotImplementedError("--%s selects a research variant outside the yolo3_darknet53 hot path" % flag)
     k = int(FLAGS.window[0])
@@ -214,7 +215,8 @@ def get_net(classes, rank_world):
                           norm_kwargs={"scope": FLAGS.syncbn_scope}, freeze_base=FLAGS.freeze_base,
                           k=k, k_join_type=FLAGS.k_join_type, k_join_pos=FLAGS.k_join_pos,
                           block_conv_type=FLAGS.block_conv_type, temporal=FLAGS.temp, t_out=FLAGS.mult_out,
-                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d)   # :348-360
+                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d,
+                          rnn_pos=FLAGS.rnn_pos or None)                          # :348-360
     net.initialize(init="he", seed=FLAGS.seed)
     if FLAGS.storage == "bf16":
         net.set_storage("bf16")                       # raises for --temp / --mult_out / --features_dir

@@ -640,7 +640,20 @@ class Parameter:
         if self.kind == 'stem_weight':
             co = self.shape[0]
             return self.storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+        if self.kind in ('gru_weight', 'gru_bias'):
+            return self._gru_read(self.storage)
         return self.storage[:int(np.prod(self.shape))].view(self.shape).clone()
+
+    # a GRU cell's 3*Ch output channels are three gate blocks (r, z, o); on the device each block is padded to the width
+    # the state tensor has (GruNode.chp), and the h2h weight's input channels to the same width - zero rows / columns
+    def _gru_read(self, st):
+        n = self.node
+        ch, chp = n.gate_ch, n.cout // 3
+        if self.kind == 'gru_bias':
+            return st[:3 * chp].view(3, chp)[:, :ch].reshape(-1).clone()
+        full = torch.empty((3 * chp, n.cin) + self.shape[2:], device=st.device)
+        ops.unpack_weight(st, full)
+        return torch.cat([full[g * chp:g * chp + ch, :n.ref_cin] for g in range(3)], dim=0).contiguous()
 
     def grad(self):
         if self.kind == 'conv_weight':
@@ -651,6 +664,8 @@ class Parameter:
         if self.kind == 'stem_weight':
             co = self.shape[0]
             return self.grad_storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+        if self.kind in ('gru_weight', 'gru_bias'):
+            return self._gru_read(self.grad_storage)
         return self.grad_storage[:int(np.prod(self.shape))].view(self.shape).clone()
 
     def set_data(self, value):
@@ -670,6 +685,17 @@ class Parameter:
             tmp = torch.zeros(co, 32, device=v.device)
             tmp[:, :27] = v.permute(0, 2, 3, 1).reshape(co, 27)
             self.storage.copy_(tmp.view(-1))
+        elif self.kind in ('gru_weight', 'gru_bias'):
+            n = self.node
+            ch, chp = n.gate_ch, n.cout // 3
+            self.storage.zero_()
+            if self.kind == 'gru_bias':
+                self.storage[:3 * chp].view(3, chp)[:, :ch].copy_(v.view(3, ch))
+            else:
+                vp = torch.zeros((3 * chp, n.cin) + self.shape[2:], device=v.device)
+                for g in range(3):
+                    vp[g * chp:g * chp + ch, :n.ref_cin] = v[g * ch:(g + 1) * ch]
+                ops.pack_weight_fwd(vp, self.storage, 3 * chp)
         else:
             self.storage.zero_()
             self.storage[:v.numel()].copy_(v.view(-1))
@@ -741,6 +767,32 @@ class CorrNode:
         self.ldy = round_up(self.Cc, 64)
 
 
+class GruNode:
+    """RNN(k, type='gru', channels=ch, kernel=(s, s), bi=True) over the K frames of a window (layers.py:267-306; the cell is
+    restated from MXNet's Conv2DGRUCell / BidirectionalCell): (B*K, h, w, cin) -> (B*K, h, w, chp), frame t
+    of the output = (hl_t + hr_t) / 2 of two independent cells run forwards and backwards in time.  Each cell owns two
+    bias-only convolutions (i2h on the K frames at once, h2h on one step's state), kept as ConvNodes outside the node list
+    so that the arena, the max-abs slots, the optimiser ranges and the gradient buckets treat them like any conv; their
+    3*ch output channels are three gate blocks (r, z, o), each padded to chp on the device (zero rows, zero bias)."""
+
+    def __init__(self, name, pname, src, dst, K, cin, ch, ksz, div, chp):
+        self.name, self.pname, self.src, self.dst, self.K = name, pname, src, dst, K
+        self.cin, self.ch, self.chp, self.k, self.div = cin, ch, chp, ksz, div
+        self.cells = []
+        for cname in ('l_cell', 'r_cell'):
+            i2h = ConvNode("%s.%s.i2h" % (pname, cname), src, "gru:%s.%s.I" % (name, cname), cin, 3 * chp, ksz, 1, div, bn=False, fr=K)
+            # (fr = K: the weight-gradient launch over the frames that had a state bounds the workspace sizes)
+            h2h = ConvNode("%s.%s.h2h" % (pname, cname), None, "gru:%s.%s.H" % (name, cname), chp, 3 * chp, ksz, 1, div, bn=False, fr=K)
+            h2h.ref_cin = ch
+            for cn, kind in ((i2h, 'i2h'), (h2h, 'h2h')):
+                cn.gru, cn.gate_ch = self, ch
+                cn.pw, cn.pb = "%s.%s.%s_weight" % (pname, cname, kind), "%s.%s.%s_bias" % (pname, cname, kind)
+            self.cells.append((cname, i2h, h2h))
+
+    def key(self, cname, what):
+        return "gru:%s.%s.%s" % (self.name, cname, what)
+
+
 class SelNode:
     """x.slice_axis(axis=1, begin=k0, end=k0+kc) on folded frames (yolo3_temporal.py:437-446): frames [k0, k0+kc) of every
     K-frame window of `src` -> `dst` (kc frames per window)."""
@@ -768,7 +820,7 @@ ROUTE_TENSORS = (('f14', 256, 8), ('f23', 512, 16), ('f28', 1024, 32))   # featu
 
 
 def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_type='2', noback=False,
-                temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0):
+                temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0, rnn_pos=None):
     """Node list of YOLOV3T over Darknet-53 (wrappers.py:54-58,101-103; three_darknet.py:252-258;
     yolo3.py:1003-1054 wiring, :1095-1177 forward).  k>1: the backbone is TimeDistributed (K frames folded
     into the batch, layers.py:241-250); 'early' joins pool each stage output over K, 'late' joins keep K frames
@@ -789,7 +841,12 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
     corr = K > 1 and k_join_pos is None and corr_pos is not None and not temporal_out and not temporal_side
     if corr:
         k_join_pos = corr_pos
-    late = K > 1 and (k_join_pos == 'late' or temporal_out)
+    # rnn_pos (yolo3.py:1022-1030,1040-1042,1128-1138): 'late' - the block has no tip cell, a 3x3 bidirectional ConvGRU over
+    # the K frames takes its place and the late join follows; 'out' - the neck runs per frame whatever k_join_pos says (the
+    # early / late joins are guarded by `_rnn_pos != 'out'`), a 1x1 ConvGRU replaces the prediction conv and TemporalPooling
+    # joins the K predictions
+    rnn = rnn_pos if K > 1 and not temporal_out and not temporal_side else None
+    late = K > 1 and (k_join_pos == 'late' or temporal_out or rnn == 'out')
     td_names = K > 1 and not temporal_out and not temporal_side
     pad_of = {}                            # zero channels at the end of a tensor built from a correlation join
 
@@ -925,19 +982,32 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
             x = add_cell("%s.body.%d" % (pre, j), x, 'n%d.b%d' % (i, j), xc, cout, 1 if j % 2 == 0 else 3)
             xc = cout
         route = x
-        tip = add_cell(pre + ".tip", route, 'n%d.tip' % i, c, 2 * c, 3)
+        if rnn == 'late':
+            tip = T('n%d.tip' % i, 2 * c, d, fr=K)
+            nodes.append(GruNode('rnn.tip%d' % i, "yolo_tips.%d.tip.rnn" % i, route, tip, K, c, 2 * c, 3, d, 2 * c))
+        else:
+            tip = add_cell(pre + ".tip", route, 'n%d.tip' % i, c, 2 * c, 3)
         tipc = 2 * c
-        if late and not temporal_out and corr:                  # yolo3.py:1139-1140: correlation join of the tip
+        if rnn == 'out':
+            # YOLOOutputV3 with rnn_shape (yolo3.py:58-60,152-155): the K tips -> K predictions -> TemporalPooling
+            Ap = round_up(A, 32)
+            pr = T('n%d.rnn' % i, A, d, Ap, fr=K)
+            nodes.append(GruNode('rnn.out%d' % i, "yolo_outputs.%d.prediction.rnn" % i, tip, pr, K, 2 * c, A, 1, d, Ap))
+            hd = T('head%d' % i, A, d, Ap)
+            nodes.append(PoolNode('pool.head%d' % i, pr, hd, K, k_join_type))
+            heads.append(hd)
+        elif late and not temporal_out and corr:                  # yolo3.py:1139-1140: correlation join of the tip
             tip, tipc = corr_join('n%d.tip' % i, tip, 2 * c, d)
         elif late and not temporal_out:                         # yolo3.py:1134-1138: join the tip over K
             tipc = 2 * c * (K if k_join_type == 'cat' else 1)
             ptip = T('n%d.tip.pool' % i, tipc, d)
             nodes.append(PoolNode('pool.tip%d' % i, tip, ptip, K, k_join_type))
             tip = ptip
-        hfr = K if temporal_out else 1                          # per-frame predictions (TimeDistributed(output))
-        hd = T('head%d' % i, A, d, round_up(A, 32), fr=hfr)
-        nodes.append(ConvNode("yolo_outputs.%d.prediction" % i, tip, hd, tipc, A, 1, 1, d, bn=False, head=True, fr=hfr))
-        heads.append(hd)
+        if rnn != 'out':
+            hfr = K if temporal_out else 1                      # per-frame predictions (TimeDistributed(output))
+            hd = T('head%d' % i, A, d, round_up(A, 32), fr=hfr)
+            nodes.append(ConvNode("yolo_outputs.%d.prediction" % i, tip, hd, tipc, A, 1, 1, d, bn=False, head=True, fr=hfr))
+            heads.append(hd)
         if i < 2:
             tr = T('n%d.tr' % i, c // 2, d, fr=nfr)
             nodes.append(ConvNode("transitions.%d%s" % (i, ".model" if (late and td_names) else ""), route, tr, c, c // 2,
@@ -962,8 +1032,20 @@ class YOLOV3(object):
 
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, ignore_iou_thresh=0.7,
                  device="cuda", syncbn_scope=None, process_group=None, k=1, k_join_type=None, k_join_pos=None,
-                 block_conv_type='2', noback=False, temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0):
+                 block_conv_type='2', noback=False, temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0,
+                 rnn_pos=None):
         self._classes = list(classes)
+        # bidirectional ConvGRU (RNN, layers.py:267-306).  What the factory refuses is refused here too: nothing is dropped
+        if rnn_pos is not None:
+            if rnn_pos not in ('late', 'out'):
+                raise ValueError("rnn_pos must be None, 'late' or 'out', got %r" % (rnn_pos,))
+            if not (k and k > 1) or noback or temporal_out or temporal_side or block_conv_type != '2' or corr_pos is not None \
+                    or (rnn_pos == 'late' and (k_join_pos != 'late' or k_join_type not in ('max', 'mean', 'cat'))) \
+                    or (rnn_pos == 'out' and k_join_type not in ('max', 'mean')):
+                raise NotImplementedError("rnn_pos %r needs a window k > 1 of the plain YOLOV3T network with block_conv_type '2', "
+                                          "no corr_pos, and a late max / mean / cat join ('late') or a max / mean join ('out'); "
+                                          "yolo3_darknet53() names the reason for each" % (rnn_pos,))
+        self._rnn_pos = rnn_pos
         self._corr_pos, self._corr_d = corr_pos, int(corr_d or 0)   # correlation join (Corr, layers.py:93-132)
         self.temporal_side = bool(temporal_side)  # YOLOV3Temporal(t_out=False): strided 2+1-D side branches, one output
         self.temporal_out = bool(temporal_out)   # YOLOV3Temporal(t_out=True): per-frame detections / losses
@@ -1014,10 +1096,13 @@ class YOLOV3(object):
                                                                 self._k_join_pos, self._block_conv_type,
                                                                 noback=self.noback, temporal_out=self.temporal_out,
                                                                 temporal_side=self.temporal_side, corr_pos=self._corr_pos,
-                                                                corr_d=self._corr_d)
+                                                                corr_d=self._corr_d, rnn_pos=self._rnn_pos)
         self._head_frames = self._k if self.temporal_out else 1
         self.input_tensors = [nm for nm, _, _ in ROUTE_TENSORS] if self.noback else ['in']
-        self.conv_nodes = [n for n in self.nodes if isinstance(n, ConvNode)]
+        self.gru_nodes = [n for n in self.nodes if isinstance(n, GruNode)]
+        # (a GruNode's four convolutions take their place in the arena order where the node stands)
+        self.conv_nodes = [m for n in self.nodes for m in ([n] if isinstance(n, ConvNode) else
+                                                           [cn for _, i2h, h2h in n.cells for cn in (i2h, h2h)] if isinstance(n, GruNode) else [])]
         # The loss gradient (dhead: (sigmoid - target) x mask) is sparse and saturated - after a few hundred steps most of its
         # entries sit 2^20 .. 2^30 below its largest ones, and an output of its consumers that reads only such entries (a
         # background pixel of the data gradient) would be formed from operands the fp16 split has staged with a handful of
@@ -1098,7 +1183,14 @@ class YOLOV3(object):
             wv = self.weights[n.w_off:n.w_off + n.w_numel]
             gv = self.grads[n.w_off:n.w_off + n.w_numel]
             n.wp, n.gwp = wv, gv
-            if n.head:
+            if getattr(n, 'gru', None) is not None:
+                # i2h_weight (3 Ch, Cin, s, s) / h2h_weight (3 Ch, Ch, s, s) in the weight range, the biases (3 Ch,) in the
+                # vector range beside the head bias (--no_wd, wd_mult, lr_mult reach them there)
+                reg(n.pw, (3 * n.gate_ch, n.ref_cin, n.k, n.k), 'gru_weight', n, wv, gv, off=n.w_off)
+                n.bias = self.weights[n.bias_off:n.bias_off + n.co_pad]
+                n.gbias = self.grads[n.bias_off:n.bias_off + n.co_pad]
+                reg(n.pb, (3 * n.gate_ch,), 'gru_bias', n, n.bias, n.gbias, off=n.bias_off)
+            elif n.head:
                 reg(n.name + ".weight", (n.cout, n.ref_cin, 1, 1), 'conv_weight', n, wv, gv, off=n.w_off)
                 n.bias = self.weights[n.bias_off:n.bias_off + n.co_pad]
                 n.gbias = self.grads[n.bias_off:n.bias_off + n.co_pad]
@@ -1160,7 +1252,7 @@ class YOLOV3(object):
                 p.set_data(v)
             elif name.endswith('bias'):
                 v = torch.zeros(p.shape)
-                if obj_bias != 0.0:
+                if obj_bias != 0.0 and p.kind != 'gru_bias':
                     v.view(3, -1)[:, 4] = obj_bias
                 p.set_data(v)
             else:
@@ -1170,6 +1262,9 @@ class YOLOV3(object):
 
     def reset_class(self, classes, reuse_weights=None):
         """yolo3.py:1230-1302 + YOLOOutputV3.reset_class :76-129: rebuild the 3 prediction convs."""
+        if self._rnn_pos == 'out':
+            raise NotImplementedError("reset_class on an rnn_pos='out' network: its predictions come from the GRU cells' gate "
+                                      "blocks, and the reference's own YOLOOutputV3.reset_class doubts that path; retrain it")
         old_classes, old = self._classes, {k: p.data().cpu() for k, p in self._params.items()}
         old_attr = {k: (p.grad_req, p.wd_mult, p.lr_mult) for k, p in self._params.items()}
         old_npred = 5 + len(old_classes)
@@ -1225,6 +1320,8 @@ class YOLOV3(object):
     def _node_trainable(self, n):
         """(weight trainable, any of gamma / beta / bias trainable) of a conv node."""
         P = self._params
+        if getattr(n, 'gru', None) is not None:
+            return P[n.pw].grad_req != 'null', P[n.pb].grad_req != 'null'
         if n.head:
             return P[n.name + ".weight"].grad_req != 'null', P[n.name + ".bias"].grad_req != 'null'
         return (P[n.name + ".0.weight"].grad_req != 'null',
@@ -1280,6 +1377,17 @@ class YOLOV3(object):
         if self.noback:
             for nm, c_, d_ in ROUTE_TENSORS:                                   # NCHW staging of the three inputs
                 bufs['in:' + nm] = torch.empty(B, c_, H // d_, W // d_, device=dev)
+        for g in self.gru_nodes:
+            # per direction: I = i2h of the folded frames (backward: dI in place), H = h2h of a step (training keeps every
+            # step's: backward recomputes the gates from I and H and writes dH in place), h = the states, step-major
+            # [K][B] so that one step is a contiguous B-frame operand, dh = the state gradient carried between steps
+            h_, w_ = H // g.div, W // g.div
+            for cname, i2h, h2h in g.cells:
+                bufs[i2h.dst] = torch.empty(B * g.K, h_, w_, 3 * g.chp, device=dev)
+                bufs[h2h.dst] = torch.empty(B * g.K if train else B, h_, w_, 3 * g.chp, device=dev)
+                bufs[g.key(cname, 'h')] = torch.empty(B * g.K, h_, w_, g.chp, device=dev)
+                if train:
+                    bufs[g.key(cname, 'dh')] = torch.empty(B, h_, w_, g.chp, device=dev)
         # max-abs slots (operand scales of the fp16-split arithmetic): one set per activation tensor, and in training
         # per conv node for the gradient dz it consumes; zeroed by the first record of every forward program
         if not bf16:
@@ -1427,6 +1535,75 @@ class YOLOV3(object):
             prog.add('vd_add', a.data_ptr(), b_.data_ptr(), o.data_ptr(), o.numel())
             prog.add('vd_amax', o.data_ptr(), o.numel(), am(n.dst))
 
+    # ------------------------------------------------------------------ bidirectional ConvGRU (GruNode)
+    def _gru_conv_desc(self, cn, x, out, N, H, W, sidx, amax_in=None):
+        """forward record of one of a GRU cell's convolutions (stride 1, 'same', bias in the epilogue) on N frames of `x`.
+        No arithmetic flag is set here: autotune_program, at the end of the plan build, picks it per record (autotune_desc),
+        and a record without max-abs slots for its operand (amax_in None: the state) can only get the fp32 MFMA or the
+        3-way bf16 split there, never the fp16 split (_tile_candidates) - the range-exact arithmetics."""
+        d = ConvDesc()
+        Hc, Wc = H // cn.div_in, W // cn.div_in
+        d.in_, d.wp, d.out = x.data_ptr(), cn.wp.data_ptr(), out.data_ptr()
+        d.N, d.Hi, d.Wi, d.Ci = N, Hc, Wc, cn.cin
+        d.Hg, d.Wg, d.in_stride = Hc, Wc, 1
+        ops._set_taps(d, cn.taps())
+        d.Kfr, d.Ho, d.Wo, d.Co = 1, Hc, Wc, cn.co_pad
+        d.out_stride, d.out_oy, d.out_ox = 1, 0, 0
+        d.ldo = d.ldr = cn.co_pad
+        d.flags, d.slope, d.shift = EPI_AFFINE, LEAKY_SLOPE, cn.bias.data_ptr()
+        d.amax_in, d.amax_w = amax_in, cn.wamax.data_ptr()
+        self._set_streamk(d, sidx)
+        return d
+
+    @staticmethod
+    def _gru_meta(cn, N, H, W, kind):
+        """roofline record of a GRU conv launch over N frames (the form of _flops)"""
+        px = N * (H // cn.div_in) * (W // cn.div_in)
+        return dict(kind=kind, node=cn.name, k=cn.k, stride=1, flops=2.0 * cn.cin * cn.cout * cn.k * cn.k * px,
+                    bytes=4.0 * (px * cn.cin + px * cn.cout + cn.cout * cn.cin * cn.k * cn.k))
+
+    def _add_gru_fwd(self, prog, g, bufs, B, H, W, train, side=None, ev_record=None, ev_wait=None):
+        """Forward launches of a GruNode.  Per direction ONE i2h conv over the B*K folded frames, then per step one h2h conv
+        on the B frames of the previous state (none at the first step: the state is zero, the gate kernel takes the h2h
+        bias) and one gate launch; then the average of the two directions into the folded output.  Training: the reverse
+        direction's chain runs on `side`; inference keeps one stream (no parallel branches in a captured graph) and one
+        H slab."""
+        K, hw = g.K, (H // g.div) * (W // g.div)
+        x = bufs[g.src]
+        par = train and side is not None
+        if par:
+            e_x, e_r = torch.cuda.Event(), torch.cuda.Event()
+            prog.add_py(ev_record(e_x, False))
+            prog.add_py(ev_wait(e_x, True))
+            prog.hold(e_x, e_r)
+        for di, (cname, i2h, h2h) in reversed(list(enumerate(g.cells))):      # the side stream's chain is queued first
+            st = side if (par and di == 1) else None
+            sidx = 4 if st is not None else 0                                # (0..3: main stream and the parity streams)
+            I, Hb, hs = bufs[i2h.dst], bufs[h2h.dst], bufs[g.key(cname, 'h')]
+            d = self._gru_conv_desc(i2h, x, I, B * K, H, W, sidx, self._amax_or_none(bufs, g.src))
+            prog.hold(d)
+            prog.add('vd_conv_igemm', C.byref(d), meta=self._gru_meta(i2h, B * K, H, W, 'fwd'), stream=st)
+            for s_ in range(K):
+                t = s_ if di == 0 else K - 1 - s_
+                Hs = None
+                if s_ > 0:
+                    Hs = Hb[s_ * B:(s_ + 1) * B] if train else Hb
+                    d = self._gru_conv_desc(h2h, hs[(s_ - 1) * B:s_ * B], Hs, B, H, W, sidx)
+                    prog.hold(d)
+                    prog.add('vd_conv_igemm', C.byref(d), meta=self._gru_meta(h2h, B, H, W, 'fwd'), stream=st)
+                prog.add('vd_gru_gate_fwd', I.data_ptr(), Hs.data_ptr() if s_ > 0 else None, h2h.bias.data_ptr(),
+                         hs[(s_ - 1) * B:].data_ptr() if s_ > 0 else None, hs[s_ * B:].data_ptr(), B, K, t, hw, g.chp,
+                         meta=dict(kind='gru_gate_fwd', node=g.name, flops=14.0 * B * hw * g.chp,
+                                   bytes=4.0 * B * hw * g.chp * (8 if s_ > 0 else 4)), stream=st)
+            if st is not None:
+                prog.add_py(ev_record(e_r, True))
+        if par:
+            prog.add_py(ev_wait(e_r, False))
+        y = bufs[g.dst]
+        prog.add('vd_gru_avg', bufs[g.key('l_cell', 'h')].data_ptr(), bufs[g.key('r_cell', 'h')].data_ptr(), y.data_ptr(), B, K,
+                 hw * g.chp, bufs['amax:' + g.dst].data_ptr(),
+                 meta=dict(kind='gru_avg', node=g.name, flops=2.0 * B * K * hw * g.chp, bytes=12.0 * B * K * hw * g.chp))
+
     def _add_amax_reset(self, prog, bufs):
         prog.add('vd_fill', bufs['amax'].data_ptr(), 0.0, bufs['amax'].numel())
 
@@ -1488,6 +1665,9 @@ class YOLOV3(object):
                 continue
             if isinstance(n, (SelNode, AddNode)):
                 self._add_sel_add_fwd(prog, n, bufs, B)
+                continue
+            if isinstance(n, GruNode):
+                self._add_gru_fwd(prog, n, bufs, B, H, W, False)
                 continue
             if n.stem:
                 self._add_stem(prog, n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, leaky=True)
@@ -1551,6 +1731,9 @@ class YOLOV3(object):
         """'fp32' (reference precision) or 'bf16' (BASELINE configs[1]): bf16 storage + bf16 MFMA with fp32
         accumulation and fp32 epilogue for inference; the prediction heads stay fp32."""
         assert precision in ('fp32', 'bf16')
+        if precision == 'bf16' and self._rnn_pos:
+            raise NotImplementedError("bf16 inference is not built for rnn_pos networks: the ConvGRU gate kernels (vd_gru.hip) "
+                                      "and the recurrent state are fp32 only")
         self.precision = precision
 
     def _build_infer_bf16(self, B, H, W):
@@ -1923,6 +2106,18 @@ class YOLOV3(object):
             seg.hold(d, wb)
             return d
 
+        side = torch.cuda.Stream(priority=int(__import__('os').environ.get('VD_SIDE_PRIO', '0'))) if self.overlap_wgrad else None
+
+        def ev_record(e, on_side):
+            def f():
+                e.record(side if on_side else torch.cuda.current_stream())
+            return f
+
+        def ev_wait(e, on_side):
+            def f():
+                (side if on_side else torch.cuda.current_stream()).wait_event(e)
+            return f
+
         # ---- forward: list of segments; a segment is a Program or a python callable (collectives)
         fwd, seg = [], Program()
         if not bf16:
@@ -1960,6 +2155,9 @@ class YOLOV3(object):
                 continue
             if isinstance(n, (SelNode, AddNode)):
                 self._add_sel_add_fwd(seg, n, bufs, B)
+                continue
+            if isinstance(n, GruNode):
+                self._add_gru_fwd(seg, n, bufs, B, H, W, True, side, ev_record, ev_wait)
                 continue
             Ho, Wo = H // n.div_out, W // n.div_out
             tvalid = getattr(n, 'tvalid', False)
@@ -2026,12 +2224,13 @@ class YOLOV3(object):
         losses = torch.zeros(B * self._head_frames, 4, device=dev)
         dh = (C.c_void_p * 3)(*[bufs['d:' + h].data_ptr() for h in self.head_names])
         head_node = {m.dst: m for m in self.conv_nodes if m.head}
-        dha = None if bf16 else (C.c_void_p * 3)(*[amx('dz:' + head_node[h].name) for h in self.head_names])   # max-abs of the three dhead
+        # (an rnn_pos='out' network has no prediction convs: nothing reads the loss gradient as a conv operand)
+        dha = None if (bf16 or not head_node) else (C.c_void_p * 3)(*[amx('dz:' + head_node[h].name) for h in self.head_names])   # max-abs of the three dhead
         lws = torch.empty(max(16, ops.yolo_loss_ws_bytes(hd)), dtype=torch.uint8, device=dev)
         seg.hold(hd, dh, dha, lws)
         seg.add('vd_yolo_loss_fwd_bwd' + sfx, C.byref(hd), slots['gt'], slots['M'], slots['obj'], slots['ctr'], slots['scl'],
                 slots['wgt'], slots['cls'], float(self._ignore_iou_thresh), slots['smooth'], losses.data_ptr(),
-                C.byref(dh), None, *([] if bf16 else [C.byref(dha)]), lws.data_ptr(), lws.numel())
+                C.byref(dh), None, *([] if bf16 else [C.byref(dha) if dha is not None else None]), lws.data_ptr(), lws.numel())
         fwd.append(seg)
 
         # ---- backward
@@ -2040,23 +2239,11 @@ class YOLOV3(object):
         # so the only edges are  dz ready -> wgrad  (event) and  wgrad done -> dz scratch reuse  (event; the dz
         # scratch is double-buffered), plus one join before the optimiser.  Tails of one GEMM fill with the other.
         bwd, seg = [], Program()
-        side = torch.cuda.Stream(priority=int(__import__('os').environ.get('VD_SIDE_PRIO', '0'))) if self.overlap_wgrad else None
         ws_w = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if side is not None else ws
         dz_bufs = [bufs['dz'], bufs['dz2']]
         dz_free = [None, None]             # event after which dz_bufs[i] may be overwritten
         n_dz = [0]
         last_side = [None]
-
-        def ev_record(e, on_side):
-            def f():
-                e.record(side if on_side else torch.cuda.current_stream())
-            return f
-
-        def ev_wait(e, on_side):
-            def f():
-                (side if on_side else torch.cuda.current_stream()).wait_event(e)
-            return f
-
         bucket_hi, bucket_acc = [self.n_weight], [0]
         written = set(self.head_names)     # gradients already produced (the loss kernel wrote d:head*)
         dgrad_packs = []                   # (node, plan, packed weight buffer) re-packed when weights change
@@ -2089,6 +2276,8 @@ class YOLOV3(object):
                 tgrad[m.dst] = tgrad[m.up] or tgrad[m.route]
             elif isinstance(m, AddNode):
                 tgrad[m.dst] = tgrad[m.a] or tgrad[m.b]
+            elif isinstance(m, GruNode):
+                tgrad[m.dst] = tgrad[m.src] or any(any(self._node_trainable(cn)) for _, a_, b_ in m.cells for cn in (a_, b_))
             else:
                 tgrad[m.dst] = tgrad[m.src]
         wtrain = [m for m in self.conv_nodes if self._node_trainable(m)[0]]
@@ -2127,7 +2316,119 @@ class YOLOV3(object):
             d.bs_mean, d.bs_invstd = m.b_mean.data_ptr(), m.b_invstd.data_ptr()
             d.bs_part, d.bs_slope = stats_ws.data_ptr() + part_off, LEAKY_SLOPE
 
+        def gru_dgrad(cn, din, nfr, dout, acc, sidx, st, packs):
+            """data gradient of a GRU conv over nfr frames: din [nfr, h, w, 3 chp] -> dout [nfr, h, w, cn.cin] (+= when acc)"""
+            Hc, Wc = H // cn.div_in, W // cn.div_in
+            if cn not in packs:
+                plan = dgrad_plans(cn.k, cn.pad, 1, Hc, Wc)[0]
+                wpk = torch.empty(cn.cin * len(plan['taps']) * cn.co_pad, device=dev)
+                dgrad_packs.append((cn, plan, wpk))
+                packs[cn] = (plan, wpk)
+            plan, wpk = packs[cn]
+            d = ConvDesc()
+            d.in_, d.wp, d.out = din.data_ptr(), wpk.data_ptr(), dout.data_ptr()
+            d.N, d.Hi, d.Wi, d.Ci = nfr, Hc, Wc, cn.co_pad
+            d.Hg, d.Wg, d.in_stride = plan['Hg'], plan['Wg'], 1
+            ops._set_taps(d, plan['taps'])
+            d.Kfr, d.Ho, d.Wo, d.Co = 1, Hc, Wc, cn.cin
+            d.out_stride, d.out_oy, d.out_ox = 1, plan['py'], plan['px']
+            d.ldo = d.ldr = cn.cin
+            d.flags, d.slope = (EPI_RESIDUAL if acc else 0), LEAKY_SLOPE
+            # gate gradients are saturated like the loss gradient: no max-abs slots, so autotune_program (end of the build)
+            # can only choose the fp32 MFMA or the 3-way bf16 split for this record, never the fp16 split
+            d.amax_in, d.amax_w = None, cn.wamax.data_ptr()
+            if acc:
+                d.residual = dout.data_ptr()
+            self._set_streamk(d, sidx)
+            seg.hold(d, wpk)
+            seg.add('vd_conv_igemm', C.byref(d), meta=self._gru_meta(cn, nfr, H, W, 'dgrad'), stream=st)
+
+        def gru_wgrad(cn, xin, dout, nfr, amax_in):
+            """weight gradient of a GRU conv over nfr frames, on the side stream like every weight gradient"""
+            Hc, Wc = H // cn.div_in, W // cn.div_in
+            wd_ = WgradDesc()
+            wd_.in_, wd_.dout, wd_.dwp = xin.data_ptr(), dout.data_ptr(), cn.gwp.data_ptr()
+            wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = nfr, Hc, Wc, cn.cin
+            wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Hc, Wc, cn.co_pad, cn.co_pad
+            wd_.in_stride = 1
+            ops._set_taps(wd_, cn.taps())
+            wd_.Kfr, wd_.splits = 1, 0
+            wd_.amax_in, wd_.amax_dout = amax_in, None
+            autotune_wgrad(wd_, ws.data_ptr(), ws_bytes)
+            seg.hold(wd_)
+            meta = self._gru_meta(cn, nfr, H, W, 'wgrad')
+            if side is not None:
+                e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
+                seg.add_py(ev_record(e_ready, False))
+                seg.add_py(ev_wait(e_ready, True))
+                seg.add('vd_conv_wgrad', C.byref(wd_), ws_w.data_ptr(), ws_bytes, meta=meta, stream=side)
+                seg.add_py(ev_record(e_done, True))
+                seg.hold(e_ready, e_done)
+                last_side[0] = e_done
+            else:
+                seg.add('vd_conv_wgrad', C.byref(wd_), ws.data_ptr(), ws_bytes, meta=meta)
+            bucket_acc[0] += cn.w_numel
+            if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or cn is first_wtrain):
+                lo, hi = cn.w_off, bucket_hi[0]
+                seg.add_py(self._bucket_launcher(lo, hi, side))
+                bucket_hi[0], bucket_acc[0] = lo, 0
+
+        def gru_backward(g):
+            """Backward through time of a GruNode: per direction, steps in reverse - gate backward (dI, dH in place, the
+            state gradient scaled by z), then the h2h data gradient ADDED into that state gradient by its residual epilogue;
+            the reverse direction's chain on the side stream.  Then, batched over time: one i2h data gradient and one i2h
+            weight gradient per direction over the B*K frames, one h2h weight gradient over the B*(K-1) frames that had a
+            state, and the bias gradients as column sums of dI / dH (the head bias's path)."""
+            K, hw = g.K, (H // g.div) * (W // g.div)
+            dy = bufs['d:' + g.dst]
+            packs = {}
+            if side is not None:
+                e_dy, e_r = torch.cuda.Event(), torch.cuda.Event()
+                seg.add_py(ev_record(e_dy, False))
+                seg.add_py(ev_wait(e_dy, True))
+                seg.hold(e_dy, e_r)
+            for di, (cname, i2h, h2h) in reversed(list(enumerate(g.cells))):
+                st = side if (side is not None and di == 1) else None
+                sidx = 4 if st is not None else 0
+                I, Hb, hs, dh = bufs[i2h.dst], bufs[h2h.dst], bufs[g.key(cname, 'h')], bufs[g.key(cname, 'dh')]
+                for s_ in reversed(range(K)):
+                    t = s_ if di == 0 else K - 1 - s_
+                    Hs = Hb[s_ * B:(s_ + 1) * B]
+                    seg.add('vd_gru_gate_bwd', I.data_ptr(), Hs.data_ptr(), 1 if s_ > 0 else 0, h2h.bias.data_ptr(),
+                            hs[(s_ - 1) * B:].data_ptr() if s_ > 0 else None, dy.data_ptr(), 0.5, dh.data_ptr(),
+                            1 if s_ < K - 1 else 0, B, K, t, hw, g.chp,
+                            meta=dict(kind='gru_gate_bwd', node=g.name, flops=30.0 * B * hw * g.chp,
+                                      bytes=4.0 * B * hw * g.chp * (16 if s_ > 0 else 11)), stream=st)
+                    if s_ > 0:
+                        gru_dgrad(h2h, Hs, B, dh, True, sidx, st, packs)
+                if st is not None:
+                    seg.add_py(ev_record(e_r, True))
+            if side is not None:
+                seg.add_py(ev_wait(e_r, False))
+            if tgrad[g.src]:
+                dsrc, acc = grad_into(g.src)
+                for di, (cname, i2h, h2h) in enumerate(g.cells):
+                    gru_dgrad(i2h, bufs[i2h.dst], B * K, dsrc, acc or di > 0, 0, None, packs)
+            for cname, i2h, h2h in g.cells:
+                for cn in (i2h, h2h):
+                    if self._node_trainable(cn)[1]:
+                        dz_ = bufs[cn.dst]
+                        seg.add('vd_bn_stats', dz_.data_ptr(), B * K * hw, cn.co_pad, cn.sums.data_ptr(), ws.data_ptr(), ws_bytes)
+                        seg.add('vd_bn_param_grads', cn.sums.data_ptr(), cn.co_pad, bufs['tmp'].data_ptr(), cn.gbias.data_ptr())
+            for cname, i2h, h2h in reversed(g.cells):                # reverse arena order (the gradient buckets)
+                hs, Hb = bufs[g.key(cname, 'h')], bufs[h2h.dst]
+                if self._node_trainable(h2h)[0]:
+                    gru_wgrad(h2h, hs, Hb[B:], B * (K - 1), None)
+                if self._node_trainable(i2h)[0]:
+                    gru_wgrad(i2h, bufs[g.src], bufs[i2h.dst], B * K, self._amax_or_none(bufs, g.src))
+
         for n in reversed(self.nodes):
+            if isinstance(n, GruNode):
+                if tgrad[n.dst]:
+                    assert n.dst in written, n.name
+                    materialize(n.dst)
+                    gru_backward(n)
+                continue
             if isinstance(n, UpcatNode):
                 if not tgrad[n.dst]:
                     continue
@@ -2455,6 +2756,9 @@ class YOLOV3(object):
         bf16 tolerance (tests/test_bf16_train_gpu.py, test_model_gpu.py)."""
         if storage not in ('fp32', 'bf16'):
             raise ValueError("storage must be 'fp32' or 'bf16'")
+        if storage == 'bf16' and getattr(self, '_rnn_pos', None):
+            raise NotImplementedError("bf16-storage training is not built for rnn_pos networks: the ConvGRU gate kernels "
+                                      "(vd_gru.hip) and the recurrent state are fp32 only")
         if storage == 'bf16' and (self.noback or self.temporal_out or getattr(self, 'temporal_side', False)):
             raise NotImplementedError("bf16-storage training is built for yolo3_darknet53 and the k > 1 windows of YOLOV3T (every "
                                       "join, neck and correlation variant), not for the noback, temporal_out and temporal_side "
@@ -2753,11 +3057,33 @@ class YOLOV3(object):
 
 def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs=None, freeze_base=False,
                     k=None, k_join_type=None, k_join_pos=None, block_conv_type='2', temporal=False, t_out=False,
-                    corr_d=None, corr_pos=None, **kwargs):
+                    corr_d=None, corr_pos=None, rnn_pos=None, **kwargs):
     """wrappers.py:9-110 -> YOLOV3T (yolo3.py:959-1054).  norm_layer='syncbn' (the reference passes
     SyncBatchNorm) selects the SyncBN collective.  k>1 builds the temporal-window variants; `t_out=True`
     (--temp --mult_out) builds YOLOV3Temporal with per-frame outputs (yolo3_temporal.py:286-555, t = k = 5)."""
     k = 1 if k is None else int(k)
+    if rnn_pos is not None:
+        # the bidirectional ConvGRU (RNN, layers.py:267-306; yolo3.py:978-988): what is built, and what is refused by name
+        if rnn_pos not in ('late', 'out'):
+            raise ValueError("rnn_pos must be None, 'late' or 'out', got %r" % (rnn_pos,))
+        if temporal or t_out:
+            raise NotImplementedError("rnn_pos with temporal / t_out: YOLOV3Temporal has no RNN (yolo3_temporal.py)")
+        if k < 2:
+            raise NotImplementedError("rnn_pos needs a window of k > 1 frames: the GRU runs over the K frames (k = %d)" % k)
+        if block_conv_type != '2':
+            raise NotImplementedError("rnn_pos with block_conv_type %r: the reference swaps axes 1 and 2 of the RNN output "
+                                      "there, so the join would pool over channels; block_conv_type '2' only" % (block_conv_type,))
+        if corr_pos is not None:
+            raise NotImplementedError("rnn_pos with corr_pos: the correlation join and the RNN are not combined (the "
+                                      "reference's `elif` never reaches Corr behind a late join, and 'out' skips every join)")
+        if rnn_pos == 'late' and (k_join_pos != 'late' or k_join_type not in ('max', 'mean', 'cat')):
+            raise NotImplementedError("rnn_pos 'late' needs k_join_pos 'late' and k_join_type max / mean / cat "
+                                      "(yolo3.py:986-988)")
+        if rnn_pos == 'out' and k_join_type not in ('max', 'mean'):
+            raise NotImplementedError("rnn_pos 'out' needs k_join_type max or mean: TemporalPooling joins the K predictions "
+                                      "and asserts it (layers.py:168), got %r" % (k_join_type,))
+        if rnn_pos == 'out':
+            k_join_pos = k_join_pos or 'late'                     # not read: 'out' guards every early / late join
     if temporal or t_out:                                         # wrappers.py:96-98
         if corr_d:
             raise NotImplementedError("YOLOV3Temporal with a correlation branch (corr_d) is outside the built scope")
@@ -2803,7 +3129,7 @@ def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs
     if norm_layer == 'syncbn':
         scope = (norm_kwargs or {}).get('scope', 'all')
     net = YOLOV3(classes, syncbn_scope=scope, k=k, k_join_type=k_join_type, k_join_pos=k_join_pos,
-                 block_conv_type=block_conv_type, **corr, **kwargs)
+                 block_conv_type=block_conv_type, rnn_pos=rnn_pos, **corr, **kwargs)
     if freeze_base:                          # wrappers.py:55-57: every Darknet parameter leaves the gradient / update
         for name, p in net.collect_params('stages.*').items():
             p.grad_req = 'null'

@@ -5,6 +5,7 @@ Follows /root/reference/detect_yolo3.py: flags :41-118, detect() :198-272 (infer
 id >= 0, normalise boxes by W, collect [id, score, x1, y1, x2, y2] per image path), save_predictions :275-330
 (one `path,id,score,x1,y1,x2,y2` text file per image), load_predictions/evaluate :333-448,659-695 (VOC mAP; the
 reference's `sid=` keyword bug at :693 is not reproduced), main :792-939 (net build :871-892).
+`--window K,1 --conv_types 21,...` detects with yolo3_3ddarknet (:872-882), the (2+1)-D Darknet backbone of frame windows.
 The network underneath is viddet_amd.model.YOLOV3 (hand-written HIP kernels).  Frames shard across ranks with
 no collective on the data path (inference = replicas only); the per-image box lists are gathered to rank 0, which writes
 the prediction files and evaluates.  Visualisation / worst-video / COCO+VID metrics are out of scope.
@@ -24,7 +25,7 @@ from viddet_amd import dist as vdist
 from viddet_amd.data import SyntheticDetection, SyntheticCombined, YOLO3VideoInferenceTransform, Loader
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
-from viddet_amd.model import yolo3_darknet53
+from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
 from train_yolov3 import _list, _bool
 
 
@@ -158,6 +159,16 @@ def main(argv=None):
         v = getattr(FLAGS, flag)
         if v and not (isinstance(v, str) and not v.strip()):
             raise NotImplementedError("--%s is outside the yolo3_darknet53 hot path" % flag)
+    # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
+    ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
+    if ct is not None:
+        for flag, on in (("k_join_type", FLAGS.k_join_type), ("k_join_pos", FLAGS.k_join_pos), ("rnn_pos", FLAGS.rnn_pos),
+                         ("corr_pos", FLAGS.corr_pos), ("precision", FLAGS.precision == "bf16"),
+                         ("block_conv_type", FLAGS.block_conv_type != "2")):
+            if on:
+                raise NotImplementedError("--%s does not combine with --conv_types %s: yolo3_3ddarknet is not passed it (its "
+                                          "neck is the single-frame one; the temporal-conv kernels are fp32)"
+                                          % (flag, ",".join(str(c) for c in ct)))
     rank, world = vdist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("detect_yolo3.py needs an MI355X: the HIP path has no CPU fallback")
@@ -172,9 +183,12 @@ def main(argv=None):
     loader = Loader(dataset, YOLO3VideoInferenceTransform(FLAGS.data_shape, FLAGS.data_shape, device_normalize=True),
                     FLAGS.batch_size, train=False, last_batch="keep", rank=rank, world=world)
     # detect_yolo3.py:871-892
-    net = yolo3_darknet53(dataset.classes, pretrained_base=False, k=FLAGS.window[0], k_join_type=FLAGS.k_join_type,
-                          k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type,
-                          corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d, rnn_pos=FLAGS.rnn_pos or None)
+    if ct is not None:
+        net = yolo3_3ddarknet(dataset.classes, pretrained_base=False, conv_types=ct, k=FLAGS.window[0])
+    else:
+        net = yolo3_darknet53(dataset.classes, pretrained_base=False, k=FLAGS.window[0], k_join_type=FLAGS.k_join_type,
+                              k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type,
+                              corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d, rnn_pos=FLAGS.rnn_pos or None)
     if FLAGS.random_init:
         net.initialize(init="he", obj_bias=-2.0)
     else:

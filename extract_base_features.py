@@ -37,6 +37,7 @@ def parse_flags(argv=None):
     A("--num_workers", type=int, default=8)
     A("--model_path", default="", help="checkpoint of the full yolo3_darknet53 network to take the trunk from")
     A("--random_init", action="store_true", help="seeded random trunk (no pretrained weights exist offline)")
+    A("--conv_types", default="2,2,2,2,2,2", help="only the 2-D trunk has cached features: anything else is refused")
     A("--seed", type=int, default=233)
     A("--synthetic_samples", type=int, default=128)
     A("--dataset_seed", type=int, default=None, help="seed of the synthetic dataset (train uses --seed, val --seed+1)")
@@ -61,6 +62,9 @@ def main(argv=None):
     FLAGS = parse_flags(argv)
     if FLAGS.network != "darknet53":
         raise NotImplementedError("Backbone CNN model {} not implemented.".format(FLAGS.network))
+    if any(c.strip() != "2" for c in FLAGS.conv_types.split(",")):
+        raise NotImplementedError("--conv_types %s: the cached features are those of the per-frame 2-D Darknet-53 trunk; a "
+                                  "(2+1)-D trunk of frame windows has none" % FLAGS.conv_types)
     if not torch.cuda.is_available():
         raise SystemExit("extract_base_features.py needs an MI355X: the HIP path has no CPU fallback")
     dataset = SyntheticDetection(FLAGS.dataset, num_samples=FLAGS.synthetic_samples,

@@ -434,6 +434,22 @@ int vd_gru_gate_bwd(float* I, float* H, int h_valid, const float* hbias, const f
                     float* dh, int carry, int B, int K, int t, int64_t HW, int Ch, void* stream);
 int vd_gru_avg(const float* hl, const float* hr, float* y, int B, int K, int64_t inner, float* amax_out, void* stream);
 
+/* Temporal half of the BACKBONE's R(2+1)D cell (--conv_types 21; Conv3DRepPad, darknet/three_darknet.py:19-70):
+ * a depthwise (3,1,1) convolution over the K frames of a window with repeat padding, no bias, nothing behind it.
+ *   x, y, res, dy, dx  [B*K, HW, C] fp32 NHWC rows, frames folded (frame b*K + t);  w, dw [C][3] = the reference's (C,1,3,1,1)
+ *   y_t = w0 x_{max(t-1,0)} + w1 x_t + w2 x_{t+1 < K ? t+1 : K-2}  [+ res_t]
+ * The tail pad is frame K-2 (slice_axis(begin=-2, end=-1), :62), not the last frame; hence K >= 2.  C % 4 == 0, 16-byte
+ * aligned pointers.  res (optional) is the residual of DarknetBasicBlockV3 added in the same pass; amax_out (optional) as in
+ * vd_bn_apply_leaky: the max-abs of y for the convolutions that read it.
+ * vd_tdw_bwd: one launch reads dy (and x) once and writes dx (NULL = skipped) and one row of weight-gradient partial sums
+ * per workgroup into ws; a second launch adds the rows in a fixed order in fp64 into dw (NULL = skipped, ws not needed).
+ * Frame 0 of dx also collects w0 dy_0 and frame K-2 also collects w2 dy_{K-1}.  No atomics: bit-reproducible. */
+int vd_tdw_fwd(const float* x, const float* w, const float* res, float* y, int B, int K, int64_t HW, int C, float* amax_out,
+               void* stream);
+int64_t vd_tdw_bwd_ws_bytes(int B, int K, int64_t HW, int C);
+int vd_tdw_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, int B, int K, int64_t HW, int C, void* ws,
+               int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * YOLO head: decode / filter / NMS / targets / loss
  * Head tensors are the raw prediction-conv outputs, NHWC [B, g, g, ldh], channel = a*(5+C)+j,

@@ -8,7 +8,7 @@ mkdir -p build_dbg
 F="-O3 -fPIC --offload-arch=gfx950 -std=c++17 -Wall -Wno-unused-function -fno-slp-vectorize -Iinclude"
 /opt/rocm/bin/hipcc $F -DVD_C32_STAMP=1 -c viddet_amd/csrc/vd_conv_c32_bf16.hip -o build_dbg/vd_conv_c32_stamp.o
 (cd viddet_amd/csrc && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../build_dbg/libviddet_c32stamp.so vd_conv.o vd_conv_sk.o vd_conv_par.o \
-    vd_wgrad_halo.o vd_conv_bf16.o vd_conv_bf16_sk.o ../../build_dbg/vd_conv_c32_stamp.o vd_stem.o vd_bn.o vd_pointwise.o vd_corr.o vd_gru.o vd_yolo.o vd_api.o)
+    vd_wgrad_halo.o vd_conv_bf16.o vd_conv_bf16_sk.o ../../build_dbg/vd_conv_c32_stamp.o vd_stem.o vd_bn.o vd_pointwise.o vd_corr.o vd_gru.o vd_tdw.o vd_yolo.o vd_api.o)
 VD_LIB=build_dbg/libviddet_c32stamp.so python - <<'PY'
 import ctypes as C
 import numpy as np, torch

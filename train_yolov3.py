@@ -14,7 +14,8 @@ absl is not installed here: argparse re-creates the same flag surface (list flag
 extract_base_features.py); `--window 5 --temp --mult_out` builds YOLOV3Temporal with per-frame outputs.  Variants
 outside the built scope (--temp without --mult_out, --motion_stream, --new_model, --hier) are accepted and
 rejected with NotImplementedError like the reference's own guards.  `--window k --corr_pos early|late --corr_d d` builds
-the correlation join (Corr, layers.py:93-132); `--window k --rnn_pos late|out` the bidirectional ConvGRU over the window
+the correlation join (Corr, layers.py:93-132); `--window K,1 --conv_types 21,21,2,2,2,2` (the stem, then the five stages: a
+non-empty prefix of 21) builds yolo3_3ddarknet, the (2+1)-D Darknet backbone of frame windows (three_darknet.py:126-226); `--window k --rnn_pos late|out` the bidirectional ConvGRU over the window
 (RNN, layers.py:267-306).
 """
 import argparse
@@ -34,7 +35,7 @@ from viddet_amd import dist as vdist
 from viddet_amd.data import (SyntheticDetection, MixupDetection, YOLO3VideoTrainTransform, YOLO3VideoInferenceTransform, Loader,
                              FeatureDataset, YOLO3NBVideoTrainTransform, YOLO3NBVideoInferenceTransform)
 from viddet_amd.metrics import VOCMApMetric, VOCMApMetricTemporal, LossMetric
-from viddet_amd.model import yolo3_darknet53, yolo3_no_backbone
+from viddet_amd.model import yolo3_darknet53, yolo3_no_backbone, yolo3_3ddarknet, check_conv_types
 from viddet_amd.schedule import LRScheduler, LRSequential
 from viddet_amd.video import Rng
 
@@ -202,6 +203,27 @@ def get_net(classes, rank_world):
         if getattr(FLAGS, flag):
             raise NotImplementedError("--%s selects a research variant outside the yolo3_darknet53 hot path" % flag)
     k = int(FLAGS.window[0])
+    ct = check_conv_types(FLAGS.conv_types, k)          # :685 integers; None = all 2, the plain network
+    if ct is not None:
+        # :348,371-399: conv_types[0] != 2 selects yolo3_3ddarknet, which is handed the classes, the norm layer, freeze_base
+        # and conv_types and nothing else - every flag it would drop is refused by name
+        for flag, on in (("k_join_type", FLAGS.k_join_type), ("k_join_pos", FLAGS.k_join_pos), ("rnn_pos", FLAGS.rnn_pos),
+                         ("corr_pos", FLAGS.corr_pos), ("temp", FLAGS.temp), ("mult_out", FLAGS.mult_out),
+                         ("features_dir", FLAGS.features_dir is not None), ("mixup", FLAGS.mixup),
+                         ("storage", FLAGS.storage == "bf16"), ("block_conv_type", FLAGS.block_conv_type != "2")):
+            if on:
+                raise NotImplementedError("--%s does not combine with --conv_types %s: yolo3_3ddarknet is not passed it (its "
+                                          "neck is the single-frame one; the temporal-conv kernels are fp32)"
+                                          % (flag, ",".join(str(c) for c in ct)))
+        net = yolo3_3ddarknet(classes, pretrained_base=False,
+                              norm_layer="syncbn" if FLAGS.syncbn and rank_world[1] > 1 else None,
+                              norm_kwargs={"scope": "reference"},     # three_darknet.py:193: the blocks keep plain BatchNorm
+                              freeze_base=FLAGS.freeze_base, conv_types=ct, k=k)
+        net.initialize(init="he", seed=FLAGS.seed)
+        start_epoch = FLAGS.start_epoch
+        if FLAGS.resume.strip():
+            start_epoch = resume(net, FLAGS.resume, FLAGS.start_epoch)
+        return net, start_epoch
     if FLAGS.features_dir is not None:                 # :335-342
         net = yolo3_no_backbone(classes, norm_layer="syncbn" if FLAGS.syncbn and rank_world[1] > 1 else None,
                                 norm_kwargs={"scope": FLAGS.syncbn_scope})

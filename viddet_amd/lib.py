@@ -136,6 +136,9 @@ SIGNATURES = {
     "vd_gru_gate_fwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i64, _i, _p]),
     "vd_gru_gate_bwd": (_i, [_p, _p, _i, _p, _p, _p, _f, _p, _i, _i, _i, _i, _i64, _i, _p]),
     "vd_gru_avg": (_i, [_p, _p, _p, _i, _i, _i64, _p, _p]),
+    "vd_tdw_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i64, _i, _p, _p]),
+    "vd_tdw_bwd_ws_bytes": (_i64, [_i, _i, _i64, _i]),
+    "vd_tdw_bwd": (_i, [_p, _p, _p, _p, _p, _i, _i, _i64, _i, _p, _i64, _p]),
     "vd_frame_slice": (_i, [_p, _p, _i, _i, _i, _i, _i64, _i, _p]),
     "vd_yolo_decode_filter": (_i, [C.POINTER(HeadDesc), _f, _p, _p, C.c_int32, _p, _p]),
     "vd_nms_ws_bytes": (_i64, [_i, _i, _i]),

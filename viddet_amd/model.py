@@ -7,6 +7,8 @@ Mirrors (paths under /root/reference):
   YOLOOutputV3                       models/definitions/yolo/yolo3.py:43-199
   YOLOV3T (wiring, NMS, losses)      models/definitions/yolo/yolo3.py:959-1302
   _conv2d / _upsample                models/definitions/layers.py:11-20,63-70
+  yolo3_3ddarknet / Darknet3D        models/definitions/yolo/wrappers.py:113-130, darknet/three_darknet.py:19-70,100-226
+                                     (--conv_types 21: the (2+1)-D backbone of frame windows)
 
 The network is a static list of nodes; for every (mode, batch, H, W) a *launch program* — a flat
 list of pre-built C-ABI calls (descriptor structs built once) — is compiled and replayed.  All
@@ -639,7 +641,7 @@ class Parameter:
             return out if shp == self.shape else out[:, :self.shape[1]].contiguous()
         if self.kind == 'stem_weight':
             co = self.shape[0]
-            return self.storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+            return self.storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous().view(self.shape)
         if self.kind in ('gru_weight', 'gru_bias'):
             return self._gru_read(self.storage)
         return self.storage[:int(np.prod(self.shape))].view(self.shape).clone()
@@ -663,7 +665,7 @@ class Parameter:
             return out if shp == self.shape else out[:, :self.shape[1]].contiguous()
         if self.kind == 'stem_weight':
             co = self.shape[0]
-            return self.grad_storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous()
+            return self.grad_storage.view(co, 32)[:, :27].reshape(co, 3, 3, 3).permute(0, 3, 1, 2).contiguous().view(self.shape)
         if self.kind in ('gru_weight', 'gru_bias'):
             return self._gru_read(self.grad_storage)
         return self.grad_storage[:int(np.prod(self.shape))].view(self.shape).clone()
@@ -683,7 +685,7 @@ class Parameter:
         elif self.kind == 'stem_weight':
             co = self.shape[0]
             tmp = torch.zeros(co, 32, device=v.device)
-            tmp[:, :27] = v.permute(0, 2, 3, 1).reshape(co, 27)
+            tmp[:, :27] = v.reshape(co, 3, 3, 3).permute(0, 2, 3, 1).reshape(co, 27)     # ((co,3,1,3,3): the (1,3,3) stem of Darknet3D)
             self.storage.copy_(tmp.view(-1))
         elif self.kind in ('gru_weight', 'gru_bias'):
             n = self.node
@@ -808,6 +810,113 @@ class AddNode:
         self.name, self.a, self.b, self.dst, self.fr = name, a, b, dst, fr
 
 
+class TdwNode:
+    """The temporal half of the backbone's _conv21d cell (three_darknet.py:19-38,41-70): Conv3DRepPad, a depthwise (3,1,1)
+    conv over the K frames of a window with repeat padding (front: frame 0, tail: frame K-2), no bias, and NO BatchNorm or
+    activation behind it (:36).  (B*K, h, w, C) -> (B*K, h, w, C), + `residual` when it closes a DarknetBasicBlockV3
+    (:120-123).  One streaming kernel each way (vd_tdw.hip).  Its weight (C,1,3,1,1) lives in the weight range of the arena
+    behind the conv weights: weight decay, --no_wd, lr_mult, grad_req and the optimiser treat it as a weight."""
+
+    def __init__(self, name, pname, src, dst, C_, div, K, residual=None):
+        self.name, self.pname, self.src, self.dst, self.C, self.div, self.K, self.residual = name, pname, src, dst, C_, div, K, residual
+        self.fr = K
+
+
+def check_conv_types(conv_types, k):
+    """--conv_types: six integers, the stem then the five stages (three_darknet.py:152-199,243-244).  Returns None for the
+    plain 2-D network (all 2), the list for a Darknet3D with a non-empty prefix of 21; everything else is refused by name."""
+    if conv_types is None:
+        return None
+    try:
+        ct = [int(c) for c in conv_types]
+    except (TypeError, ValueError):
+        raise NotImplementedError("conv_types %r: six integers out of 2 and 21 are built" % (conv_types,))
+    if len(ct) != 6:
+        raise NotImplementedError("conv_types needs 6 entries (the stem and the five stages), got %d: %r" % (len(ct), ct))
+    if any(c == 3 for c in ct):
+        raise NotImplementedError("conv_types 3 (3x3x3 convolutions in the backbone, an 81-tap stem) is outside the built "
+                                  "scope; 2 and 21 are built: %r" % (ct,))
+    if any(c not in (2, 21) for c in ct):
+        raise NotImplementedError("conv_types entries must be 2 or 21, got %r" % (ct,))
+    if all(c == 2 for c in ct):
+        return None
+    n21 = ct.index(2) if 2 in ct else 6
+    if n21 == 0 or any(c == 21 for c in ct[n21:]):
+        raise NotImplementedError("conv_types %r: a 21 after a 2 - the trunk is pooled over time once, where the 2-D stages "
+                                  "begin (three_darknet.py:174-176), so the 21 entries must be a prefix" % (ct,))
+    if not (k and int(k) >= 2):
+        raise NotImplementedError("conv_types %r needs a window of K >= 2 frames (k = %r): K = 1 is refused, the tail pad of "
+                                  "the temporal conv is frame K-2 (three_darknet.py:62)" % (ct, k))
+    return ct
+
+
+def _darknet3d_trunk(nodes, T, tensors, conv_types, K):
+    """Darknet3D with return_features=True (three_darknet.py:152-226) on windows of K frames folded into the batch.  The
+    parameter names are YOLOV3TB's `d_model.features.{i}`; the temporal pool occupies an index of `features` (:176), so the
+    indices behind it are the 2-D network's plus one.  Returns the routes a, b, c (single-frame maps, :205-226)."""
+    feat = lambda i: "d_model.features.%d" % i
+
+    def cell21(name, src, dst, cin, cout, stride, div, residual=None, stem=False):
+        """_conv21d(cout, 3, 1, strides) (:19-38): (1,3,3) conv + BN + LeakyReLU on every frame, then the temporal conv"""
+        sp = T(dst + '.s', cout, div * stride, fr=K)
+        n1 = ConvNode(name, src, sp, cin, cout, 3, stride, div, stem=stem, fr=K)
+        n1.conv3d = True
+        nodes.append(n1)
+        out = T(dst, cout, div * stride, fr=K)
+        n1.tdw = TdwNode('tdw.' + dst, name + ".3.conv.weight", sp, out, cout, div * stride, K, residual)
+        nodes.append(n1.tdw)
+        return out
+
+    T('in', 3, 1, fr=K)
+    cur = cell21(feat(0), 'in', 'f0', 3, 32, 1, 1, stem=True)
+    idx, div, fr = 1, 1, K
+    routes = []
+
+    def pool_trunk():
+        nxt = T(cur + '.pool', tensors[cur][0], div)
+        pn = PoolNode('pool.trunk', cur, nxt, K, 'max')
+        pn.feature_index = idx
+        nodes.append(pn)
+        if routes and routes[-1] == cur:            # conv_swap == 4 (:211-214): the pool is the last feature of route a
+            routes[-1] = nxt
+        return nxt
+
+    for gi, (nlayer, ch) in enumerate(zip([1, 2, 8, 8, 4], [64, 128, 256, 512, 1024])):
+        t21 = conv_types[gi + 1] == 21
+        if not t21 and fr > 1:                                                       # :174-176
+            cur, fr, idx = pool_trunk(), 1, idx + 1
+        if t21:
+            cur = cell21(feat(idx), cur, 'f%d' % idx, ch // 2, ch, 2, div)           # :187-189, strides (1,2,2)
+        else:
+            nxt = T('f%d' % idx, ch, div * 2)
+            nodes.append(ConvNode(feat(idx), cur, nxt, ch // 2, ch, 3, 2, div))
+            cur = nxt
+        div, idx = div * 2, idx + 1
+        for _ in range(nlayer):                                                      # DarknetBasicBlockV3 (:100-123)
+            mid = T('f%d.m' % idx, ch // 2, div, fr=fr)
+            n0 = ConvNode(feat(idx) + ".body.0", cur, mid, ch, ch // 2, 1, 1, div, fr=fr)
+            n0.conv3d = t21                          # _conv3d 1x1x1: per-frame arithmetic, 5-D weight
+            nodes.append(n0)
+            if t21:
+                cur = cell21(feat(idx) + ".body.1", mid, 'f%d' % idx, ch // 2, ch, 1, div, residual=cur)
+            else:
+                nxt = T('f%d' % idx, ch, div)
+                nodes.append(ConvNode(feat(idx) + ".body.1", mid, nxt, ch // 2, ch, 3, 1, div, residual=cur))
+                cur = nxt
+            idx += 1
+        if gi >= 2:
+            routes.append(cur)
+    if fr > 1:                                                                       # :197-199 the whole trunk was 2+1-D
+        cur = pool_trunk()
+        routes[-1] = cur
+    for i, r in enumerate(routes):                   # :219,224-225 a route that left the trunk with K frames: its own max
+        if tensors[r][3] > 1:
+            pr = T('route%d.pool' % i, tensors[r][0], tensors[r][1])
+            nodes.append(PoolNode('pool.route%d' % i, r, pr, K, 'max'))
+            routes[i] = pr
+    return routes
+
+
 def _feature_name(f):
     if f < 15:
         return "stages.0.%d" % f
@@ -820,7 +929,7 @@ ROUTE_TENSORS = (('f14', 256, 8), ('f23', 512, 16), ('f28', 1024, 32))   # featu
 
 
 def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_type='2', noback=False,
-                temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0, rnn_pos=None):
+                temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0, rnn_pos=None, conv_types=None, frames=1):
     """Node list of YOLOV3T over Darknet-53 (wrappers.py:54-58,101-103; three_darknet.py:252-258;
     yolo3.py:1003-1054 wiring, :1095-1177 forward).  k>1: the backbone is TimeDistributed (K frames folded
     into the batch, layers.py:241-250); 'early' joins pool each stage output over K, 'late' joins keep K frames
@@ -869,7 +978,12 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
         return nm
 
     routes = []
-    if noback:
+    d3 = conv_types is not None
+    if d3:
+        # yolo3_3ddarknet (wrappers.py:113-130): Darknet3D on windows of `frames` frames, then YOLOV3TB with k = 1
+        assert K == 1 and not noback and not temporal_out and not temporal_side
+        routes = _darknet3d_trunk(nodes, T, tensors, conv_types, frames)
+    elif noback:
         # YOLOV3_noback (yolo3.py:1730-1840): the three backbone feature maps are the inputs (net(x1, x2, x3)); only
         # transitions / yolo_blocks / yolo_outputs exist, under the same structural names as in the full network
         assert K == 1, "YOLOV3_noback has no temporal window"
@@ -895,7 +1009,7 @@ def build_graph(num_class, k=1, k_join_type=None, k_join_pos=None, block_conv_ty
         nodes.append(n2)
         return out
 
-    for gi, (nlayer, ch) in enumerate(zip([] if noback else [1, 2, 8, 8, 4], [64, 128, 256, 512, 1024])):
+    for gi, (nlayer, ch) in enumerate(zip([] if (noback or d3) else [1, 2, 8, 8, 4], [64, 128, 256, 512, 1024])):
         if temporal_side and gi in (3, 4):
             i = gi - 2                                                               # side branch 1 / 2
             if gi == 3:
@@ -1033,8 +1147,16 @@ class YOLOV3(object):
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, ignore_iou_thresh=0.7,
                  device="cuda", syncbn_scope=None, process_group=None, k=1, k_join_type=None, k_join_pos=None,
                  block_conv_type='2', noback=False, temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0,
-                 rnn_pos=None):
+                 rnn_pos=None, conv_types=None):
         self._classes = list(classes)
+        # Darknet3D backbone on windows of k frames (yolo3_3ddarknet, wrappers.py:113-130): the neck and heads are the plain
+        # single-frame ones (YOLOV3TB with k = 1), so nothing that joins or mixes frames behind the backbone combines with it
+        self._conv_types = check_conv_types(conv_types, k)
+        if self._conv_types is not None and (k_join_type or k_join_pos or block_conv_type != '2' or noback or temporal_out or
+                                             temporal_side or corr_pos is not None or rnn_pos is not None):
+            raise NotImplementedError("conv_types %r builds yolo3_3ddarknet, whose neck is the single-frame one: k_join_type / "
+                                      "k_join_pos, block_conv_type, corr_pos, rnn_pos, temporal and the no-backbone network do "
+                                      "not combine with it" % (self._conv_types,))
         # bidirectional ConvGRU (RNN, layers.py:267-306).  What the factory refuses is refused here too: nothing is dropped
         if rnn_pos is not None:
             if rnn_pos not in ('late', 'out'):
@@ -1092,14 +1214,16 @@ class YOLOV3(object):
     # ------------------------------------------------------------------ construction
     def _build(self, num_class):
         self.num_class = num_class
-        self.nodes, self.tensors, self.head_names = build_graph(num_class, self._k, self._k_join_type,
+        self.nodes, self.tensors, self.head_names = build_graph(num_class, 1 if self._conv_types else self._k, self._k_join_type,
                                                                 self._k_join_pos, self._block_conv_type,
                                                                 noback=self.noback, temporal_out=self.temporal_out,
                                                                 temporal_side=self.temporal_side, corr_pos=self._corr_pos,
-                                                                corr_d=self._corr_d, rnn_pos=self._rnn_pos)
+                                                                corr_d=self._corr_d, rnn_pos=self._rnn_pos,
+                                                                conv_types=self._conv_types, frames=self._k)
         self._head_frames = self._k if self.temporal_out else 1
         self.input_tensors = [nm for nm, _, _ in ROUTE_TENSORS] if self.noback else ['in']
         self.gru_nodes = [n for n in self.nodes if isinstance(n, GruNode)]
+        self.tdw_nodes = [n for n in self.nodes if isinstance(n, TdwNode)]
         # (a GruNode's four convolutions take their place in the arena order where the node stands)
         self.conv_nodes = [m for n in self.nodes for m in ([n] if isinstance(n, ConvNode) else
                                                            [cn for _, i2h, h2h in n.cells for cn in (i2h, h2h)] if isinstance(n, GruNode) else [])]
@@ -1123,6 +1247,10 @@ class YOLOV3(object):
         for n in self.conv_nodes:
             n.w_off = off
             n.w_numel = n.co_pad * n.T * n.ci_eff
+            off += round_up(n.w_numel, 64)
+        self.n_wconv = off                           # end of the conv weights; the temporal depthwise weights follow them
+        for n in self.tdw_nodes:
+            n.w_off, n.w_numel = off, 3 * n.C
             off += round_up(n.w_numel, 64)
         self.n_weight = off
         for n in self.conv_nodes:
@@ -1209,6 +1337,11 @@ class YOLOV3(object):
                 reg(n.name + ".1.beta", (n.cout,), 'vector', n, n.beta, n.gbeta, off=n.beta_off)
                 reg(n.name + ".1.running_mean", (n.cout,), 'vector', n, n.rmean, None, trainable=False)
                 reg(n.name + ".1.running_var", (n.cout,), 'vector', n, n.rvar, None, trainable=False)
+                t = getattr(n, 'tdw', None)
+                if t is not None:                    # Conv3DRepPad registers its Conv3D as `.conv` (three_darknet.py:55)
+                    t.w = self.weights[t.w_off:t.w_off + t.w_numel]
+                    t.gw = self.grads[t.w_off:t.w_off + t.w_numel]
+                    reg(t.pname, (t.C, 1, 3, 1, 1), 'vector', t, t.w, t.gw, off=t.w_off)
         self._params = P
         self._opt_ranges = None
 
@@ -1495,7 +1628,8 @@ class YOLOV3(object):
         fl, ra = flags.cpu().numpy(), ratios.cpu().numpy()
         new = {}
         for i, n in enumerate(bn):
-            for k, name in ((0, n.dst), (1, 'dz:' + n.name)):
+            # (the operand tensor behind a _conv21d cell is its temporal conv's output: per-channel taps, same channel scales)
+            for k, name in ((0, n.tdw.dst if getattr(n, 'tdw', None) is not None else n.dst), (1, 'dz:' + n.name)):
                 if fl[2 * i + k] and name not in self._range_exact:
                     new[name] = float(ra[2 * i + k])
         if new:
@@ -1604,6 +1738,14 @@ class YOLOV3(object):
                  hw * g.chp, bufs['amax:' + g.dst].data_ptr(),
                  meta=dict(kind='gru_avg', node=g.name, flops=2.0 * B * K * hw * g.chp, bytes=12.0 * B * K * hw * g.chp))
 
+    def _add_tdw_fwd(self, prog, n, bufs, B, H, W):
+        """y = tdw(x, w) [+ residual] with the max-abs of y for the convs that read it (the same in inference and training)"""
+        hw = (H // n.div) * (W // n.div)
+        prog.add('vd_tdw_fwd', bufs[n.src].data_ptr(), n.w.data_ptr(), bufs[n.residual].data_ptr() if n.residual else None,
+                 bufs[n.dst].data_ptr(), B, n.K, hw, n.C, bufs['amax:' + n.dst].data_ptr(),
+                 meta=dict(kind='tdw_fwd', node=n.name, flops=6.0 * B * n.K * hw * n.C,
+                           bytes=4.0 * B * n.K * hw * n.C * (3 if n.residual else 2)))
+
     def _add_amax_reset(self, prog, bufs):
         prog.add('vd_fill', bufs['amax'].data_ptr(), 0.0, bufs['amax'].numel())
 
@@ -1669,6 +1811,9 @@ class YOLOV3(object):
             if isinstance(n, GruNode):
                 self._add_gru_fwd(prog, n, bufs, B, H, W, False)
                 continue
+            if isinstance(n, TdwNode):
+                self._add_tdw_fwd(prog, n, bufs, B, H, W)
+                continue
             if n.stem:
                 self._add_stem(prog, n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, leaky=True)
                 prog.add('vd_amax', bufs[n.dst].data_ptr(), bufs[n.dst].numel(), am(n.dst))
@@ -1731,6 +1876,9 @@ class YOLOV3(object):
         """'fp32' (reference precision) or 'bf16' (BASELINE configs[1]): bf16 storage + bf16 MFMA with fp32
         accumulation and fp32 epilogue for inference; the prediction heads stay fp32."""
         assert precision in ('fp32', 'bf16')
+        if precision == 'bf16' and getattr(self, '_conv_types', None):
+            raise NotImplementedError("bf16 inference is not built for conv_types networks: the temporal-conv kernels "
+                                      "(vd_tdw.hip) are fp32 only")
         if precision == 'bf16' and self._rnn_pos:
             raise NotImplementedError("bf16 inference is not built for rnn_pos networks: the ConvGRU gate kernels (vd_gru.hip) "
                                       "and the recurrent state are fp32 only")
@@ -1977,7 +2125,7 @@ class YOLOV3(object):
         """extract_base_features.py:127-130: f1 = features[:15](x), f2 = features[15:24](f1), f3 = features[24:](f2) in
         inference mode (BatchNorm on running statistics) -> three NCHW fp32 tensors (B,256,H/8,W/8), (B,512,H/16,W/16),
         (B,1024,H/32,W/32), the inputs of the no-backbone network."""
-        if self.noback or self._k > 1:
+        if self.noback or self._k > 1 or self._conv_types:
             raise NotImplementedError("extract_features is the per-frame Darknet-53 trunk of the full k=1 network")
         B, H, W = self._in_shape(x)
         key = ('features', B, H, W)
@@ -2047,6 +2195,8 @@ class YOLOV3(object):
                 ws_bytes = max(ws_bytes, ops.wgrad_ws_bytes(B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.k, n.stride,
                                                             n.pad, n.kd, n.pad_d))
             ws_bytes = max(ws_bytes, ops.bn_stats_ws_bytes(B * n.fr * Ho * Wo, _bf16_pitch(n.co_pad) if bf16 else n.co_pad))
+        for n in self.tdw_nodes:
+            ws_bytes = max(ws_bytes, int(lib.vd_tdw_bwd_ws_bytes(B, n.K, (H // n.div) * (W // n.div), n.C)))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
@@ -2159,6 +2309,9 @@ class YOLOV3(object):
             if isinstance(n, GruNode):
                 self._add_gru_fwd(seg, n, bufs, B, H, W, True, side, ev_record, ev_wait)
                 continue
+            if isinstance(n, TdwNode):
+                self._add_tdw_fwd(seg, n, bufs, B, H, W)
+                continue
             Ho, Wo = H // n.div_out, W // n.div_out
             tvalid = getattr(n, 'tvalid', False)
             M = B * (n.fr - 2 if tvalid else n.fr) * Ho * Wo
@@ -2244,7 +2397,7 @@ class YOLOV3(object):
         dz_free = [None, None]             # event after which dz_bufs[i] may be overwritten
         n_dz = [0]
         last_side = [None]
-        bucket_hi, bucket_acc = [self.n_weight], [0]
+        bucket_hi, bucket_acc = [self.n_wconv], [0]     # (the temporal depthwise weights behind n_wconv: allreduce_grads)
         written = set(self.head_names)     # gradients already produced (the loss kernel wrote d:head*)
         dgrad_packs = []                   # (node, plan, packed weight buffer) re-packed when weights change
 
@@ -2258,7 +2411,7 @@ class YOLOV3(object):
         producers = {m.dst: m for m in self.conv_nodes if m.bn}
         consumers = {}
         for m in self.nodes:
-            srcs = [m.src, m.residual] if isinstance(m, ConvNode) else ([m.up, m.route] if isinstance(m, UpcatNode) else
+            srcs = [m.src, m.residual] if isinstance(m, (ConvNode, TdwNode)) else ([m.up, m.route] if isinstance(m, UpcatNode) else
                                                                           ([m.a, m.b] if isinstance(m, AddNode) else [m.src]))
             for t in srcs:
                 if t:
@@ -2276,6 +2429,8 @@ class YOLOV3(object):
                 tgrad[m.dst] = tgrad[m.up] or tgrad[m.route]
             elif isinstance(m, AddNode):
                 tgrad[m.dst] = tgrad[m.a] or tgrad[m.b]
+            elif isinstance(m, TdwNode):
+                tgrad[m.dst] = self._params[m.pname].grad_req != 'null' or tgrad[m.src] or bool(m.residual and tgrad[m.residual])
             elif isinstance(m, GruNode):
                 tgrad[m.dst] = tgrad[m.src] or any(any(self._node_trainable(cn)) for _, a_, b_ in m.cells for cn in (a_, b_))
             else:
@@ -2423,6 +2578,38 @@ class YOLOV3(object):
                     gru_wgrad(i2h, bufs[g.src], bufs[i2h.dst], B * K, self._amax_or_none(bufs, g.src))
 
         for n in reversed(self.nodes):
+            if isinstance(n, TdwNode):
+                # backward of the temporal conv, in front of its spatial cell's BatchNorm backward: the skip gradient of a
+                # block is dy itself (alias, as for a 2-D block); ONE launch then writes dx = d:src and the weight
+                # gradient's partial rows, a second folds them (vd_tdw.hip).  dx is left out when nothing upstream needs a
+                # gradient, dw under grad_req 'null'.  It runs on the main stream: its dx is on the critical path and the
+                # weight gradient falls out of the same read of dy.
+                if not tgrad[n.dst]:
+                    continue
+                assert n.dst in written, n.name
+                materialize(n.dst)
+                dy = bufs['d:' + n.dst]
+                if n.residual and tgrad[n.residual]:
+                    dres, acc = grad_into(n.residual)
+                    if acc:
+                        seg.add('vd_add', dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
+                    else:
+                        alias[n.residual] = dy
+                        if not self.alias_skip_grad:
+                            materialize(n.residual)
+                t_train = self._params[n.pname].grad_req != 'null'
+                dxp = None
+                if tgrad[n.src]:
+                    dsrc, acc = grad_into(n.src)
+                    assert not acc, n.name           # the temporal conv is the only reader of its spatial cell
+                    dxp = dsrc.data_ptr()
+                if dxp is not None or t_train:
+                    hw = (H // n.div) * (W // n.div)
+                    seg.add('vd_tdw_bwd', dy.data_ptr(), bufs[n.src].data_ptr(), n.w.data_ptr(), dxp,
+                            n.gw.data_ptr() if t_train else None, B, n.K, hw, n.C, ws.data_ptr(), ws_bytes,
+                            meta=dict(kind='tdw_bwd', node=n.name, flops=(12.0 if t_train else 6.0) * B * n.K * hw * n.C,
+                                      bytes=4.0 * B * n.K * hw * n.C * (1 + (dxp is not None) + t_train)))
+                continue
             if isinstance(n, GruNode):
                 if tgrad[n.dst]:
                     assert n.dst in written, n.name
@@ -2756,6 +2943,9 @@ class YOLOV3(object):
         bf16 tolerance (tests/test_bf16_train_gpu.py, test_model_gpu.py)."""
         if storage not in ('fp32', 'bf16'):
             raise ValueError("storage must be 'fp32' or 'bf16'")
+        if storage == 'bf16' and getattr(self, '_conv_types', None):
+            raise NotImplementedError("bf16-storage training is not built for conv_types networks: the temporal-conv kernels "
+                                      "(vd_tdw.hip) are fp32 only")
         if storage == 'bf16' and getattr(self, '_rnn_pos', None):
             raise NotImplementedError("bf16-storage training is not built for rnn_pos networks: the ConvGRU gate kernels "
                                       "(vd_gru.hip) and the recurrent state are fp32 only")
@@ -3017,7 +3207,7 @@ class YOLOV3(object):
             self._reduced_from = self.n_params
             if lo > wt_lo:                               # anything before the first bucket (not expected)
                 torch.distributed.all_reduce(self.grads[wt_lo:lo], group=self.process_group)
-            torch.distributed.all_reduce(self.grads[self.n_weight:], group=self.process_group)
+            torch.distributed.all_reduce(self.grads[self.n_wconv:], group=self.process_group)
         else:
             torch.distributed.all_reduce(self.grads[wt_lo:], group=self.process_group)
 
@@ -3040,6 +3230,37 @@ class YOLOV3(object):
     def save_parameters(self, path):
         from .params_io import save_params
         save_params(path, self.state_arrays())
+
+    def inflate_from_2d(self, src):
+        """get_darknet's transfer of 2-D weights (three_darknet.py:289-318), extended to the whole detector: `src` is a
+        k = 1 yolo3_darknet53 network or its {name: array} dict.  Spatial and 1x1x1 weights are the 2-D weights with a unit
+        time axis (the reference divides by shape[-3] = 1), BatchNorm parameters and running statistics are copied, every
+        temporal weight becomes 1/3 in its three taps, the neck and heads are copied by name.  A window of K equal frames
+        then reproduces the 2-D network (the three taps see the same frame whatever the padding repeats)."""
+        if not self._conv_types:
+            raise NotImplementedError("inflate_from_2d is the weight transfer of a conv_types network (yolo3_3ddarknet)")
+        if isinstance(src, YOLOV3):
+            if src._k != 1 or src.noback or getattr(src, '_conv_types', None):
+                raise ValueError("inflate_from_2d takes the plain k = 1 yolo3_darknet53 network")
+            src = {k_: p.data() for k_, p in src.collect_params().items()}
+        pool_at = [n.feature_index for n in self.nodes if isinstance(n, PoolNode) and n.name == 'pool.trunk'][0]
+        to2d = {}
+        for f in range(29):                  # features index of the 2-D network -> this network's (the pool takes one)
+            to2d["d_model.features.%d." % (f + (1 if f >= pool_at else 0))] = _feature_name(f) + "."
+        for name, p in self._params.items():
+            if name.endswith(".3.conv.weight"):
+                p.set_data(torch.full(p.shape, 1.0 / p.shape[2]))
+                continue
+            key = name
+            if name.startswith("d_model."):
+                pre = name[:name.index(".", len("d_model.features.")) + 1]
+                key = to2d[pre] + name[len(pre):]
+            if key not in src:
+                raise KeyError("inflate_from_2d: %s (for %s) is missing in the 2-D network" % (key, name))
+            v = torch.as_tensor(np.asarray(src[key].detach().cpu() if torch.is_tensor(src[key]) else src[key]), dtype=torch.float32)
+            if len(p.shape) == 5 and v.dim() == 4:
+                v = v.unsqueeze(2)
+            p.set_data(v)
 
     def load_parameters(self, path, allow_missing=False, ignore_extra=False):
         from .params_io import load_params
@@ -3132,6 +3353,32 @@ def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs
                  block_conv_type=block_conv_type, rnn_pos=rnn_pos, **corr, **kwargs)
     if freeze_base:                          # wrappers.py:55-57: every Darknet parameter leaves the gradient / update
         for name, p in net.collect_params('stages.*').items():
+            p.grad_req = 'null'
+    return net
+
+
+def yolo3_3ddarknet(classes, pretrained_base=False, norm_layer=None, norm_kwargs=None, freeze_base=False,
+                    conv_types=(2, 2, 2, 2, 2, 2), k=None, **kwargs):
+    """wrappers.py:113-130 -> YOLOV3TB (yolo3.py:1305-1439, k = 1) over Darknet3D (three_darknet.py:126-226): a Darknet-53
+    whose stem and first stages are (2+1)-D (`conv_types`: the stem, then the five stages; 21 = a per-frame (1,3,3) conv + BN +
+    LeakyReLU followed by a depthwise (3,1,1) conv with repeat padding), run on windows of `k` frames and max-pooled over time
+    where the 2-D stages begin.  conv_types all 2 is yolo3_darknet53.  norm_layer='syncbn' reaches the stem and the five
+    stride-2 convs only: the blocks are built with plain BatchNorm (three_darknet.py:193), which is scope 'reference'.
+    `net.inflate_from_2d(src)` starts it from a trained 2-D detector (get_darknet, three_darknet.py:289-318)."""
+    ct = check_conv_types(conv_types, 2 if k is None else k)       # (all 2: no window is needed)
+    if ct is None:
+        return yolo3_darknet53(classes, pretrained_base=pretrained_base, norm_layer=norm_layer, norm_kwargs=norm_kwargs,
+                               freeze_base=freeze_base, k=k, **kwargs)
+    check_conv_types(ct, k)
+    scope = None
+    if norm_layer == 'syncbn':
+        scope = (norm_kwargs or {}).get('scope', 'reference')
+        if scope != 'reference':
+            raise NotImplementedError("conv_types %r with syncbn scope %r: the blocks of Darknet3D are built with plain "
+                                      "BatchNorm (three_darknet.py:193); scope 'reference' only" % (ct, scope))
+    net = YOLOV3(classes, syncbn_scope=scope, k=int(k), conv_types=ct, **kwargs)
+    if freeze_base:                          # wrappers.py:118-120: every Darknet3D parameter, temporal weights included
+        for name, p in net.collect_params('d_model.*').items():
             p.grad_req = 'null'
     return net
 

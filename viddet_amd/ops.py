@@ -437,6 +437,21 @@ def temporal_pool_bwd(dy, argmax, dx, B, K, inner, type_):
     check(_lib().vd_temporal_pool_bwd(ptr(dy), ptr(argmax), ptr(dx), B, K, inner, type_, _s()), "vd_temporal_pool_bwd")
 
 
+def tdw_fwd(x, w, res, y, B, K, HW, C_, amax_out=None):
+    """y = depthwise (3,1,1) conv of x over the K frames of each window, repeat padding (tail pad = frame K-2) [+ res]"""
+    check(_lib().vd_tdw_fwd(ptr(x), ptr(w), ptr(res), ptr(y), B, K, HW, C_, ptr(amax_out), _s()), "vd_tdw_fwd")
+
+
+def tdw_bwd_ws_bytes(B, K, HW, C_):
+    return int(_lib().vd_tdw_bwd_ws_bytes(B, K, HW, C_))
+
+
+def tdw_bwd(dy, x, w, dx, dw, B, K, HW, C_, ws=None):
+    """dx (None: skipped) and dw [C][3] (None: skipped) of tdw_fwd; ws = the partial-sum rows of the weight gradient"""
+    check(_lib().vd_tdw_bwd(ptr(dy), ptr(x), ptr(w), ptr(dx), ptr(dw), B, K, HW, C_, ptr(ws),
+                            0 if ws is None else ws.numel() * ws.element_size(), _s()), "vd_tdw_bwd")
+
+
 def sgd_momentum(w, g, m, lr, momentum, wd, rescale):
     check(_lib().vd_sgd_momentum(ptr(w), ptr(g), ptr(m), w.numel(), lr, momentum, wd, rescale, _s()), "vd_sgd_momentum")
 

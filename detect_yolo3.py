@@ -8,7 +8,9 @@ reference's `sid=` keyword bug at :693 is not reproduced), main :792-939 (net bu
 `--window K,1 --conv_types 21,...` detects with yolo3_3ddarknet (:872-882), the (2+1)-D Darknet backbone of frame windows.
 The network underneath is viddet_amd.model.YOLOV3 (hand-written HIP kernels).  Frames shard across ranks with
 no collective on the data path (inference = replicas only); the per-image box lists are gathered to rank 0, which writes
-the prediction files and evaluates.  Visualisation / worst-video / COCO+VID metrics are out of scope.
+the prediction files and evaluates.  `--model_agnostic` (:797-798, :861-862, :893, :922-925) detects class-agnostically: one
+candidate per anchor scored by its objectness, plain NMS over the image, predictions under pred_ag, results named *_ag.
+Visualisation / worst-video / COCO+VID metrics are out of scope.
 """
 import argparse
 import os
@@ -102,6 +104,50 @@ def detect(net, dataset, loader, max_do=-1):
     return boxes
 
 
+def pred_dir(save_dir, save_prefix, agnostic=False):
+    """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag"""
+    return os.path.join(save_dir, save_prefix, "pred_ag" if agnostic else "pred")
+
+
+def result_name(metric_name, model_agnostic=False):
+    """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798, so `_met` is never appended here)"""
+    return metric_name + "_ag" if model_agnostic else metric_name
+
+
+def check_flags(FLAGS):
+    """What the parsed flags ask for that is not built is refused here, before anything touches the GPU; returns the checked
+    conv_types (None: the plain 2-D backbone)."""
+    # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
+    # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
+    for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
+                 "worst_video_path", "trained_on"):
+        v = getattr(FLAGS, flag)
+        if v and not (isinstance(v, str) and not v.strip()):
+            raise NotImplementedError("--%s is outside the yolo3_darknet53 hot path" % flag)
+    if FLAGS.model_agnostic:
+        FLAGS.metric_agnostic = True                      # detect_yolo3.py:797-798
+    elif FLAGS.metric_agnostic:
+        raise NotImplementedError("--metric_agnostic without --model_agnostic only acts inside VIDDetectionMetric "
+                                  "(detect_yolo3.py:189-190), which is not built: the voc metric takes no agnostic argument")
+    # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
+    ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
+    if ct is not None:
+        for flag, on in (("k_join_type", FLAGS.k_join_type), ("k_join_pos", FLAGS.k_join_pos), ("rnn_pos", FLAGS.rnn_pos),
+                         ("corr_pos", FLAGS.corr_pos), ("precision", FLAGS.precision == "bf16"),
+                         ("block_conv_type", FLAGS.block_conv_type != "2")):
+            if on:
+                raise NotImplementedError("--%s does not combine with --conv_types %s: yolo3_3ddarknet is not passed it (its "
+                                          "neck is the single-frame one; the temporal-conv kernels are fp32)"
+                                          % (flag, ",".join(str(c) for c in ct)))
+        if FLAGS.model_agnostic:
+            raise NotImplementedError("--model_agnostic does not combine with --conv_types %s: yolo3_3ddarknet is built "
+                                      "without the flag (detect_yolo3.py:872-882)" % ",".join(str(c) for c in ct))
+    if FLAGS.model_agnostic and FLAGS.rnn_pos == "out":
+        raise NotImplementedError("--model_agnostic with --rnn_pos out: the RNN output block is a tail of its own that is not "
+                                  "built agnostic")
+    return ct
+
+
 def save_predictions(save_dir, dataset, boxes, overwrite=True, max_do=-1):
     """detect_yolo3.py:275-330: one text file per image, lines `path,id,score,x1,y1,x2,y2`."""
     os.makedirs(save_dir, exist_ok=True)
@@ -152,23 +198,7 @@ def main(argv=None):
     FLAGS.window = [int(s) for s in FLAGS.window]
     if FLAGS.window[0] == 1:
         FLAGS.k_join_type = FLAGS.k_join_pos = None
-    # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
-    # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
-    for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "model_agnostic",
-                 "metric_agnostic", "offset", "per_frame_metric", "worst_video_path", "trained_on"):
-        v = getattr(FLAGS, flag)
-        if v and not (isinstance(v, str) and not v.strip()):
-            raise NotImplementedError("--%s is outside the yolo3_darknet53 hot path" % flag)
-    # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
-    ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
-    if ct is not None:
-        for flag, on in (("k_join_type", FLAGS.k_join_type), ("k_join_pos", FLAGS.k_join_pos), ("rnn_pos", FLAGS.rnn_pos),
-                         ("corr_pos", FLAGS.corr_pos), ("precision", FLAGS.precision == "bf16"),
-                         ("block_conv_type", FLAGS.block_conv_type != "2")):
-            if on:
-                raise NotImplementedError("--%s does not combine with --conv_types %s: yolo3_3ddarknet is not passed it (its "
-                                          "neck is the single-frame one; the temporal-conv kernels are fp32)"
-                                          % (flag, ",".join(str(c) for c in ct)))
+    ct = check_flags(FLAGS)
     rank, world = vdist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("detect_yolo3.py needs an MI355X: the HIP path has no CPU fallback")
@@ -188,13 +218,14 @@ def main(argv=None):
     else:
         net = yolo3_darknet53(dataset.classes, pretrained_base=False, k=FLAGS.window[0], k_join_type=FLAGS.k_join_type,
                               k_join_pos=FLAGS.k_join_pos, block_conv_type=FLAGS.block_conv_type,
-                              corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d, rnn_pos=FLAGS.rnn_pos or None)
+                              corr_pos=FLAGS.corr_pos or None, corr_d=FLAGS.corr_d, rnn_pos=FLAGS.rnn_pos or None,
+                              agnostic=FLAGS.model_agnostic)
     if FLAGS.random_init:
         net.initialize(init="he", obj_bias=-2.0)
     else:
         net.load_parameters(FLAGS.model_path)
     net.set_precision(FLAGS.precision)
-    save_dir = os.path.join(FLAGS.save_dir, FLAGS.save_prefix, "pred")
+    save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic)
     boxes = detect(net, dataset, loader, FLAGS.max_do)
     if world > 1:
         # frames are sharded over the ranks (replicas, no collective on the data path); the per-image box lists (host
@@ -214,6 +245,12 @@ def main(argv=None):
         (names, values), = evaluate([VOCMApMetric(iou_thresh=0.5, class_names=dataset.classes)], dataset, preds,
                                     FLAGS.data_shape)
         print("{}={:.4f}".format(names[-1], values[-1]))
+        if FLAGS.model_agnostic:
+            # detect_yolo3.py:920-931: the per-class and the mean AP, `name value` per line, in <metric>_ag.txt beside pred_ag.
+            # The metric is handed the rows as they are (ids all 0): the reference's voc / coco metrics take no agnostic argument
+            with open(os.path.join(FLAGS.save_dir, FLAGS.save_prefix, result_name("voc", True) + ".txt"), "w") as f:
+                for k, v in zip(names, values):
+                    f.write("{} {}\n".format(k, v))
         return names, values
     return None
 

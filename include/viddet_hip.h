@@ -480,6 +480,20 @@ int vd_nms_topk(const vd_head_desc* h, const float* cand_score, const int32_t* c
                 int32_t cap, const int32_t* counts, float nms_thresh, int topk, int post_nms,
                 float* out_ids, float* out_scores, float* out_boxes, int32_t* out_rows,
                 void* ws, int64_t ws_bytes, void* stream);
+/* Class-agnostic tail (YOLOOutputV3(agnostic=True), yolo3.py:184-188, + the same box_nms / slice_axis): ONE candidate per
+ * (pixel, anchor), id 0, score = sigmoid(objectness) - the class channels are never read.  row indexes the (B, P, 6) tensor
+ * the reference concatenates: [head][pixel][anchor], P = 3 * sum g[s]^2.  cap >= P cannot overflow (counts / the overflow
+ * flags are kept for symmetry with the per-class pair).  head_bf16 != 0: h->head[s] point to bf16 tensors of the same
+ * geometry (ldh counted in elements).  With a single id the NMS is plain NMS over the image: the set and the sweep order are
+ * those of "sort by (score desc, row asc), take topk, greedy sweep"; out_ids are 0 for kept rows, -1 fill as vd_nms_topk.
+ * No floating-point atomics; bit-identical from run to run. */
+int vd_yolo_decode_filter_agnostic(const vd_head_desc* h, int head_bf16, float valid_thresh,
+                                   float* cand_score, int32_t* cand_row, int32_t cap, int32_t* counts,
+                                   void* stream);
+int vd_nms_agnostic(const vd_head_desc* h, int head_bf16, const float* cand_score, const int32_t* cand_row,
+                    int32_t cap, const int32_t* counts, float nms_thresh, int topk, int post_nms,
+                    float* out_ids, float* out_scores, float* out_boxes, int32_t* out_rows,
+                    void* ws, int64_t ws_bytes, void* stream);
 
 /* Training (yolo3.py:1140-1187 + yolo_target.py:173-281 + gluoncv YOLOV3Loss):
  * fused decode -> dynamic ignore mask (IoU>thr vs gt) -> target merge -> 4 losses and their

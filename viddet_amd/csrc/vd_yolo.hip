@@ -282,9 +282,86 @@ __global__ __launch_bounds__(256) void k_decode_filter_obj(const vd_head_desc h,
     }
 }
 
+// Class-agnostic form (YOLOOutputV3(agnostic=True), yolo3.py:184-188): ONE candidate per (pixel, anchor), score =
+// sigmoid(objectness), row = its index in the (B, P, 6) tensor the reference concatenates ([head][pixel][anchor]: the entry
+// index itself).  The class channels are never read.  A lane owns one entry and reads its ONE objectness logit; the box
+// channels are read where the per-class path reads them - in the NMS, for the <= topk survivors of an image - so a
+// candidate stays the 8-byte (score, row) pair and no box is decoded for an anchor that the top-k drops.
+// Traffic: 4 useful bytes per anchor (the issue's 20 would carry the box too).  What L2 fetches is whole 128-byte lines of
+// a gather whose stride is (5 + C) * sizeof(HT): one line per anchor as soon as that stride reaches 128 bytes (fp32 heads,
+// C >= 27: 128 B per anchor = 3/8 of the head at C = 80, 11 % at C = 285); below it neighbouring anchors share lines and the
+// whole head is read once (32 B per anchor at C = 3).  The box channels sit in the objectness logit's line (or the one
+// before it), so reading them here would add no line - only the 16 bytes per candidate to write and read back.
+// A workgroup owns AGN_EPT x 256 consecutive entries, requests its AGN_EPT logits together, collects what passes in LDS (the
+// buffer holds every entry it owns: no spill path) and publishes with ONE global atomic: 23 per image at 608 x 608.  The
+// append order is arbitrary, as in the kernels above; the NMS keys by (score, row).
+constexpr int AGN_EPT = 4;
+
+template <typename HT>
+__global__ __launch_bounds__(256) void k_decode_filter_agn(const vd_head_desc h, float thresh, float* __restrict__ cand_score,
+                                                           int32_t* __restrict__ cand_row, int cap, int32_t* __restrict__ counts) {
+    __shared__ float lscore[AGN_EPT * 256];
+    __shared__ int32_t lrow[AGN_EPT * 256];
+    __shared__ int lcount, gbase;
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.y;
+    const int npred = 5 + h.C;
+    const int R0 = h.g[0] * h.g[0], R1 = h.g[1] * h.g[1], R2 = h.g[2] * h.g[2];
+    const int E = 3 * (R0 + R1 + R2);                 // (pixel, anchor) entries of one image (< 2^31: checked on the host)
+    if (threadIdx.x == 0) lcount = 0;
+    __syncthreads();
+    float logit[AGN_EPT];
+#pragma unroll
+    for (int j = 0; j < AGN_EPT; ++j) {
+        const int64_t e = ((int64_t)blockIdx.x * AGN_EPT + j) * 256 + threadIdx.x;
+        logit[j] = 0.f;
+        if (e < E) {
+            const int r = (int)(e / 3), a = (int)(e - 3 * (int64_t)r);
+            int s, pix;
+            if (r < R0) { s = 0; pix = r; }
+            else if (r < R0 + R1) { s = 1; pix = r - R0; }
+            else { s = 2; pix = r - R0 - R1; }
+            const int g = h.g[s];
+            logit[j] = (float)(reinterpret_cast<const HT*>(h.head[s]) + ((int64_t)b * g * g + pix) * h.ldh + a * npred)[4];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < AGN_EPT; ++j) {
+        const int64_t e = ((int64_t)blockIdx.x * AGN_EPT + j) * 256 + threadIdx.x;
+        const float obj = vd_sigmoid(logit[j]);
+        const bool pass = e < E && obj > thresh;
+        const unsigned long long m = __ballot(pass);
+        if (m) {
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&lcount, (int)__popcll(m));          // LDS atomic
+            base = __shfl(base, 0);
+            if (pass) {
+                const int slot = base + (int)__popcll(m & ((1ull << lane) - 1ull));   // < AGN_EPT * 256: one slot per owned entry
+                lscore[slot] = obj;
+                lrow[slot] = (int)e;
+            }
+        }
+    }
+    __syncthreads();
+    const int nl = lcount;
+    if (threadIdx.x == 0) gbase = atomicAdd(&counts[b], nl);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nl; i += 256) {
+        const int slot = gbase + i;
+        if (slot < cap) {
+            cand_score[(int64_t)b * cap + slot] = lscore[i];
+            cand_row[(int64_t)b * cap + slot] = lrow[i];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // inference: top-k + per-class NMS, one workgroup per image
 // ------------------------------------------------------------------------------------------
+// AGN (class-agnostic tail, vd_nms_agnostic): a row indexes the (B, P, 6) tensor of YOLOOutputV3(agnostic=True) - [head][pixel]
+// [anchor], every id 0 - instead of the per-class (B, C*P, 6) one; HT = storage type of the head tensors the survivors' boxes
+// are re-decoded from.  <false, float> is the per-class kernel, statement for statement.
+template <bool AGN, typename HT>
 __global__ __launch_bounds__(NMS_THREADS) void k_nms(const vd_head_desc h, const float* __restrict__ cand_score,
                                                      const int32_t* __restrict__ cand_row, int cap,
                                                      const int32_t* __restrict__ counts, float nms_thresh,
@@ -444,7 +521,7 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms(const vd_head_desc h, const
     if (nsel > SORT_N) nsel = SORT_N;
     // re-decode the survivors' boxes from the head tensor
     const int R0 = h.g[0] * h.g[0], R1 = h.g[1] * h.g[1];
-    const int base1 = h.C * 3 * R0, base2 = h.C * 3 * (R0 + R1);
+    const int base1 = (AGN ? 1 : h.C) * 3 * R0, base2 = (AGN ? 1 : h.C) * 3 * (R0 + R1);
     const int npred = 5 + h.C;
     for (int idx = tid; idx < TOPK_MAX * (TOPK_MAX / 64); idx += NMS_THREADS) smask[idx] = 0ull;   // (was the select's histogram)
     if (tid < nsel) {
@@ -454,10 +531,10 @@ __global__ __launch_bounds__(NMS_THREADS) void k_nms(const vd_head_desc h, const
         else if (row < base2) { s = 1; rr = row - base1; }
         else { s = 2; rr = row - base2; }
         const int g = h.g[s], gg3 = g * g * 3;
-        const int c = rr / gg3, rem = rr - c * gg3;
+        const int c = AGN ? 0 : rr / gg3, rem = rr - c * gg3;
         const int pix = rem / 3, a = rem - pix * 3;
-        const float* src = h.head[s] + ((int64_t)b * g * g + pix) * h.ldh + a * npred;
-        float raw[4] = {src[0], src[1], src[2], src[3]};
+        const HT* src = reinterpret_cast<const HT*>(h.head[s]) + ((int64_t)b * g * g + pix) * h.ldh + a * npred;
+        float raw[4] = {(float)src[0], (float)src[1], (float)src[2], (float)src[3]};
         const Box bb = decode_box(raw, pix % g, pix / g, h.stride[s], h.anchors[s][2 * a], h.anchors[s][2 * a + 1]);
         bx1[tid] = bb.x1; by1[tid] = bb.y1; bx2[tid] = bb.x2; by2[tid] = bb.y2;
         bcls[tid] = c;
@@ -821,9 +898,49 @@ int vd_nms_topk(const vd_head_desc* h, const float* cand_score, const int32_t* c
     VD_REQUIRE(post_nms > 0, "vd_nms_topk: post_nms must be > 0");
     VD_REQUIRE(nms_thresh > 0.f && nms_thresh < 1.f, "vd_nms_topk: nms_thresh must be in (0,1)");
     int32_t* overflow = (ws && ws_bytes >= (int64_t)h->B * (int64_t)sizeof(int32_t)) ? (int32_t*)ws : nullptr;
-    hipLaunchKernelGGL(k_nms, dim3(h->B), dim3(NMS_THREADS), 0, (hipStream_t)stream, *h, cand_score, cand_row, cap, counts,
+    hipLaunchKernelGGL((k_nms<false, float>), dim3(h->B), dim3(NMS_THREADS), 0, (hipStream_t)stream, *h, cand_score, cand_row, cap, counts,
                        nms_thresh, topk, post_nms, out_ids, out_scores, out_boxes, out_rows, overflow);
     VD_CHECK_LAUNCH("vd_nms_topk");
+    return VD_OK;
+}
+
+int vd_yolo_decode_filter_agnostic(const vd_head_desc* h, int head_bf16, float valid_thresh, float* cand_score, int32_t* cand_row,
+                                   int32_t cap, int32_t* counts, void* stream) {
+    VD_REQUIRE(head_ok(h), "vd_yolo_decode_filter_agnostic: bad head descriptor");
+    VD_REQUIRE(cand_score && cand_row && counts && cap > 0, "vd_yolo_decode_filter_agnostic: bad args");
+    VD_REQUIRE(valid_thresh >= 0.f, "vd_yolo_decode_filter_agnostic: valid_thresh must be >= 0 (scores are keyed as positive floats)");
+    const int64_t E = 3ll * ((int64_t)h->g[0] * h->g[0] + (int64_t)h->g[1] * h->g[1] + (int64_t)h->g[2] * h->g[2]);
+    VD_REQUIRE(E < (1ll << 31), "vd_yolo_decode_filter_agnostic: row index overflows int32");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * h->B, s) != hipSuccess) {
+        vd_set_error("vd_yolo_decode_filter_agnostic: memset failed");
+        return VD_ELAUNCH;
+    }
+    const dim3 grid((unsigned)vd_cdiv(E, AGN_EPT * 256), (unsigned)h->B);
+    if (head_bf16)
+        hipLaunchKernelGGL(k_decode_filter_agn<__bf16>, grid, dim3(256), 0, s, *h, valid_thresh, cand_score, cand_row, cap, counts);
+    else
+        hipLaunchKernelGGL(k_decode_filter_agn<float>, grid, dim3(256), 0, s, *h, valid_thresh, cand_score, cand_row, cap, counts);
+    VD_CHECK_LAUNCH("vd_yolo_decode_filter_agnostic");
+    return VD_OK;
+}
+
+int vd_nms_agnostic(const vd_head_desc* h, int head_bf16, const float* cand_score, const int32_t* cand_row, int32_t cap,
+                    const int32_t* counts, float nms_thresh, int topk, int post_nms, float* out_ids, float* out_scores,
+                    float* out_boxes, int32_t* out_rows, void* ws, int64_t ws_bytes, void* stream) {
+    VD_REQUIRE(head_ok(h), "vd_nms_agnostic: bad head descriptor");
+    VD_REQUIRE(cand_score && cand_row && counts && out_ids && out_scores && out_boxes && out_rows, "vd_nms_agnostic: null");
+    VD_REQUIRE(topk > 0 && topk <= TOPK_MAX, "vd_nms_agnostic: topk=%d outside (0,%d]", topk, TOPK_MAX);
+    VD_REQUIRE(post_nms > 0, "vd_nms_agnostic: post_nms must be > 0");
+    VD_REQUIRE(nms_thresh > 0.f && nms_thresh < 1.f, "vd_nms_agnostic: nms_thresh must be in (0,1)");
+    int32_t* overflow = (ws && ws_bytes >= (int64_t)h->B * (int64_t)sizeof(int32_t)) ? (int32_t*)ws : nullptr;
+    if (head_bf16)
+        hipLaunchKernelGGL((k_nms<true, __bf16>), dim3(h->B), dim3(NMS_THREADS), 0, (hipStream_t)stream, *h, cand_score, cand_row, cap,
+                           counts, nms_thresh, topk, post_nms, out_ids, out_scores, out_boxes, out_rows, overflow);
+    else
+        hipLaunchKernelGGL((k_nms<true, float>), dim3(h->B), dim3(NMS_THREADS), 0, (hipStream_t)stream, *h, cand_score, cand_row, cap,
+                           counts, nms_thresh, topk, post_nms, out_ids, out_scores, out_boxes, out_rows, overflow);
+    VD_CHECK_LAUNCH("vd_nms_agnostic");
     return VD_OK;
 }
 

@@ -143,6 +143,8 @@ SIGNATURES = {
     "vd_yolo_decode_filter": (_i, [C.POINTER(HeadDesc), _f, _p, _p, C.c_int32, _p, _p]),
     "vd_nms_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_nms_topk": (_i, [C.POINTER(HeadDesc), _p, _p, C.c_int32, _p, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    "vd_yolo_decode_filter_agnostic": (_i, [C.POINTER(HeadDesc), _i, _f, _p, _p, C.c_int32, _p, _p]),
+    "vd_nms_agnostic": (_i, [C.POINTER(HeadDesc), _i, _p, _p, C.c_int32, _p, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     "vd_yolo_loss_ws_bytes": (_i64, [C.POINTER(HeadDesc)]),
     "vd_yolo_loss_fwd_bwd": (_i, [C.POINTER(HeadDesc), _p, _i, _p, _p, _p, _p, _p, _f, _i, _p,
                                   C.POINTER(_fp * 3), _p, C.POINTER(_fp * 3), _p, _i64, _p]),

@@ -1147,8 +1147,26 @@ class YOLOV3(object):
     def __init__(self, classes, nms_thresh=0.45, nms_topk=400, post_nms=100, ignore_iou_thresh=0.7,
                  device="cuda", syncbn_scope=None, process_group=None, k=1, k_join_type=None, k_join_pos=None,
                  block_conv_type='2', noback=False, temporal_out=False, temporal_side=False, corr_pos=None, corr_d=0,
-                 rnn_pos=None, conv_types=None):
+                 rnn_pos=None, conv_types=None, agnostic=False):
         self._classes = list(classes)
+        # class-agnostic detection (YOLOOutputV3(agnostic=True), yolo3.py:184-188): inference emits one candidate per anchor
+        # (id 0, score = sigmoid(objectness)) into the same box_nms.  The branch sits behind `if autograd.is_training()`, so
+        # the graph, the parameters and training are those of agnostic=False; only the decode + NMS tail of the inference
+        # plans differs (_add_agnostic_tail)
+        self.agnostic = bool(agnostic)
+        if self.agnostic:
+            if conv_types is not None and check_conv_types(conv_types, k) is not None:
+                raise NotImplementedError("agnostic with conv_types: detect_yolo3.py builds yolo3_3ddarknet without the flag "
+                                          "(detect_yolo3.py:872-882); the class-agnostic tail is built for yolo3_darknet53")
+            if rnn_pos == 'out':
+                raise NotImplementedError("agnostic with rnn_pos 'out': its predictions come from YOLOOutputV3's own RNN "
+                                          "output block (yolo3.py:1040-1042), a tail of its own that is not built agnostic")
+            if temporal_out or temporal_side:
+                raise NotImplementedError("agnostic with temporal / t_out: YOLOV3Temporal is not passed the flag "
+                                          "(wrappers.py:96-98)")
+            if noback:
+                raise NotImplementedError("agnostic with the no-backbone network: YOLOV3_noback has no agnostic argument "
+                                          "(wrappers.py:133-161)")
         # Darknet3D backbone on windows of k frames (yolo3_3ddarknet, wrappers.py:113-130): the neck and heads are the plain
         # single-frame ones (YOLOV3TB with k = 1), so nothing that joins or mixes frames behind the backbone combines with it
         self._conv_types = check_conv_types(conv_types, k)
@@ -1841,6 +1859,10 @@ class YOLOV3(object):
         hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
                                 STRIDES[::-1], ANCHORS[::-1], Bh, self.num_class)
         P = 3 * sum(g * g for g in grids)
+        if self.agnostic:
+            o = self._add_agnostic_tail(prog, hd, P, Bh)
+            autotune_program(prog)
+            return prog, bufs, o
         # one candidate slot per row of the reference's (B, C*P, 6) tensor: box_nms (yolo3.py:1197-1202) has no cap, and an
         # untrained net (validation after epoch 0) passes valid_thresh on every row.  8 bytes x C*P per image (14.6 MB at
         # 608x608 / 80 classes) is address space, not traffic: only the rows that pass are ever written or read.
@@ -1862,6 +1884,24 @@ class YOLOV3(object):
                  o['overflow'].data_ptr(), 4 * Bh)
         autotune_program(prog)
         return prog, bufs, o
+
+    def _add_agnostic_tail(self, prog, hd, P, Bh):
+        """The class-agnostic decode + NMS of an inference plan (fp32 and bf16 plans: the heads are fp32 in both).  One
+        candidate per anchor at the most, so the lists hold P entries per image and cannot overflow."""
+        dev = self.device
+        o = dict(cand_score=torch.empty(Bh, P, device=dev), cand_row=torch.empty(Bh, P, dtype=torch.int32, device=dev),
+                 counts=torch.zeros(Bh, dtype=torch.int32, device=dev), ids=torch.empty(Bh, self.post_nms, 1, device=dev),
+                 scores=torch.empty(Bh, self.post_nms, 1, device=dev), bboxes=torch.empty(Bh, self.post_nms, 4, device=dev),
+                 rows=torch.empty(Bh, self.post_nms, dtype=torch.int32, device=dev),
+                 overflow=torch.zeros(Bh, dtype=torch.int32, device=dev))
+        prog.hold(hd, o)
+        prog.add('vd_yolo_decode_filter_agnostic', C.byref(hd), 0, 0.01, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), P,
+                 o['counts'].data_ptr())
+        prog.add('vd_nms_agnostic', C.byref(hd), 0, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), P,
+                 o['counts'].data_ptr(), float(self.nms_thresh), int(self.nms_topk), int(self.post_nms),
+                 o['ids'].data_ptr(), o['scores'].data_ptr(), o['bboxes'].data_ptr(), o['rows'].data_ptr(),
+                 o['overflow'].data_ptr(), 4 * Bh)
+        return o
 
     def _refresh_fold(self):
         if not self._fold_dirty:
@@ -2019,6 +2059,8 @@ class YOLOV3(object):
         hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
                                 STRIDES[::-1], ANCHORS[::-1], Bh, self.num_class)
         P = 3 * sum(g * g for g in grids)
+        if self.agnostic:
+            return prog, bufs, self._add_agnostic_tail(prog, hd, P, Bh), packs
         cap = self.num_class * P          # no candidate cap (see _build_infer)
         o = dict(cand_score=torch.empty(Bh, cap, device=dev), cand_row=torch.empty(Bh, cap, dtype=torch.int32, device=dev),
                  counts=torch.zeros(Bh, dtype=torch.int32, device=dev), ids=torch.empty(Bh, self.post_nms, 1, device=dev),
@@ -3278,11 +3320,19 @@ class YOLOV3(object):
 
 def yolo3_darknet53(classes, pretrained_base=False, norm_layer=None, norm_kwargs=None, freeze_base=False,
                     k=None, k_join_type=None, k_join_pos=None, block_conv_type='2', temporal=False, t_out=False,
-                    corr_d=None, corr_pos=None, rnn_pos=None, **kwargs):
+                    corr_d=None, corr_pos=None, rnn_pos=None, agnostic=False, **kwargs):
     """wrappers.py:9-110 -> YOLOV3T (yolo3.py:959-1054).  norm_layer='syncbn' (the reference passes
     SyncBatchNorm) selects the SyncBN collective.  k>1 builds the temporal-window variants; `t_out=True`
     (--temp --mult_out) builds YOLOV3Temporal with per-frame outputs (yolo3_temporal.py:286-555, t = k = 5)."""
     k = 1 if k is None else int(k)
+    if agnostic:
+        # class-agnostic detection (wrappers.py:101-103 hands `agnostic` to YOLOV3T): what is refused is refused by name
+        if temporal or t_out:
+            raise NotImplementedError("agnostic with temporal / t_out: YOLOV3Temporal is not passed the flag (wrappers.py:96-98)")
+        if rnn_pos == 'out':
+            raise NotImplementedError("agnostic with rnn_pos 'out': its predictions come from YOLOOutputV3's own RNN output "
+                                      "block (yolo3.py:1040-1042), a tail of its own that is not built agnostic")
+        kwargs = dict(kwargs, agnostic=True)
     if rnn_pos is not None:
         # the bidirectional ConvGRU (RNN, layers.py:267-306; yolo3.py:978-988): what is built, and what is refused by name
         if rnn_pos not in ('late', 'out'):
@@ -3366,6 +3416,9 @@ def yolo3_3ddarknet(classes, pretrained_base=False, norm_layer=None, norm_kwargs
     stride-2 convs only: the blocks are built with plain BatchNorm (three_darknet.py:193), which is scope 'reference'.
     `net.inflate_from_2d(src)` starts it from a trained 2-D detector (get_darknet, three_darknet.py:289-318)."""
     ct = check_conv_types(conv_types, 2 if k is None else k)       # (all 2: no window is needed)
+    if ct is not None and kwargs.get('agnostic'):
+        raise NotImplementedError("agnostic with conv_types %r: detect_yolo3.py builds yolo3_3ddarknet without the flag "
+                                  "(detect_yolo3.py:872-882); the class-agnostic tail is built for yolo3_darknet53" % (ct,))
     if ct is None:
         return yolo3_darknet53(classes, pretrained_base=pretrained_base, norm_layer=norm_layer, norm_kwargs=norm_kwargs,
                                freeze_base=freeze_base, k=k, **kwargs)

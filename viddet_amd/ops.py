@@ -482,6 +482,18 @@ def nms_topk(h, cand_score, cand_row, cap, counts, nms_thresh, topk, post_nms, i
                              _s()), "vd_nms_topk")
 
 
+def yolo_decode_filter_agnostic(h, valid_thresh, cand_score, cand_row, cap, counts, head_bf16=False):
+    """class-agnostic candidates (one per anchor, score = sigmoid(objectness)); head_bf16: h.head point to bf16 tensors"""
+    check(_lib().vd_yolo_decode_filter_agnostic(C.byref(h), 1 if head_bf16 else 0, valid_thresh, ptr(cand_score), ptr(cand_row),
+                                                cap, ptr(counts), _s()), "vd_yolo_decode_filter_agnostic")
+
+
+def nms_agnostic(h, cand_score, cand_row, cap, counts, nms_thresh, topk, post_nms, ids, scores, boxes, rows, ws, head_bf16=False):
+    check(_lib().vd_nms_agnostic(C.byref(h), 1 if head_bf16 else 0, ptr(cand_score), ptr(cand_row), cap, ptr(counts), nms_thresh,
+                                 topk, post_nms, ptr(ids), ptr(scores), ptr(boxes), ptr(rows), ptr(ws),
+                                 ws.numel() * ws.element_size(), _s()), "vd_nms_agnostic")
+
+
 def yolo_loss_fwd_bwd(h, gt, M, obj_t, center_t, scale_t, weight_t, class_t, ignore_thresh, label_smooth, losses,
                       dheads, box_out, ws, dhead_amax=None):
     arr = (C.c_void_p * 3)(*[t.data_ptr() for t in dheads])

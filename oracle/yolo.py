@@ -196,6 +196,8 @@ def bbox_batch_iou(a, b, eps=1e-15):
 
 
 def dynamic_targets(box_preds, gt_boxes, ignore_iou_thresh=0.7):
+    if gt_boxes.shape[1] == 0:                                           # an empty gt axis: nothing to overlap, no ignore
+        return np.zeros(box_preds.shape[:2] + (1,))
     ious = bbox_batch_iou(box_preds, gt_boxes)
     ious_max = ious.max(axis=-1, keepdims=True)
     return (ious_max > ignore_iou_thresh) * -1.0                         # :204

@@ -213,6 +213,7 @@ def test_loss_fwd_bwd(cfg):
         assert maxdiff(d[..., :3 * (5 + c)], ref) < 1e-5
         assert float(np.abs(d[..., 3 * (5 + c):]).max(initial=0.0)) == 0.0
         off += n
-    # the ignore branch was really taken somewhere (dynamic IoU > 0.7) unless there is no gt
-    if sum(cfg["nvalid"]) > 0 and cfg["size"] >= 128:
-        assert (merged[0] < 0).sum() >= 0
+    # the ignore branch was really taken somewhere (dynamic IoU > 0.7 on a non-positive anchor): seeds 32..36 have 1, 2, 1, 3
+    # and 4 such anchors by the oracle (31 and 37 have none; tests/test_yolo_edges_gpu.py plants them by the dozen)
+    if 32 <= cfg["seed"] <= 36:
+        assert ((merged[0] < 0) & ~(obj_t > 0)).sum() > 0

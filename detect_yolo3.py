@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from viddet_amd import dist as vdist
-from viddet_amd.data import SyntheticDetection, SyntheticCombined, YOLO3VideoInferenceTransform, Loader
+from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticVideo, YOLO3VideoInferenceTransform, Loader
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
 from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
@@ -74,10 +74,29 @@ def parse_flags(argv=None):
     A("--synthetic_samples", type=int, default=32)
     A("--precision", default="fp32", choices=["fp32", "bf16"],
       help="(no reference counterpart) bf16: bf16 storage + bf16 MFMA inference, fp32 heads (net.set_precision, BASELINE configs[1])")
+    A("--stream", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) detect on whole synthetic clips with net.detect_video: the per-frame part of the network "
+           "runs once per frame into a feature ring, --batch_size output frames per chunk; the same prediction files and metric "
+           "as the windowed run on the same clips (DESIGN.md 19)")
+    A("--synthetic_videos", type=int, default=None,
+      help="(no reference counterpart) the dataset is SyntheticVideo: this many clips of --synthetic_samples frames each, "
+           "windows by --window K,step inside a clip (default with --stream: 2; without --stream the windowed path runs on it)")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
     return ap.parse_args(argv)
+
+
+def _collect(boxes, dataset, ids, scores, bboxes, sidxs, W):
+    """detect_yolo3.py:228-262: clip, keep rows with a class, normalise the boxes, file them under the image path"""
+    ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
+    bboxes = np.clip(bboxes.cpu().numpy(), 0, W)                           # :228 clip to image size
+    for id_, score, box, sidx in zip(ids, scores, bboxes, sidxs):
+        file = dataset.sample_path(int(sidx))
+        valid = np.where(id_.flat >= 0)[0]                                 # :255 boxes that have a class
+        box = box[valid, :] / W                                            # :257 normalise boxes
+        for i_, b_, s_ in zip(id_.flat[valid].astype(int), box, score.flat[valid]):
+            boxes.setdefault(file, []).append([i_, s_] + list(b_))
 
 
 def detect(net, dataset, loader, max_do=-1):
@@ -90,14 +109,26 @@ def detect(net, dataset, loader, max_do=-1):
     for x, _label, sidxs in loader:
         ids, scores, bboxes = net(torch.from_numpy(x).cuda())
         W = x.shape[-2] if x.dtype == np.uint8 else x.shape[-1]           # uint8 frames are (B,H,W,3)
-        ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
-        bboxes = np.clip(bboxes.cpu().numpy(), 0, W)                       # :228 clip to image size
-        for id_, score, box, sidx in zip(ids, scores, bboxes, sidxs):
-            file = dataset.sample_path(int(sidx))
-            valid = np.where(id_.flat >= 0)[0]                             # :255 boxes that have a class
-            box = box[valid, :] / W                                        # :257 normalise boxes
-            for i_, b_, s_ in zip(id_.flat[valid].astype(int), box, score.flat[valid]):
-                boxes.setdefault(file, []).append([i_, s_] + list(b_))
+        _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        c += x.shape[0]
+        if c > max_do:
+            break
+    return boxes
+
+
+def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1):
+    """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
+    the ranks (a clip's feature ring lives on one GPU)."""
+    net.set_nms(nms_thresh=0.45, nms_topk=400)
+    tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True)
+    boxes = dict()
+    if max_do < 0:
+        max_do = len(dataset)
+    c = 0
+    for v in range(rank, dataset.num_videos, world):
+        x, _, _ = tf(dataset.video_frames(v), np.zeros((0, 6)))            # uint8 (T,H,W,3), normalised on the device
+        ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk)
+        _collect(boxes, dataset, ids, scores, bboxes, [dataset.sample_index(v, t) for t in range(x.shape[0])], x.shape[-2])
         c += x.shape[0]
         if c > max_do:
             break
@@ -145,6 +176,22 @@ def check_flags(FLAGS):
     if FLAGS.model_agnostic and FLAGS.rnn_pos == "out":
         raise NotImplementedError("--model_agnostic with --rnn_pos out: the RNN output block is a tail of its own that is not "
                                   "built agnostic")
+    if getattr(FLAGS, "stream", False):
+        # net.detect_video runs the per-frame part of the network once per frame: what mixes the frames of a window ahead
+        # of the join has no such part (YOLOV3._stream_refusal names the same reasons)
+        for flag, on, why in (
+                ("conv_types", ct is not None, "the (2+1)-D backbone mixes the frames of a window inside the backbone"),
+                ("corr_pos", FLAGS.corr_pos, "the correlation join compares every frame with its window's centre frame and has "
+                                             "no form that reads the feature ring"),
+                ("rnn_pos", FLAGS.rnn_pos, "the ConvGRU carries a state across the frames of a window ahead of the join"),
+                ("block_conv_type", FLAGS.block_conv_type != "2", "the neck's 3-D / 2+1-D convs mix the frames of a window ahead "
+                                                                  "of the late join"),
+                ("dataset", len(FLAGS.dataset) > 1, "the combined set has no clips")):
+            if on:
+                raise NotImplementedError("--stream does not combine with --%s: %s" % (flag, why))
+        if int(FLAGS.window[0]) > 1 and (FLAGS.k_join_type not in ("max", "mean", "cat") or FLAGS.k_join_pos not in ("early", "late")):
+            raise NotImplementedError("--stream with --window %s needs --k_join_type max|mean|cat and --k_join_pos early|late: "
+                                      "the graph is split at that join" % FLAGS.window[0])
     return ct
 
 
@@ -206,6 +253,11 @@ def main(argv=None):
     name = FLAGS.dataset[0]
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
+    elif FLAGS.stream or FLAGS.synthetic_videos is not None:
+        # clips: --synthetic_videos of them (given, or 2 with --stream), --synthetic_samples frames each, windows by --window K,step
+        dataset = SyntheticVideo(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
+                                 frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
+                                 step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1)
     else:
         # --window k: a sample is the k-frame window around the frame the rows belong to (as train_yolov3.py's sets)
         dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples, window=FLAGS.window[0])
@@ -226,7 +278,11 @@ def main(argv=None):
         net.load_parameters(FLAGS.model_path)
     net.set_precision(FLAGS.precision)
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic)
-    boxes = detect(net, dataset, loader, FLAGS.max_do)
+    if FLAGS.stream:
+        boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
+                              FLAGS.max_do, rank, world)
+    else:
+        boxes = detect(net, dataset, loader, FLAGS.max_do)
     if world > 1:
         # frames are sharded over the ranks (replicas, no collective on the data path); the per-image box lists (host
         # objects) are merged so that ONE rank writes every file - a rank must never write an (empty) file for an image

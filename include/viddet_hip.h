@@ -565,6 +565,19 @@ int vd_yolo_loss_fwd_bwd_bf16(const vd_head_desc* h, const float* gt, int M, con
                               int label_smooth, float* losses, void* const dhead[3], float* box_out, void* ws, int64_t ws_bytes,
                               void* stream);
 
+/* ---- the joins of streaming video detection (vd_stream.hip): vd_temporal_pool / vd_temporal_pool_bf16 /
+ * vd_temporal_cat (forward) read in place from a ring of cached per-frame features.  ring [S][inner] = [S][hw][C]; slots
+ * [B][K] int32 in device memory, values in [0, S), any order, repeats allowed (a value outside the range is clamped into it:
+ * a bad table never reads outside the ring).  pool: y [B][inner], type 0 = max, 1 = mean; cat: y [B][hw][K*C].  The same
+ * arithmetic in the same order as the windowed kernels: the results are bit-equal to those kernels on the gathered copy
+ * [B][K][inner].  1 <= K < 128, S >= 1, inner % 4 == 0 (fp32) / % 8 (bf16), C % 4 == 0 (bf16 tensors go through the cat with
+ * C halved, as through vd_temporal_cat), ring / y 16-byte aligned.  Inference only: there is no backward. */
+int vd_temporal_pool_idx(const float* ring, const int32_t* slots, float* y, int S, int B, int K, int64_t inner, int type,
+                         void* stream);
+int vd_temporal_pool_idx_bf16(const void* ring, const int32_t* slots, void* y, int S, int B, int K, int64_t inner, int type,
+                              void* stream);
+int vd_temporal_cat_idx(const float* ring, const int32_t* slots, float* y, int S, int B, int K, int64_t hw, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,49 @@ class SyntheticDetection:
         return imgs, frames[self._window // 2][1]
 
 
+class SyntheticVideo(SyntheticDetection):
+    """Deterministic synthetic CLIPS: `num_videos` clips of `frames_per_video` distinct frames each.  Sample
+    idx = v * frames_per_video + t is frame t of clip v as the VID dataset yields it with --window K,step
+    (datasets/imgnetvid.py:486-506, restated in viddet_amd/stream.py): the K-frame window around t, padded inside its own
+    clip by repeating the first / last frame, with the centre frame's label - so the windowed path runs on it unchanged,
+    and `video_frames(v)` is the clip that net.detect_video streams over."""
+
+    def __init__(self, name="synthetic", num_videos=2, frames_per_video=16, window=1, step=1, **kw):
+        from .stream import stream_window_slots
+        self.num_videos, self.frames_per_video, self._step = int(num_videos), int(frames_per_video), int(step)
+        if self.num_videos < 1 or self.frames_per_video < 1:
+            raise ValueError("SyntheticVideo needs at least one clip of at least one frame")
+        if kw.get("mult_out"):
+            raise NotImplementedError("SyntheticVideo yields the centre frame's label (no --mult_out)")
+        super().__init__(name, num_samples=self.num_videos * self.frames_per_video, window=window, **kw)
+        self.window_frames = stream_window_slots(self.frames_per_video, max(1, self._window), self._step)   # [T][K]
+
+    def sample_index(self, v, t):
+        if not (0 <= v < self.num_videos and 0 <= t < self.frames_per_video):
+            raise IndexError("no frame %d of clip %d" % (t, v))
+        return v * self.frames_per_video + t
+
+    def sample_path(self, idx):
+        v, t = divmod(int(idx), self.frames_per_video)
+        return "synthetic/s%d_v%03d_%06d.jpg" % (self._seed, v, t)
+
+    def _clip_frame(self, v, t):
+        return self._frame(np.random.default_rng([self._seed, 7919, v, t]))
+
+    def video_frames(self, v):
+        """uint8 (T, h, w, 3): the frames of clip v in order"""
+        self.sample_index(v, 0)
+        return np.stack([self._clip_frame(v, t)[0] for t in range(self.frames_per_video)])
+
+    def __getitem__(self, idx):
+        v, t = divmod(int(idx), self.frames_per_video)
+        self.sample_index(v, t)
+        img, label = self._clip_frame(v, t)
+        if self._window <= 1:
+            return img, label
+        return np.stack([img if f == t else self._clip_frame(v, int(f))[0] for f in self.window_frames[t]]), label
+
+
 class SyntheticCombined(SyntheticDetection):
     """Stand-in for CombinedDetection(datasets, class_tree=True) (detect_yolo3.py:167, datasets/combined.py): the label set of
     several datasets arranged in a class tree - one group label per dataset under 'ROOT' (labels are ordered parents first,

@@ -163,6 +163,10 @@ SIGNATURES = {
     "vd_stem_wgrad_bf16": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i64, _p]),
     "vd_yolo_loss_fwd_bwd_bf16": (_i, [C.POINTER(HeadDesc), _p, _i, _p, _p, _p, _p, _p, _f, _i, _p,
                                        C.POINTER(_fp * 3), _p, _p, _i64, _p]),
+    # the joins of streaming video detection off a ring of cached per-frame features (vd_stream.hip)
+    "vd_temporal_pool_idx": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
+    "vd_temporal_pool_idx_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
+    "vd_temporal_cat_idx": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
 }
 
 _lib = None

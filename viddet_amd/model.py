@@ -1378,7 +1378,7 @@ class YOLOV3(object):
     def set_nms(self, nms_thresh=0.45, nms_topk=400, post_nms=100):
         # yolo3.py:1208-1228
         self.nms_thresh, self.nms_topk, self.post_nms = nms_thresh, nms_topk, post_nms
-        self._programs = {k: v for k, v in self._programs.items() if k[0] not in ('infer', 'infer_bf16')}
+        self._programs = {k: v for k, v in self._programs.items() if k[0] not in ('infer', 'infer_bf16', 'stream', 'stream_bf16')}
         self._graph_cache.clear()
 
     def initialize(self, init='uniform', seed=233, obj_bias=0.0):
@@ -1779,7 +1779,7 @@ class YOLOV3(object):
     def _add_stem(self, prog, n, bufs, B, H, W, out, *, scale=None, shift=None, leaky=False, bf16=False, stats=None):
         """vd_stem_conv: the 3 -> 32 stem straight from the NCHW batch (vd_stem.hip)."""
         flags = (EPI_AFFINE if scale is not None else 0) | (EPI_LEAKY if leaky else 0)
-        prog.add('vd_stem_conv', bufs['in'].data_ptr(), n.wp.data_ptr(), out.data_ptr(), out.shape[-1], B * self._k, H, W,
+        prog.add('vd_stem_conv', bufs['in'].data_ptr(), n.wp.data_ptr(), out.data_ptr(), out.shape[-1], bufs['in'].shape[0], H, W,
                  scale.data_ptr() if scale is not None else None, shift.data_ptr() if shift is not None else None,
                  LEAKY_SLOPE, flags, 1 if bf16 else 0, stats, meta=self._flops(n, B, H, W, 'fwd'))
 
@@ -1802,13 +1802,32 @@ class YOLOV3(object):
         bufs = self._buffers('infer', B, H, W, False)
         prog = Program()
         self._add_input_stage(prog, bufs, B, H, W)
+        self._add_infer_nodes(prog, self.nodes, bufs, B, H, W)
+        o = self._add_detect_tail(prog, bufs, B, H, W)
+        autotune_program(prog)
+        return prog, bufs, o
+
+    def _add_infer_nodes(self, prog, nodes, bufs, B, H, W, ring=None):
+        """The fp32 inference records of `nodes` on B samples.  ring = (slot table [B][K] int32, S): the joins read their
+        K frames from the ring of cached per-frame features `bufs['ring:' + source]` (detect_video, vd_stream.hip)."""
         am = lambda t: bufs['amax:' + t].data_ptr()
-        for n in self.nodes:
+        for n in nodes:
             if isinstance(n, UpcatNode):
                 o = bufs[n.dst]
                 prog.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
                          o.shape[1], o.shape[2], n.cu, n.cr)
                 prog.add('vd_amax_merge', am(n.up), am(n.route), am(n.dst))       # a concatenation: max of the two
+                continue
+            if isinstance(n, PoolNode) and ring is not None:
+                o, xs = bufs[n.dst], bufs['ring:' + n.src]
+                if n.type == 2:
+                    prog.add('vd_temporal_cat_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
+                             xs.shape[1] * xs.shape[2], xs.shape[3])
+                else:
+                    prog.add('vd_temporal_pool_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K, o[0].numel(),
+                             n.type, meta=dict(kind='pool_idx', bytes=4.0 * o.numel() * (n.K + 1)))
+                # the ring's frames went through the prefix in other launches: the operand scale is the join's own max-abs
+                prog.add('vd_amax', o.data_ptr(), o.numel(), am(n.dst))
                 continue
             if isinstance(n, PoolNode):
                 o, xs = bufs[n.dst], bufs[n.src]
@@ -1854,15 +1873,16 @@ class YOLOV3(object):
                                     leaky=True, amax_out=True)
             prog.hold(d)
             prog.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
+
+    def _add_detect_tail(self, prog, bufs, B, H, W):
+        """decode + NMS of an inference plan over the (fp32) heads in `bufs`; returns the output tensors"""
         grids = self._grid(H, W)
         Bh = B * self._head_frames           # images the decode / NMS see (B*t with per-frame predictions)
         hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
                                 STRIDES[::-1], ANCHORS[::-1], Bh, self.num_class)
         P = 3 * sum(g * g for g in grids)
         if self.agnostic:
-            o = self._add_agnostic_tail(prog, hd, P, Bh)
-            autotune_program(prog)
-            return prog, bufs, o
+            return self._add_agnostic_tail(prog, hd, P, Bh)
         # one candidate slot per row of the reference's (B, C*P, 6) tensor: box_nms (yolo3.py:1197-1202) has no cap, and an
         # untrained net (validation after epoch 0) passes valid_thresh on every row.  8 bytes x C*P per image (14.6 MB at
         # 608x608 / 80 classes) is address space, not traffic: only the rows that pass are ever written or read.
@@ -1882,8 +1902,7 @@ class YOLOV3(object):
                  o['counts'].data_ptr(), float(self.nms_thresh), int(self.nms_topk), int(self.post_nms),
                  o['ids'].data_ptr(), o['scores'].data_ptr(), o['bboxes'].data_ptr(), o['rows'].data_ptr(),
                  o['overflow'].data_ptr(), 4 * Bh)
-        autotune_program(prog)
-        return prog, bufs, o
+        return o
 
     def _add_agnostic_tail(self, prog, hd, P, Bh):
         """The class-agnostic decode + NMS of an inference plan (fp32 and bf16 plans: the heads are fp32 in both).  One
@@ -1945,7 +1964,6 @@ class YOLOV3(object):
                 bufs[name] = torch.zeros(B * fr, H // div, W // div, cp(c), dtype=BFT, device=dev)
         prog = Program()
         packs = []
-        fuse_stem = None
         if self.noback:
             # the three cached feature maps arrive as fp32 NCHW: NHWC, then one conversion each
             for nm, c_, d_ in ROUTE_TENSORS:
@@ -1955,12 +1973,32 @@ class YOLOV3(object):
                 prog.add('vd_nchw_to_nhwc', bufs['in:' + nm].data_ptr(), bufs['f32:' + nm].data_ptr(), B, c_, H // d_, W // d_)
                 n_el = bufs[nm].numel()
                 prog.add('vd_pack_weight_bf16', bufs['f32:' + nm].data_ptr(), bufs[nm].data_ptr(), 1, 1, n_el, n_el, 1)
-        for n in self.nodes:
+        self._add_infer_nodes_bf16(prog, self.nodes, bufs, B, H, W, packs)
+        return prog, bufs, self._add_detect_tail(prog, bufs, B, H, W), packs
+
+    def _add_infer_nodes_bf16(self, prog, nodes, bufs, B, H, W, packs, ring=None):
+        """The bf16 inference records of `nodes` on B samples; the bf16 weight images they read are appended to `packs`.
+        ring: as in _add_infer_nodes."""
+        dev = self.device
+        BFT = torch.bfloat16
+        cp = lambda c: 32 if c == 32 else round_up(c, 64)
+        fuse_stem = None
+        for n in nodes:
             if isinstance(n, UpcatNode):
                 o = bufs[n.dst]
                 # 16-byte-unit copy kernel: pass channel counts as if fp32 (bf16 count / 2)
                 prog.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
                          o.shape[1], o.shape[2], cp(n.cu) // 2, cp(n.cr) // 2)
+                continue
+            if isinstance(n, PoolNode) and ring is not None:
+                o, xs = bufs[n.dst], bufs['ring:' + n.src]
+                assert xs.shape[3] % 8 == 0
+                if n.type == 2:
+                    prog.add('vd_temporal_cat_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
+                             xs.shape[1] * xs.shape[2], xs.shape[3] // 2)
+                else:
+                    prog.add('vd_temporal_pool_idx_bf16', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
+                             o[0].numel(), n.type, meta=dict(kind='pool_idx', bytes=2.0 * o.numel() * (n.K + 1)))
                 continue
             if isinstance(n, PoolNode):
                 o, xs = bufs[n.dst], bufs[n.src]
@@ -1988,8 +2026,8 @@ class YOLOV3(object):
                 # the stem and the stride-2 conv behind it as ONE launch (vd_stem_conv_c32_bf16: the stem's 32-channel map is
                 # computed inside the first-stage patch kernel and never stored; same bits) where that conv is the stem's only
                 # reader; VD_STEM_FUSED=0: two launches
-                users = [m for m in self.nodes if isinstance(m, ConvNode) and (m.src == n.dst or m.residual == n.dst)] + \
-                        [m for m in self.nodes if not isinstance(m, ConvNode) and n.dst in
+                users = [m for m in nodes if isinstance(m, ConvNode) and (m.src == n.dst or m.residual == n.dst)] + \
+                        [m for m in nodes if not isinstance(m, ConvNode) and n.dst in
                          [getattr(m, a, None) for a in ('src', 'up', 'route', 'a', 'b')]]
                 import os
                 fuse_stem = None
@@ -2054,27 +2092,6 @@ class YOLOV3(object):
             prog.add('vd_conv_igemm_bf16', C.byref(d), 1 if n.head else 0, meta=self._flops(n, B, H, W, 'fwd'))
             if tvalid:
                 prog.add('vd_frame_slice', out.data_ptr(), bufs[n.dst].data_ptr(), B, n.fr, 1, n.fr - 2, out[0].numel() // 2, 0)
-        grids = self._grid(H, W)
-        Bh = B * self._head_frames           # images the decode / NMS see (B*t with per-frame predictions)
-        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
-                                STRIDES[::-1], ANCHORS[::-1], Bh, self.num_class)
-        P = 3 * sum(g * g for g in grids)
-        if self.agnostic:
-            return prog, bufs, self._add_agnostic_tail(prog, hd, P, Bh), packs
-        cap = self.num_class * P          # no candidate cap (see _build_infer)
-        o = dict(cand_score=torch.empty(Bh, cap, device=dev), cand_row=torch.empty(Bh, cap, dtype=torch.int32, device=dev),
-                 counts=torch.zeros(Bh, dtype=torch.int32, device=dev), ids=torch.empty(Bh, self.post_nms, 1, device=dev),
-                 scores=torch.empty(Bh, self.post_nms, 1, device=dev), bboxes=torch.empty(Bh, self.post_nms, 4, device=dev),
-                 rows=torch.empty(Bh, self.post_nms, dtype=torch.int32, device=dev),
-                 overflow=torch.zeros(Bh, dtype=torch.int32, device=dev))
-        prog.hold(hd, o)
-        prog.add('vd_yolo_decode_filter', C.byref(hd), 0.01, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), cap,
-                 o['counts'].data_ptr())
-        prog.add('vd_nms_topk', C.byref(hd), o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), cap,
-                 o['counts'].data_ptr(), float(self.nms_thresh), int(self.nms_topk), int(self.post_nms),
-                 o['ids'].data_ptr(), o['scores'].data_ptr(), o['bboxes'].data_ptr(), o['rows'].data_ptr(),
-                 o['overflow'].data_ptr(), 4 * Bh)
-        return prog, bufs, o, packs
 
     def _refresh_bf16(self, packs):
         """Re-derive the bf16 weight images and the padded fp32 scale/shift vectors after a parameter change."""
@@ -2162,6 +2179,223 @@ class YOLOV3(object):
             K = self._k
             return (o['ids'].view(B, K, -1, 1), o['scores'].view(B, K, -1, 1), o['bboxes'].view(B, K, -1, 4))
         return o['ids'], o['scores'], o['bboxes']
+
+    # ------------------------------------------------------------------ streaming video detection
+    def _stream_refusal(self):
+        """Why this network cannot detect on a clip frame by frame (None: it can).  Decided from the constructor's
+        arguments first, so that every refusal carries the name the caller used; _stream_split() then checks the graph."""
+        if self._conv_types:
+            return ("conv_types %r: the (2+1)-D backbone mixes the frames of a window inside the backbone itself (the temporal "
+                    "depthwise convs, vd_tdw.hip), so no part of it is per-frame" % (self._conv_types,))
+        if self.noback:
+            return ("noback: the no-backbone network takes cached feature maps, not frames: it has no window, no join and no "
+                    "per-frame prefix to run once")
+        if self.temporal_out or self.temporal_side:
+            return ("temporal / t_out: YOLOV3Temporal has no pooled or stacked join to split at - its side branches are temporal "
+                    "convs over the window's frames (t_out: every frame keeps its own predictions)")
+        if self._rnn_pos:
+            return ("rnn_pos %r: the ConvGRU carries a state across the K frames of a window ahead of the join, so a frame's "
+                    "features depend on the window it is seen in" % (self._rnn_pos,))
+        if self._corr_pos:
+            return ("corr_pos %r: the correlation join compares every frame with the centre frame of ITS window (vd_corr.hip "
+                    "reads a materialised window); it has no form that reads a ring" % (self._corr_pos,))
+        if self._block_conv_type != '2':
+            return ("block_conv_type %r: the neck's 3-D / 2+1-D convs mix the frames of a window ahead of the late join, so "
+                    "the neck is not per-frame" % (self._block_conv_type,))
+        if self._k > 1 and (self._k_join_type not in ('max', 'mean', 'cat') or self._k_join_pos not in ('early', 'late')):
+            return ("k_join_type %r / k_join_pos %r: a window k > 1 needs a max | mean | cat join, early or late, to split at"
+                    % (self._k_join_type, self._k_join_pos))
+        return None
+
+    def _stream_split(self):
+        """Split the inference graph at the joins: (prefix, suffix).  The prefix is every node whose output a PoolNode
+        transitively needs - re-made as nodes over single frames (fr = 1; they share the parameters) - the suffix the joins
+        and everything behind them.  Asserts that the prefix is per-frame arithmetic and that the suffix sees the prefix
+        through the joins only."""
+        import copy
+        pools = [n for n in self.nodes if isinstance(n, PoolNode)]
+        assert pools, "no join to split at"
+        ins = lambda n: [t for t in (getattr(n, a, None) for a in ('src', 'residual', 'up', 'route', 'a', 'b')) if t is not None]
+        need = {p.src for p in pools}
+        for n in reversed(self.nodes):
+            if not isinstance(n, PoolNode) and n.dst in need:
+                need.update(ins(n))
+        prefix, suffix = [], []
+        for n in self.nodes:
+            if isinstance(n, PoolNode) or n.dst not in need:
+                suffix.append(n)
+                continue
+            ok = (isinstance(n, ConvNode) and n.kd == 1 and not getattr(n, 'tvalid', False)) or isinstance(n, UpcatNode)
+            assert ok and n.fr == self._k, "%s (%s) upstream of a join is not per-frame" % (n.name, type(n).__name__)
+            m = copy.copy(n)
+            m.fr = 1
+            prefix.append(m)
+        for n in suffix:
+            if isinstance(n, PoolNode):
+                assert n.K == self._k and self.tensors[n.src][3] == self._k and self.tensors[n.dst][3] == 1, n.name
+            else:
+                assert isinstance(n, (ConvNode, UpcatNode)) and n.fr == 1 and not (set(ins(n)) & need), \
+                    "%s behind the joins reads a per-frame tensor" % n.name
+        return prefix, suffix
+
+    def _stream_bufs(self, names, rows, H, W, bf16):
+        """activation tensors `names` of a streaming plan on `rows` frames (layouts of _buffers / _build_infer_bf16)"""
+        dev, bufs = self.device, {}
+        cp = lambda c: 32 if c == 32 else round_up(c, 64)
+        for name in names:
+            c, div, ld, _ = self.tensors[name]
+            if name == 'in':
+                bufs['in'] = torch.zeros(rows, 3, H, W, device=dev)
+            elif bf16 and name not in self.head_names:
+                bufs[name] = torch.zeros(rows, H // div, W // div, cp(c), dtype=torch.bfloat16, device=dev)    # pad channels stay 0
+            else:
+                bufs[name] = torch.empty(rows, H // div, W // div, ld, device=dev)
+                if not bf16:
+                    bufs[name].normal_()                           # the autotuner times on these: noise, not zero pages (_buffers)
+        if not bf16:
+            act = [nm for nm in names if nm != 'in']
+            bufs['amax'] = torch.zeros(max(1, len(act)) * L.AMAX_FLOATS, device=dev)
+            for i, nm in enumerate(act):
+                bufs['amax:' + nm] = bufs['amax'][i * L.AMAX_FLOATS:(i + 1) * L.AMAX_FLOATS]
+        return bufs
+
+    def _build_stream(self, Bc, H, W, S):
+        """The two programs of detect_video: the per-frame prefix on Bc frames, and the joins off the ring + the suffix +
+        decode / NMS on Bc windows."""
+        bf16 = self.precision == 'bf16'
+        prefix, suffix = self._stream_split()
+        srcs = [n.src for n in suffix if isinstance(n, PoolNode)]
+        pnames = ['in'] + [n.dst for n in prefix]
+        snames = [n.dst for n in suffix]
+        pb = self._stream_bufs(pnames, Bc, H, W, bf16)
+        sb = self._stream_bufs(snames, Bc, H, W, bf16)
+        for t in srcs:                                           # slot = frame index mod S
+            sb['ring:' + t] = torch.zeros((S,) + tuple(pb[t].shape[1:]), dtype=pb[t].dtype, device=self.device)
+        slots = torch.zeros(Bc, self._k, dtype=torch.int32, device=self.device)
+        pre, suf, packs = Program(), Program(), []
+        if bf16:
+            self._add_infer_nodes_bf16(pre, prefix, pb, Bc, H, W, packs)
+            self._add_infer_nodes_bf16(suf, suffix, sb, Bc, H, W, packs, ring=(slots, S))
+        else:
+            self._add_amax_reset(pre, pb)
+            self._add_infer_nodes(pre, prefix, pb, Bc, H, W)
+            self._add_amax_reset(suf, sb)
+            self._add_infer_nodes(suf, suffix, sb, Bc, H, W, ring=(slots, S))
+        o = self._add_detect_tail(suf, sb, Bc, H, W)
+        if not bf16:                                             # (the bf16 plans are tuned once their weight images exist)
+            autotune_program(pre)
+            autotune_program(suf)
+        return dict(pre=pre, suf=suf, pb=pb, sb=sb, o=o, packs=packs, slots=slots, srcs=srcs, S=S)
+
+    def _stage_frames(self, dst, frames, a, b):
+        """frames [a, b) of the clip -> the first rows of the NCHW input tensor `dst`, normalised as net(x) does; the rows
+        behind them repeat the last one (a padded row must hold real data: the fp32 operand scales are per tensor)"""
+        n = b - a
+        if frames.dtype == torch.uint8:
+            xd = frames[a:b].to(self.device).contiguous()
+            L.check(L.load().vd_preprocess_u8_nchw(xd.data_ptr(), dst.data_ptr(), n, dst.shape[2], dst.shape[3], L.stream_ptr()),
+                    'vd_preprocess_u8_nchw')
+        else:
+            dst[:n].copy_(frames[a:b])
+        if n < dst.shape[0]:
+            dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
+
+    def detect_video(self, frames, step=1, chunk=8):
+        """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
+        (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
+        (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
+
+        The graph is split at the joins (_stream_split).  The prefix runs on the frames that are not yet in a ring of
+        S = chunk + 2*(K//2)*step slots per join source (slot = frame mod S); per chunk of output frames the slot table of
+        its windows is uploaded, the joins read the ring in place (vd_stream.hip) and the suffix runs at batch `chunk`.  A
+        shorter last chunk runs the same programs on padded rows (repeats of its last real row) whose outputs are dropped.
+        Honours set_precision, set_nms and agnostic; k = 1 is plain batched detection in chunks.  `stream_stats` counts the
+        frames that went through each part in the last call; last_rows / last_overflow cover the T frames.  With
+        `stream_keep_heads` set on the net, `stream_heads` keeps the three raw head tensors of the T frames (k > 1)."""
+        why = self._stream_refusal()
+        if why is not None:
+            raise NotImplementedError("detect_video with " + why)
+        if self._k > 1:
+            self._stream_split()                                  # the graph's own word, before anything touches the GPU
+        from .stream import stream_window_slots, ring_size, chunk_slots
+        step, chunk = int(step), int(chunk)
+        if step < 1 or chunk < 1:
+            raise ValueError("detect_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
+        u8 = frames.dtype == torch.uint8
+        if frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
+            raise ValueError("expected a clip (T,3,H,W), or (T,H,W,3) uint8, got %s" % (tuple(frames.shape),))
+        T, H, W = self._in_shape(frames)
+        assert 0 < self.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
+        dev, K = self.device, self._k
+        out = dict(ids=torch.empty(T, self.post_nms, 1, device=dev), scores=torch.empty(T, self.post_nms, 1, device=dev),
+                   bboxes=torch.empty(T, self.post_nms, 4, device=dev),
+                   rows=torch.empty(T, self.post_nms, dtype=torch.int32, device=dev),
+                   overflow=torch.zeros(T, dtype=torch.int32, device=dev))
+        stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
+        heads = [] if getattr(self, 'stream_keep_heads', False) else None     # tests: the raw head tensors of every chunk
+
+        def keep(o, t0, n, bufs=None):
+            for k_ in out:
+                out[k_][t0:t0 + n].copy_(o[k_][:n])
+            if heads is not None and bufs is not None:
+                heads.append([bufs[h][:n].clone() for h in self.head_names])
+            stats['suffix_frames'] += n
+            stats['chunks'] += 1
+
+        if K == 1:
+            # no join, no prefix: the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame
+            for t0 in range(0, T, chunk):
+                n = min(chunk, T - t0)
+                x = frames[t0:t0 + n]
+                if n < chunk:
+                    x = torch.cat([x, x[-1:].expand((chunk - n,) + tuple(x.shape[1:]))], dim=0)
+                self._forward_infer(x)
+                keep(self._programs[('infer_bf16' if self.precision == 'bf16' else 'infer', chunk, H, W)][2], t0, n)
+        else:
+            S = ring_size(K, step, chunk)
+            bf16 = self.precision == 'bf16'
+            key = ('stream_bf16' if bf16 else 'stream', chunk, H, W, S)
+            if key not in self._programs:
+                self._programs[key] = self._build_or_evict(lambda: self._build_stream(chunk, H, W, S))
+            sp = self._programs[key]
+            if bf16:
+                # every plan owns its bf16 weight images (see _forward_infer)
+                if sp.get('packs_version') != (self._weights_version, self._stats_version):
+                    self._refresh_bf16(sp['packs'])
+                    if 'packs_version' not in sp:
+                        self._tune_bf16(sp['pre'])
+                        self._tune_bf16(sp['suf'])
+                    sp['packs_version'] = (self._weights_version, self._stats_version)
+            else:
+                self._refresh_fold()
+            self._refresh_wamax()
+            windows = stream_window_slots(T, K, step)
+            reach = (K // 2) * step
+            done = 0                                             # frames [max(0, done - S), done) are in the ring
+            for t0 in range(0, T, chunk):
+                n = min(chunk, T - t0)
+                need = min(T, t0 + n + reach)
+                while done < need:                               # each frame goes through the prefix here, once
+                    m = min(chunk, need - done)
+                    self._stage_frames(sp['pb']['in'], frames, done, done + m)
+                    sp['pre'].run()
+                    for t in sp['srcs']:                         # rows -> slots (a run of frames wraps at most once: m <= S)
+                        ring, src = sp['sb']['ring:' + t], sp['pb'][t]
+                        s0 = done % S
+                        m0 = min(m, S - s0)
+                        ring[s0:s0 + m0].copy_(src[:m0])
+                        if m0 < m:
+                            ring[:m - m0].copy_(src[m0:m])
+                    done += m
+                    stats['prefix_frames'] += m
+                tab = chunk_slots(windows, t0, n, chunk, S, max(0, done - S), done)
+                sp['slots'].copy_(torch.from_numpy(tab))
+                sp['suf'].run()
+                keep(sp['o'], t0, n, sp['sb'])
+        self.stream_stats = stats
+        self.stream_heads = [torch.cat(h) for h in zip(*heads)] if heads else None
+        self.last_rows, self.last_overflow = out['rows'], out['overflow']
+        return out['ids'], out['scores'], out['bboxes']
 
     def extract_features(self, x):
         """extract_base_features.py:127-130: f1 = features[:15](x), f2 = features[15:24](f1), f3 = features[24:](f2) in

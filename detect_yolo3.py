@@ -78,6 +78,11 @@ def parse_flags(argv=None):
       help="(no reference counterpart) detect on whole synthetic clips with net.detect_video: the per-frame part of the network "
            "runs once per frame into a feature ring, --batch_size output frames per chunk; the same prediction files and metric "
            "as the windowed run on the same clips (DESIGN.md 19)")
+    A("--device_resize", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) ship the raw uint8 frames at their source size and resize them to --data_shape on the "
+           "device, inside the kernel that normalises them (net.set_device_resize): the host's imresize leaves the per-frame "
+           "path; predictions differ from the host-resized run only where the fp32 resample rounds a grey level the other "
+           "way (DESIGN.md 20)")
     A("--synthetic_videos", type=int, default=None,
       help="(no reference counterpart) the dataset is SyntheticVideo: this many clips of --synthetic_samples frames each, "
            "windows by --window K,step inside a clip (default with --stream: 2; without --stream the windowed path runs on it)")
@@ -99,8 +104,9 @@ def _collect(boxes, dataset, ids, scores, bboxes, sidxs, W):
             boxes.setdefault(file, []).append([i_, s_] + list(b_))
 
 
-def detect(net, dataset, loader, max_do=-1):
-    """detect_yolo3.py:198-272."""
+def detect(net, dataset, loader, max_do=-1, data_shape=None):
+    """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
+    (--device_resize: raw frames, resized on the device)."""
     net.set_nms(nms_thresh=0.45, nms_topk=400)
     boxes = dict()
     if max_do < 0:
@@ -108,7 +114,7 @@ def detect(net, dataset, loader, max_do=-1):
     c = 0
     for x, _label, sidxs in loader:
         ids, scores, bboxes = net(torch.from_numpy(x).cuda())
-        W = x.shape[-2] if x.dtype == np.uint8 else x.shape[-1]           # uint8 frames are (B,H,W,3)
+        W = data_shape or (x.shape[-2] if x.dtype == np.uint8 else x.shape[-1])   # uint8 frames are (B,H,W,3)
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         c += x.shape[0]
         if c > max_do:
@@ -116,11 +122,11 @@ def detect(net, dataset, loader, max_do=-1):
     return boxes
 
 
-def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1):
+def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
-    the ranks (a clip's feature ring lives on one GPU)."""
+    the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size."""
     net.set_nms(nms_thresh=0.45, nms_topk=400)
-    tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True)
+    tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize)
     boxes = dict()
     if max_do < 0:
         max_do = len(dataset)
@@ -128,7 +134,8 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     for v in range(rank, dataset.num_videos, world):
         x, _, _ = tf(dataset.video_frames(v), np.zeros((0, 6)))            # uint8 (T,H,W,3), normalised on the device
         ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk)
-        _collect(boxes, dataset, ids, scores, bboxes, [dataset.sample_index(v, t) for t in range(x.shape[0])], x.shape[-2])
+        _collect(boxes, dataset, ids, scores, bboxes, [dataset.sample_index(v, t) for t in range(x.shape[0])],
+                 data_shape if device_resize else x.shape[-2])
         c += x.shape[0]
         if c > max_do:
             break
@@ -176,6 +183,9 @@ def check_flags(FLAGS):
     if FLAGS.model_agnostic and FLAGS.rnn_pos == "out":
         raise NotImplementedError("--model_agnostic with --rnn_pos out: the RNN output block is a tail of its own that is not "
                                   "built agnostic")
+    if getattr(FLAGS, "device_resize", False) and len(FLAGS.dataset) > 1:
+        raise NotImplementedError("--device_resize does not combine with several --dataset names: the combined set's path is "
+                                  "left on the host resize")
     if getattr(FLAGS, "stream", False):
         # net.detect_video runs the per-frame part of the network once per frame: what mixes the frames of a window ahead
         # of the join has no such part (YOLOV3._stream_refusal names the same reasons)
@@ -262,7 +272,9 @@ def main(argv=None):
         # --window k: a sample is the k-frame window around the frame the rows belong to (as train_yolov3.py's sets)
         dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples, window=FLAGS.window[0])
     # frames travel as uint8 and are normalised on the device (vd_preprocess_u8_nchw: the transform's own arithmetic)
-    loader = Loader(dataset, YOLO3VideoInferenceTransform(FLAGS.data_shape, FLAGS.data_shape, device_normalize=True),
+    # (--device_resize: at their source size, resized there too - vd_resize_u8_nchw)
+    loader = Loader(dataset, YOLO3VideoInferenceTransform(FLAGS.data_shape, FLAGS.data_shape, device_normalize=True,
+                                                          device_resize=FLAGS.device_resize),
                     FLAGS.batch_size, train=False, last_batch="keep", rank=rank, world=world)
     # detect_yolo3.py:871-892
     if ct is not None:
@@ -277,12 +289,14 @@ def main(argv=None):
     else:
         net.load_parameters(FLAGS.model_path)
     net.set_precision(FLAGS.precision)
+    if FLAGS.device_resize:
+        net.set_device_resize(FLAGS.data_shape, FLAGS.data_shape)
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic)
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
-                              FLAGS.max_do, rank, world)
+                              FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize)
     else:
-        boxes = detect(net, dataset, loader, FLAGS.max_do)
+        boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None)
     if world > 1:
         # frames are sharded over the ranks (replicas, no collective on the data path); the per-image box lists (host
         # objects) are merged so that ONE rank writes every file - a rank must never write an (empty) file for an image

@@ -578,6 +578,18 @@ int vd_temporal_pool_idx_bf16(const void* ring, const int32_t* slots, void* y, i
                               void* stream);
 int vd_temporal_cat_idx(const float* ring, const int32_t* slots, float* y, int S, int B, int K, int64_t hw, int C, void* stream);
 
+/* ---- resize of raw uint8 frames on the device, fused with the input normalisation (vd_resize.hip).
+ * in [N,H0,W0,3] uint8 -> out [N,3,H,W] fp32, normalised as vd_preprocess_u8_nchw normalises; out_u8 (may be NULL) receives
+ * the resized frame [N,H,W,3] uint8.  The resample is separable and given by tables in device memory, per axis T taps per
+ * output index: idx_y [H][Ty] int32 / w_y [H][Ty] fp32, idx_x [W][Tx] / w_x [W][Tx] - what viddet_amd/video.py _axis_taps
+ * returns (area, bilinear, bicubic, Lanczos), cast; an index outside the axis is clamped into it (a bad table reads a wrong
+ * pixel, never memory outside the frame).  fp32 arithmetic in a fixed order (horizontal taps 0 .. Tx-1, then vertical taps
+ * 0 .. Ty-1, fmaf from 0), rintf, clamp to [0, 255]: `out` is bit-equal to vd_preprocess_u8_nchw applied to `out_u8`.
+ * 1 <= Ty, Tx <= 16; all sizes >= 1; out and the tables 4-byte aligned; VD_EINVAL where the source rows one tile needs do not
+ * fit in LDS (a shrink beyond what 16 taps cover).  No atomics, bit-reproducible. */
+int vd_resize_u8_nchw(const uint8_t* in, float* out, uint8_t* out_u8, int N, int H0, int W0, int H, int W, const int32_t* idx_y,
+                      const float* w_y, int Ty, const int32_t* idx_x, const float* w_x, int Tx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

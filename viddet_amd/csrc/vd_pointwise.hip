@@ -12,6 +12,7 @@
 // All kernels move 16 B per lane (float4) with channel-contiguous NHWC addressing and a capped
 // grid-stride launch (<= 4096 blocks) so the 256 CUs stay saturated without launch overhead.
 #include "vd_common.h"
+#include "vd_preprocess.h"
 
 namespace {
 
@@ -161,23 +162,19 @@ __global__ void k_nchw_to_nhwc(const float* __restrict__ in, float* __restrict__
 }
 
 __global__ void k_preprocess_u8(const uint8_t* __restrict__ in, float* __restrict__ out, int64_t n) {
-    // mean/std of transforms.py:167-168; x/255 first (to_tensor), then (x-mean)/std (normalize)
-    const float mean[3] = {0.485f, 0.456f, 0.406f};
-    const float stdv[3] = {0.229f, 0.224f, 0.225f};
+    // x/255 first (to_tensor), then (x-mean)/std (normalize): vd_preprocess.h
     GRID_STRIDE(i, n) {
         const int c = (int)(i % 3);
-        out[i] = ((float)in[i] / 255.0f - mean[c]) / stdv[c];
+        out[i] = vd_normalize_level((float)in[i], c);
     }
 }
 
 // the same arithmetic, written as the planar [N,3,H,W] batch the stem kernel reads (vd_stem.hip): one thread = one pixel
 __global__ void k_preprocess_u8_nchw(const uint8_t* __restrict__ in, float* __restrict__ out, int64_t npix, int64_t hw) {
-    const float mean[3] = {0.485f, 0.456f, 0.406f};
-    const float stdv[3] = {0.229f, 0.224f, 0.225f};
     GRID_STRIDE(i, npix) {
         const int64_t n = i / hw, r = i - n * hw;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) out[(n * 3 + c) * hw + r] = ((float)in[i * 3 + c] / 255.0f - mean[c]) / stdv[c];
+        for (int c = 0; c < 3; ++c) out[(n * 3 + c) * hw + r] = vd_normalize_level((float)in[i * 3 + c], c);
     }
 }
 

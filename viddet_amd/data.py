@@ -189,18 +189,26 @@ class YOLO3VideoInferenceTransform:
     """transforms.py:297-350: resize to (width,height) with interp 9 (area when shrinking / bicubic when enlarging,
     viddet_amd/video.py imresize), to_tensor, normalize; boxes resized along.  device_normalize=True keeps the resized
     frames as uint8 (H,W,3) / (k,H,W,3): the network normalises them on the GPU (vd_preprocess_u8_nchw) - the same
-    arithmetic, a quarter of the bytes over PCIe."""
+    arithmetic, a quarter of the bytes over PCIe.  device_resize=True (with device_normalize) returns the frames untouched,
+    uint8 at their source size: the network resizes them on the GPU too (YOLOV3.set_device_resize, vd_resize_u8_nchw); the
+    boxes are resized to (width,height) as before."""
 
-    def __init__(self, width, height, device_normalize=False):
-        self._w, self._h, self._u8 = width, height, device_normalize
+    def __init__(self, width, height, device_normalize=False, device_resize=False):
+        if device_resize and not device_normalize:
+            raise ValueError("device_resize=True needs device_normalize=True: the device resizes raw uint8 frames inside the "
+                             "kernel that normalises them")
+        self._w, self._h, self._u8, self._raw = width, height, device_normalize, bool(device_resize)
 
     def __call__(self, img, label, idx=0):
         h, w = img.shape[-3], img.shape[-2]
-        frames = img if img.ndim == 4 else img[np.newaxis]
-        ims = [imresize(f, self._w, self._h, interp=9) for f in frames]                      # transforms.py:329-333
-        out = np.stack(ims) if self._u8 else np.stack([_to_tensor_normalize(im) for im in ims])
-        if img.ndim != 4:
-            out = out[0]
+        if self._raw:
+            out = np.asarray(img, dtype=np.uint8)
+        else:
+            frames = img if img.ndim == 4 else img[np.newaxis]
+            ims = [imresize(f, self._w, self._h, interp=9) for f in frames]                  # transforms.py:329-333
+            out = np.stack(ims) if self._u8 else np.stack([_to_tensor_normalize(im) for im in ims])
+            if img.ndim != 4:
+                out = out[0]
         bb = tbbox.resize(label, (w, h), (self._w, self._h))
         if isinstance(bb, (list, tuple)):                  # per-frame labels (--mult_out): (k, M, 6), -1 padded
             return out, pad_stack([np.asarray(b, dtype=np.float32) for b in bb]), idx

@@ -167,6 +167,8 @@ SIGNATURES = {
     "vd_temporal_pool_idx": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
     "vd_temporal_pool_idx_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
     "vd_temporal_cat_idx": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
+    # raw uint8 frames resized and normalised on the device (vd_resize.hip)
+    "vd_resize_u8_nchw": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p]),
 }
 
 _lib = None

@@ -1216,6 +1216,8 @@ class YOLOV3(object):
         self.overlap_wgrad = _os.environ.get('VD_OVERLAP', '1') != '0'   # wgrad GEMMs on a side stream (_build_train)
         self.fuse_bn_stats = _os.environ.get('VD_FUSE_STATS', '1') != '0'  # BN statistics in the conv epilogue
         self.precision = 'fp32'        # inference precision: 'fp32' | 'bf16' (set_precision)
+        self._dev_resize = None        # (height, width, interp): raw uint8 frames are resized on the device (set_device_resize)
+        self._resize_cache = {}        # (H0, W0, H, W, interp) -> the tap tables of that resize, host and device
         self.bucketed_allreduce = _os.environ.get('VD_BUCKETED', '1') != '0'
         self.alias_skip_grad = _os.environ.get('VD_ALIAS_SKIP', '1') != '0'    # skip gradients by alias, not by copy
         self.fuse_bn_bwd = _os.environ.get('VD_FUSE_BWD', '1') != '0'          # BN backward reductions in the dgrad epilogue
@@ -1791,12 +1793,29 @@ class YOLOV3(object):
             # uint8 frames (B,H,W,3) or windows (B,K,H,W,3) straight from the loader: /255, normalise and NHWC -> planar in
             # one kernel (transforms.py:239-245), a quarter of the host-to-device bytes
             n_, h_, w_ = bufs['in'].shape[0], bufs['in'].shape[2], bufs['in'].shape[3]
+            if self._dev_resize is not None:                      # frames of any size, resized on the way (set_device_resize)
+                h_, w_ = x.shape[-3], x.shape[-2]
             assert x.shape[-1] == 3 and x.numel() == n_ * h_ * w_ * 3, "uint8 input must be (B[,K],H,W,3)"
-            xd = x.to(self.device).contiguous()
-            L.check(L.load().vd_preprocess_u8_nchw(xd.data_ptr(), bufs['in'].data_ptr(), n_, h_, w_, L.stream_ptr()),
-                    'vd_preprocess_u8_nchw')
+            self._preprocess_u8(x.to(self.device).contiguous(), bufs['in'], n_)
         else:
             bufs['in'].copy_(x.reshape(bufs['in'].shape))
+
+    def _preprocess_u8(self, xd, dst, n):
+        """n uint8 frames (..,H0,W0,3) on the device -> the first n rows of the NCHW input tensor `dst`, normalised: one
+        vd_preprocess_u8_nchw launch, or - device resize on and the frames not yet the size of dst - one vd_resize_u8_nchw
+        launch that resamples them on the way (its output is vd_preprocess_u8_nchw of the resized uint8 frames, bit for bit)"""
+        h, w = dst.shape[2], dst.shape[3]
+        h0, w0 = xd.shape[-3], xd.shape[-2]
+        if self._dev_resize is None or (h0, w0) == (h, w):       # (imresize returns a copy of a frame of the target size)
+            L.check(L.load().vd_preprocess_u8_nchw(xd.data_ptr(), dst.data_ptr(), n, h, w, L.stream_ptr()), 'vd_preprocess_u8_nchw')
+            return
+        t = self._resize_tables(h0, w0)
+        if t['dev'] is None:
+            t['dev'] = [torch.from_numpy(a).to(self.device) for a in t['host']]
+        iy, wy, ix, wx = t['dev']
+        L.check(L.load().vd_resize_u8_nchw(xd.data_ptr(), dst.data_ptr(), None, n, h0, w0, h, w, iy.data_ptr(), wy.data_ptr(),
+                                           iy.shape[1], ix.data_ptr(), wx.data_ptr(), ix.shape[1], L.stream_ptr()),
+                'vd_resize_u8_nchw')
 
     def _build_infer(self, B, H, W):
         bufs = self._buffers('infer', B, H, W, False)
@@ -2133,9 +2152,54 @@ class YOLOV3(object):
         """(B, H, W) of the image batch a call refers to (the no-backbone inputs are the stride-8/16/32 maps)."""
         if self.noback:
             return x[0].shape[0], x[0].shape[-2] * 8, x[0].shape[-1] * 8
+        if self._dev_resize is not None:            # raw (B[,K],H0,W0,3) frames, resized to the target on the device
+            if x.dtype != torch.uint8:
+                raise ValueError("set_device_resize is on: the network takes raw uint8 frames (B[,K],H0,W0,3); a float batch is "
+                                 "already normalised at its own size - switch it off with set_device_resize(None)")
+            self._resize_tables(x.shape[-3], x.shape[-2])
+            return x.shape[0], self._dev_resize[0], self._dev_resize[1]
         if x.dtype == torch.uint8:                  # (B[,K],H,W,3) frames, normalised on the device
             return x.shape[0], x.shape[-3], x.shape[-2]
         return x.shape[0], x.shape[-2], x.shape[-1]
+
+    def set_device_resize(self, width, height=None, interp=9):
+        """Resize raw uint8 frames to (height, width) on the device (vd_resize.hip); width None switches it off
+        (the default: every call behaves as without it).  On: uint8 inputs (B,H0,W0,3), (B,K,H0,W0,3) and detect_video's
+        (T,H0,W0,3) have any one source size per call and go through video.imresize's resample (interp 9: area when both axes
+        shrink, bicubic when both grow, bilinear otherwise) inside the kernel that normalises them; the plans are those of
+        the target size.  Float inputs are refused while it is on."""
+        if width is None:
+            self._dev_resize = None
+            return
+        if self.noback:
+            raise NotImplementedError("set_device_resize with noback: the no-backbone network takes cached feature maps, not "
+                                      "frames - there is nothing to resize")
+        width, height = int(width), int(width if height is None else height)
+        if width < 32 or height < 32 or width % 32 or height % 32:
+            raise ValueError("set_device_resize: width and height must be positive multiples of 32 (the network's stride), got "
+                             "width=%d height=%d" % (width, height))
+        from .video import resolve_interp
+        if resolve_interp(2, 2, 1, 1, interp) not in (1, 2, 3, 4):
+            raise ValueError("set_device_resize: interp %r is not a separable interpolation (1 bilinear, 2 area, 3 bicubic, "
+                             "4 Lanczos, 9 = by direction)" % (interp,))
+        self._dev_resize = (height, width, interp)
+
+    def _resize_tables(self, h0, w0):
+        """The tap tables of the (h0, w0) -> target resize, cached on the net per (H0, W0, H, W, interp): {'host': the four
+        arrays of video.resize_tables, 'dev': their uploads (made by the first launch that needs them)}.  Refuses, before
+        anything touches the GPU, a resize whose taps the kernel does not take."""
+        h, w, interp = self._dev_resize
+        key = (int(h0), int(w0), h, w, interp)
+        t = self._resize_cache.get(key)
+        if t is None:
+            from .video import resize_tables
+            tabs = resize_tables(key[0], key[1], h, w, interp)[1:]
+            ty, tx = tabs[0].shape[1], tabs[2].shape[1]
+            if ty > 16 or tx > 16:
+                raise ValueError("set_device_resize: a %dx%d -> %dx%d resize has Ty=%d / Tx=%d taps per output pixel, "
+                                 "vd_resize_u8_nchw takes at most 16 (area shrinking up to 15x)" % (key[0], key[1], h, w, ty, tx))
+            t = self._resize_cache[key] = dict(host=tabs, dev=None)
+        return t
 
     def _forward_infer(self, x):
         B, H, W = self._in_shape(x)
@@ -2292,9 +2356,7 @@ class YOLOV3(object):
         behind them repeat the last one (a padded row must hold real data: the fp32 operand scales are per tensor)"""
         n = b - a
         if frames.dtype == torch.uint8:
-            xd = frames[a:b].to(self.device).contiguous()
-            L.check(L.load().vd_preprocess_u8_nchw(xd.data_ptr(), dst.data_ptr(), n, dst.shape[2], dst.shape[3], L.stream_ptr()),
-                    'vd_preprocess_u8_nchw')
+            self._preprocess_u8(frames[a:b].to(self.device).contiguous(), dst, n)
         else:
             dst[:n].copy_(frames[a:b])
         if n < dst.shape[0]:

@@ -174,6 +174,27 @@ def _resample_axis(x, axis, idx, w):
     return out
 
 
+def resolve_interp(h0, w0, h, w, interp):
+    """interp 9 -> area (2) when both axes shrink, bicubic (3) when both enlarge, bilinear (1) otherwise; every other code
+    is returned as it is."""
+    if interp == 9:
+        return 2 if (h < h0 and w < w0) else (3 if (h > h0 and w > w0) else 1)
+    return interp
+
+
+def resize_tables(h0, w0, h, w, interp=9):
+    """The tap tables of an (h0,w0) -> (h,w) imresize in the form the device kernel takes (vd_resize_u8_nchw):
+    (interp_used, idx_y (h,Ty) int32, w_y (h,Ty) float32, idx_x (w,Tx) int32, w_x (w,Tx) float32), contiguous - `_axis_taps`
+    of each axis after interp 9 is resolved by imresize's rule, cast.  Separable interpolations only (1-4, 9)."""
+    interp = resolve_interp(h0, w0, h, w, interp)
+    if interp not in (1, 2, 3, 4):
+        raise ValueError("resize_tables: interp %r has no tap tables (1 bilinear, 2 area, 3 bicubic, 4 Lanczos, 9)" % (interp,))
+    iy, wy = _axis_taps(h0, h, interp)
+    ix, wx = _axis_taps(w0, w, interp)
+    return (interp, np.ascontiguousarray(iy, dtype=np.int32), np.ascontiguousarray(wy, dtype=np.float32),
+            np.ascontiguousarray(ix, dtype=np.int32), np.ascontiguousarray(wx, dtype=np.float32))
+
+
 def imresize(img, w, h, interp=1, rng=None):
     """(h0,w0,c) image -> (h,w,c).  interp: 0 nearest, 1 bilinear, 2 area, 3 bicubic, 4 Lanczos (8x8), 9 = area when
     shrinking, bicubic when enlarging, bilinear otherwise, 10 = one of 0-4 at random.  uint8 in -> uint8 out (rounded,
@@ -182,8 +203,7 @@ def imresize(img, w, h, interp=1, rng=None):
     h0, w0 = img.shape[:2]
     if interp == 10:
         interp = int((Rng() if rng is None else rng).np.randint(0, 5))
-    if interp == 9:
-        interp = 2 if (h < h0 and w < w0) else (3 if (h > h0 and w > w0) else 1)
+    interp = resolve_interp(h0, w0, h, w, interp)
     if (h, w) == (h0, w0):
         return img.copy()
     x = img.astype(np.float64)

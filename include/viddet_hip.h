@@ -590,6 +590,22 @@ int vd_temporal_cat_idx(const float* ring, const int32_t* slots, float* y, int S
 int vd_resize_u8_nchw(const uint8_t* in, float* out, uint8_t* out_u8, int N, int H0, int W0, int H, int W, const int32_t* idx_y,
                       const float* w_y, int Ty, const int32_t* idx_x, const float* w_x, int Tx, void* stream);
 
+/* ---- training augmentation on the device (vd_augment.hip): the pixels of colour distortion, expansion,
+ * crop, resize and flip in one launch, from decisions taken on the host.  raw: the uint8 frames of N samples, K frames
+ * [h0,w0,3] each, sample n at byte src_off[n] with (h0, w0) = src_hw[n]; frames n*K .. n*K+K-1 share record n.
+ * color [N][12] fp32: M (3x3 row-major) and b, level_c = sum_i x_i M[i][c] + b[c].  idx_y [N][H][Ty] int32 / w_y [N][H][Ty] fp32,
+ * idx_x [N][W][Tx] / w_x [N][W][Tx]: per-axis taps in SOURCE coordinates; an index < 0 is a tap on the canvas fill `fill[3]`,
+ * one >= the source's size is clamped into it (a bad table reads a wrong pixel of the sample's own frames, never memory outside
+ * them).  out [N*K,3,H,W] fp32, normalised as vd_preprocess_u8_nchw normalises, no rounding to uint8.  fp32 in a fixed order:
+ * horizontal taps 0 .. Tx-1 per source row then vertical taps 0 .. Ty-1 (fmaf from 0, fill taps skipped) give S[i]; per axis
+ * Wsrc = sum of source-tap weights, Wall = sum of all weights (adds from 0 in tap order), multiplied across the axes; then
+ * t = S[0]*M[0][c]; t = fmaf(S[1], M[1][c], t); t = fmaf(S[2], M[2][c], t); t = fmaf(b[c], Wsrc, t);
+ * t = fmaf(fill[c], Wall - Wsrc, t) - the colour affine once per output pixel.  1 <= Ty, Tx <= 32; all sizes >= 1; src_off
+ * 8-byte aligned, every other table and out 4-byte aligned.  No atomics, bit-reproducible. */
+int vd_augment_u8_nchw(const uint8_t* raw, const int64_t* src_off, const int32_t* src_hw, const float* color, const int32_t* idx_y,
+                       const float* w_y, int Ty, const int32_t* idx_x, const float* w_x, int Tx, const float* fill, float* out, int N,
+                       int K, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from viddet_amd import dist as vdist
+from viddet_amd.augment import augment_on_device
 from viddet_amd.data import (SyntheticDetection, MixupDetection, YOLO3VideoTrainTransform, YOLO3VideoInferenceTransform, Loader,
                              FeatureDataset, YOLO3NBVideoTrainTransform, YOLO3NBVideoInferenceTransform)
 from viddet_amd.metrics import VOCMApMetric, VOCMApMetricTemporal, LossMetric
@@ -113,10 +114,26 @@ def parse_flags(argv=None):
       help="(no reference counterpart) bf16: training activations and gradients in bf16, fp32 statistics / losses / master "
            "weights - net.set_storage('bf16'), BASELINE configs[4]; yolo3_darknet53 and its --window k > 1 variants (every join, neck "
            "and --corr_pos), not --temp / --mult_out / --features_dir")
+    A("--device_augment", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) the pixels of the training augmentation (colour distortion, expansion, crop, resize, flip, "
+           "normalisation) are computed on the GPU by vd_augment_u8_nchw from the raw uint8 frames; the draws, boxes and targets "
+           "stay on the host and are the ones the host path takes (DESIGN.md 21); not with --mixup / --features_dir")
     return ap.parse_args(argv)
 
 
 FLAGS = None
+
+
+def check_device_augment_flags(flags):
+    """--device_augment is refused by name, before any GPU work, beside the two flags whose input it cannot be"""
+    if not flags.device_augment:
+        return
+    if flags.mixup:
+        raise NotImplementedError("--device_augment does not combine with --mixup: MixupDetection blends float images on the host, "
+                                  "the device augmentation reads raw uint8 frames")
+    if flags.features_dir is not None:
+        raise NotImplementedError("--device_augment does not combine with --features_dir: cached features have no frames to "
+                                  "augment")
 
 
 def get_dataset(dataset_name, dataset_val_name, save_prefix=""):
@@ -152,10 +169,12 @@ def get_dataloader(train_dataset, val_dataset, data_shape, batch_size, rank, wor
                             last_batch="discard", rank=rank, world=world)
         return train_loader, val_loader
     rng = Rng.seeded(FLAGS.seed + rank)
+    dev = dict(device_augment=True) if FLAGS.device_augment else {}
     if FLAGS.no_random_shape:                          # :258-262
-        tf = YOLO3VideoTrainTransform(w, h, train_dataset.num_class, rng, mixup=FLAGS.mixup)
+        tf = YOLO3VideoTrainTransform(w, h, train_dataset.num_class, rng, mixup=FLAGS.mixup, **dev)
     else:                                              # :263-271 the default: a random side of 320 ... 608 every 10 batches
-        tf = [YOLO3VideoTrainTransform(x * 32, x * 32, train_dataset.num_class, rng, mixup=FLAGS.mixup) for x in range(10, 20)]
+        tf = [YOLO3VideoTrainTransform(x * 32, x * 32, train_dataset.num_class, rng, mixup=FLAGS.mixup, **dev)
+              for x in range(10, 20)]
     train_loader = Loader(train_dataset, tf, per_rank, train=True, shuffle=True, seed=FLAGS.seed, rank=rank, world=world,
                           interval=FLAGS.random_shape_interval, num_workers=FLAGS.num_workers)
     # validation frames travel as uint8 and are normalised on the device (same arithmetic, a quarter of the bytes)
@@ -329,7 +348,10 @@ def train(net, train_data, train_dataset, val_data, eval_metric, save_prefix, st
                 logger.info("Max epoch time of %d minutes reached after completing %d%% of epoch. "
                             "Moving on to next epoch" % (FLAGS.max_epoch_time, int(100 * (i / num_batches))))
                 break
-            dv = [torch.from_numpy(b).cuda() for b in batch]
+            if FLAGS.device_augment:                        # raw frames + records: the pixels are made on the device
+                dv = [augment_on_device(batch[0])] + [torch.from_numpy(b).cuda() for b in batch[1:]]
+            else:
+                dv = [torch.from_numpy(b).cuda() for b in batch]
             batch_size = dv[0].shape[0] * world
             if FLAGS.features_dir is not None:
                 # net(x1, x2, x3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)  (:595-617)
@@ -393,6 +415,7 @@ def main(argv=None):
     else:
         FLAGS.k_join_type = None
         FLAGS.k_join_pos = None
+    check_device_augment_flags(FLAGS)
     np.random.seed(FLAGS.seed)                          # gutils.random.seed (:697): numpy, python's random, the framework
     import random as _pyrandom
     _pyrandom.seed(FLAGS.seed)

@@ -12,7 +12,8 @@ import numpy as np
 
 from . import bbox as tbbox
 from .targets import prefetch_targets
-from .video import Rng, imresize, random_color_distort, random_expand
+from .augment import AugmentBatch, AugmentRecord, augment_record, check_source_size
+from .video import Rng, color_distort_params, expand_params, imresize, random_color_distort, random_expand
 
 NUM_CLASSES = {"voc": 20, "coco": 80, "det": 200, "vid": 30, "comb": 285, "synthetic": 20}
 MEAN = np.array([0.485, 0.456, 0.406], np.float32)     # transforms.py:167
@@ -221,9 +222,15 @@ class YOLO3VideoTrainTransform:
     constrained random crop, resize with a random interpolation (0-4), random horizontal flip (0.5), to_tensor +
     normalise, then the prefetch targets (:252-294).  One set of decisions per sample: every frame of a window gets the
     same distortion / crop / flip.  `rng`: viddet_amd.video.Rng (numpy + python generators; default = a private pair
-    seeded with 0; Rng() = the global modules, exactly the reference's sources)."""
+    seeded with 0; Rng() = the global modules, exactly the reference's sources).
 
-    def __init__(self, width, height, num_class, rng=None, augment=True, device_normalize=False, mixup=False):
+    device_augment=True (no reference counterpart) takes the same decisions from the same draws in the same
+    order - boxes, targets and the generators' final state are those of the host path - but touches no pixel: in place of the
+    pixel column it returns the untouched uint8 frames and a viddet_amd.augment.AugmentRecord (colour affine, tap tables in
+    source coordinates, canvas fill), which Loader collates into an AugmentBatch for augment_on_device."""
+
+    def __init__(self, width, height, num_class, rng=None, augment=True, device_normalize=False, mixup=False,
+                 device_augment=False):
         """mixup (transforms.py:166,264-270): the labels carry a last column of mix ratios (MixupDetection), which goes to
         the target generator as gt_mixratio -> the objectness target (yolo_target.py:124-125).  The class id is column 4,
         as in gluoncv's YOLO3DefaultTrainTransform, which this transform was derived from: the reference's own test
@@ -236,8 +243,42 @@ class YOLO3VideoTrainTransform:
         elif isinstance(rng, np.random.Generator):             # an older call form: derive the pair from the generator
             rng = Rng.seeded(int(rng.integers(0, 2 ** 31 - 1)))
         self._rng, self._augment, self._u8 = rng, augment, device_normalize
+        self._dev = bool(device_augment)
+        if self._dev and (device_normalize or mixup):
+            raise ValueError("device_augment=True returns raw frames and a record: it does not combine with "
+                             "device_normalize=True (rounded uint8 pixels) or mixup=True (MixupDetection blends float images on "
+                             "the host)")
+
+    def _decide(self, img, label):
+        """device_augment: the draws of __call__ in its order, without pixels -> (frames, record, boxes)."""
+        rng = self._rng
+        frames = np.asarray(img, dtype=np.uint8)
+        h0, w0 = frames.shape[-3], frames.shape[-2]
+        check_source_size(h0, w0, self._h, self._w)
+        bb = label
+        ops, expand, crop = [], None, None
+        h, w = h0, w0
+        if self._augment:
+            ops = color_distort_params(rng)
+            if rng.np.uniform(0, 1) > 0.5:
+                expand = expand_params(h0, w0, rng)
+                bb = tbbox.translate(bb, x_offset=expand[0], y_offset=expand[1])
+                w, h = expand[2], expand[3]
+            bb, crop = tbbox.random_crop_with_constraints(bb, (w, h), py_rng=rng.py, np_rng=rng.np)
+            w, h = int(crop[2]), int(crop[3])
+        interp = int(rng.np.randint(0, 5)) if self._augment else 1
+        bb = tbbox.resize(bb, (w, h), (self._w, self._h))
+        flip = bool(rng.np.uniform(0, 1) > 0.5)
+        if flip:
+            bb = tbbox.flip(bb, (self._w, self._h), flip_x=True)
+        rec = augment_record(h0, w0, self._h, self._w, ops=ops, expand=expand, crop=crop, interp=interp, flip=flip,
+                             fill=[m * 255 for m in MEAN], window=frames.ndim == 4)
+        return frames, rec, bb
 
     def __call__(self, img, label):
+        if self._dev:
+            frames, rec, bb = self._decide(img, label)
+            return (frames, rec) + self._targets(bb)
         rng = self._rng
         frames = (img if img.ndim == 4 else img[np.newaxis])
         bb = label
@@ -263,6 +304,10 @@ class YOLO3VideoTrainTransform:
             x = np.stack([_to_tensor_normalize(im) for im in ims])
         if img.ndim != 4:
             x = x[0]
+        return (x,) + self._targets(bb)
+
+    def _targets(self, bb):
+        """the five target columns and gt of the transformed boxes"""
         bboxs = list(bb) if isinstance(bb, (list, tuple)) else [bb]       # the crop returns a list of per-frame arrays
         if len(bboxs) > 1:
             # per-frame labels (--mult_out, transforms.py:252-294): targets of every frame stacked on a leading t axis,
@@ -271,13 +316,13 @@ class YOLO3VideoTrainTransform:
                                    b[np.newaxis, :, -1:] if self._mixup else None) for b in bboxs]
             cols = [np.concatenate([t[i] for t in tg], axis=0) for i in range(5)]
             gt = pad_stack([np.asarray(b[:, :4], dtype=np.float32) for b in bboxs])
-            return (x,) + tuple(cols) + (gt,)
+            return tuple(cols) + (gt,)
         b0 = np.asarray(bboxs[0])                                         # :269-271 one label set: un-stacked targets
         gt = b0[np.newaxis, :, :4]
         ids = b0[np.newaxis, :, 4:5]
         obj, ctr, scl, wgt, cls = prefetch_targets(self._h, self._w, gt, ids, self._c,
                                                    b0[np.newaxis, :, -1:] if self._mixup else None)
-        return x, obj[0], ctr[0], scl[0], wgt[0], cls[0], gt[0].astype(np.float32)
+        return obj[0], ctr[0], scl[0], wgt[0], cls[0], gt[0].astype(np.float32)
 
 
 def feature_file_id(img_path):
@@ -398,6 +443,11 @@ class Loader:
 
     def _collate(self, samples):
         cols = list(zip(*samples))
+        if self.train and len(cols) > 1 and isinstance(cols[1][0], AugmentRecord):
+            # device_augment: the raw frames and their records become ONE batch object in the pixel column's place
+            cols = [None] + cols[2:]
+            return [AugmentBatch([s[0] for s in samples], [s[1] for s in samples])] + \
+                   [np.stack(c) for c in cols[1:-1]] + [pad_stack(cols[-1])]
         if self.train:
             # Stack every column, Pad(-1) the trailing gt boxes (train_yolov3.py:238 / :252: 8+1 columns with
             # cached features, 6+1 with frames)

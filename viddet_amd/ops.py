@@ -429,6 +429,12 @@ def preprocess_u8(x_u8, out):
     check(_lib().vd_preprocess_u8_nhwc(ptr(x_u8), ptr(out), x_u8.numel() // 3, _s()), "vd_preprocess_u8_nhwc")
 
 
+def augment_u8_nchw(raw, src_off, src_hw, color, idx_y, w_y, Ty, idx_x, w_x, Tx, fill, out, N, K, H, W):
+    """vd_augment_u8_nchw; every array argument is a device tensor (the sections of viddet_amd.augment's packed upload)"""
+    check(_lib().vd_augment_u8_nchw(ptr(raw), ptr(src_off), ptr(src_hw), ptr(color), ptr(idx_y), ptr(w_y), Ty, ptr(idx_x), ptr(w_x),
+                                    Tx, ptr(fill), ptr(out), N, K, H, W, _s()), "vd_augment_u8_nchw")
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

@@ -34,19 +34,26 @@ class Rng:
         return cls(np.random.RandomState(seed), _pyrandom.Random(seed))
 
 
-def random_expand(src, max_ratio=4, fill=0, keep_ratio=True, rng=None):
-    """video.py:12-65: place the (k,h,w,c) frames on a larger canvas filled with `fill`.
-    Returns (canvas, (offset_x, offset_y, new_width, new_height)).  Draws: random.uniform(1, max_ratio)
-    [, a second one if not keep_ratio], random.randint(0, oh - h), random.randint(0, ow - w)."""
+def expand_params(h, w, rng=None, max_ratio=4, keep_ratio=True):
+    """The decisions of `random_expand` for (h,w) frames, without pixels: (offset_x, offset_y, new_width, new_height).
+    Draws: random.uniform(1, max_ratio) [, a second one if not keep_ratio], random.randint(0, oh - h),
+    random.randint(0, ow - w)."""
     rng = Rng() if rng is None else rng
-    if max_ratio <= 1:
-        return src, (0, 0, src.shape[1], src.shape[0])          # (:39-40, the reference's own index slip kept)
-    k, h, w, c = src.shape
     ratio_x = rng.py.uniform(1, max_ratio)
     ratio_y = ratio_x if keep_ratio else rng.py.uniform(1, max_ratio)
     oh, ow = int(h * ratio_y), int(w * ratio_x)
     off_y = rng.py.randint(0, oh - h)
     off_x = rng.py.randint(0, ow - w)
+    return off_x, off_y, ow, oh
+
+
+def random_expand(src, max_ratio=4, fill=0, keep_ratio=True, rng=None):
+    """video.py:12-65: place the (k,h,w,c) frames on a larger canvas filled with `fill`.
+    Returns (canvas, (offset_x, offset_y, new_width, new_height)).  Draws: those of `expand_params`."""
+    if max_ratio <= 1:
+        return src, (0, 0, src.shape[1], src.shape[0])          # (:39-40, the reference's own index slip kept)
+    k, h, w, c = src.shape
+    off_x, off_y, ow, oh = expand_params(h, w, rng, max_ratio, keep_ratio)
     if np.isscalar(fill):
         dst = np.full((k, oh, ow, c), fill, dtype=src.dtype)
     else:
@@ -69,43 +76,89 @@ def hue_matrix(alpha):
     return np.dot(np.dot(_ITYIQ, bt), _TYIQ).T
 
 
+_GRAY = (0.299, 0.587, 0.114)
+
+
+def color_distort_params(rng=None, brightness_delta=32, contrast_low=0.5, contrast_high=1.5, saturation_low=0.5,
+                         saturation_high=1.5, hue_delta=18):
+    """The decisions of `random_color_distort`, without pixels: the operations that were drawn, in the order they apply, as
+    [(name, parameter)] - ('brightness', float32 delta), ('contrast', float32 factor), ('saturation', float32 factor),
+    ('hue', python float angle).  Draw order: brightness gate (np.uniform) [+ delta], order coin (np.randint(0, 2)), then
+    contrast / saturation / hue - or saturation / hue / contrast - each a gate (np.uniform(0, 1) > 0.5) followed, if taken, by
+    its parameter (np.uniform; the hue angle from random.uniform)."""
+    rng = Rng() if rng is None else rng
+    ops = []
+
+    def brightness():
+        if rng.np.uniform(0, 1) > 0.5:
+            ops.append(("brightness", np.float32(rng.np.uniform(-brightness_delta, brightness_delta))))
+
+    def contrast():
+        if rng.np.uniform(0, 1) > 0.5:
+            ops.append(("contrast", np.float32(rng.np.uniform(contrast_low, contrast_high))))
+
+    def saturation():
+        if rng.np.uniform(0, 1) > 0.5:
+            ops.append(("saturation", np.float32(rng.np.uniform(saturation_low, saturation_high))))
+
+    def hue():
+        if rng.np.uniform(0, 1) > 0.5:
+            ops.append(("hue", rng.py.uniform(-hue_delta, hue_delta)))
+
+    brightness()
+    if rng.np.randint(0, 2):
+        contrast(), saturation(), hue()
+    else:
+        saturation(), hue(), contrast()
+    return ops
+
+
+def apply_color_ops(src, ops):
+    """The float32 arithmetic of video.py:68-158 for a list of `color_distort_params` operations."""
+    x = np.asarray(src).astype(np.float32)
+    for name, p in ops:
+        if name == "brightness":
+            x = x + p
+        elif name == "contrast":
+            x = x * p
+        elif name == "saturation":
+            gray = (x * np.array(_GRAY, np.float32)).sum(axis=-1, keepdims=True)
+            x = x * p + gray * (np.float32(1.0) - p)
+        elif name == "hue":
+            x = np.dot(x, hue_matrix(p).astype(np.float32))
+        else:
+            raise ValueError("colour operation %r" % (name,))
+    return x.astype(np.float32)
+
+
+def color_affine(ops):
+    """The operations of `color_distort_params` composed into one affine map of RGB, in fp64: (M (3,3), b (3,)) with
+    out_c = sum_i x_i M[i][c] + b[c].  Each operation is affine (brightness x + d, contrast x * a, saturation
+    x * a + gray * (1 - a), hue x . hue_matrix(alpha)), with the float32 parameters `apply_color_ops` uses."""
+    M, b = np.eye(3), np.zeros(3)
+    for name, p in ops:
+        if name == "brightness":
+            b = b + float(p)
+            continue
+        if name == "contrast":
+            A = np.eye(3) * float(p)
+        elif name == "saturation":
+            g = np.array(_GRAY, np.float32).astype(np.float64)
+            A = np.eye(3) * float(p) + np.outer(g, np.ones(3)) * float(np.float32(1.0) - p)
+        elif name == "hue":
+            A = hue_matrix(p).astype(np.float32).astype(np.float64)
+        else:
+            raise ValueError("colour operation %r" % (name,))
+        M, b = M @ A, b @ A
+    return M, b
+
+
 def random_color_distort(src, brightness_delta=32, contrast_low=0.5, contrast_high=1.5, saturation_low=0.5,
                          saturation_high=1.5, hue_delta=18, rng=None):
-    """video.py:68-158 on frames in [0, 255]; returns float32.  Draw order: brightness gate (np.uniform) [+ delta],
-    order coin (np.randint(0, 2)), then contrast / saturation / hue - or saturation / hue / contrast - each a gate
-    (np.uniform(0, 1) > 0.5) followed, if taken, by its parameter (np.uniform; the hue angle from random.uniform)."""
-    rng = Rng() if rng is None else rng
-    src = np.asarray(src).astype(np.float32)
-
-    def brightness(x):
-        if rng.np.uniform(0, 1) > 0.5:
-            x = x + np.float32(rng.np.uniform(-brightness_delta, brightness_delta))
-        return x
-
-    def contrast(x):
-        if rng.np.uniform(0, 1) > 0.5:
-            x = x * np.float32(rng.np.uniform(contrast_low, contrast_high))
-        return x
-
-    def saturation(x):
-        if rng.np.uniform(0, 1) > 0.5:
-            alpha = np.float32(rng.np.uniform(saturation_low, saturation_high))
-            gray = (x * np.array([0.299, 0.587, 0.114], np.float32)).sum(axis=-1, keepdims=True)
-            x = x * alpha + gray * (np.float32(1.0) - alpha)
-        return x
-
-    def hue(x):
-        if rng.np.uniform(0, 1) > 0.5:
-            alpha = rng.py.uniform(-hue_delta, hue_delta)
-            x = np.dot(x, hue_matrix(alpha).astype(np.float32))
-        return x
-
-    src = brightness(src)
-    if rng.np.randint(0, 2):
-        src = hue(saturation(contrast(src)))
-    else:
-        src = contrast(hue(saturation(src)))
-    return src.astype(np.float32)
+    """video.py:68-158 on frames in [0, 255]; returns float32.  Draws: those of `color_distort_params` (no draw depends on a
+    pixel, so they are all taken first)."""
+    ops = color_distort_params(rng, brightness_delta, contrast_low, contrast_high, saturation_low, saturation_high, hue_delta)
+    return apply_color_ops(src, ops)
 
 
 # --------------------------------------------------------------------------------------------

@@ -606,6 +606,21 @@ int vd_augment_u8_nchw(const uint8_t* raw, const int64_t* src_off, const int32_t
                        const float* w_y, int Ty, const int32_t* idx_x, const float* w_x, int Tx, const float* fill, float* out, int N,
                        int K, int H, int W, void* stream);
 
+/* ---- YOLO training targets on the device (vd_targets.hip): viddet_amd/targets.py::prefetch_targets in two
+ * launches, from the label rows alone.  gt [N][M][4] fp32 corner boxes, rows padded with -1; ids [N][M][idw] fp32, idw = 1 a
+ * class index, idw = C a multi-hot row; mix [N][M] mixup ratios (the objectness target) or NULL (1).  Outputs, fp32, EVERY
+ * element written on every call: obj [N][P][1], ctr [N][P][2], scl [N][P][2], wgt [N][P][2] (default 0) and cls [N][P][C]
+ * (default -1), P = 3 * sum over strides 32, 16, 8 of (H/s)(W/s), row = the stride-32 layer first, (y*w + x)*3 + a inside a
+ * layer.  Per gt: width, height and centre x0 + w/2 in fp32, then fp64 without FMA contraction - shape IoU against the nine
+ * anchors (inter / union, 0 where union <= 0, first maximum wins), fx = gx / W * w_layer, lx = (int)fx, ctr = fx - lx,
+ * scl = log(max(gw, 1) / anchor), wgt = 2 - gw*gh / W / H; bit-equal to the host except log().  A row is valid if all four
+ * coordinates are >= 0 (NaN is not); an image's rows END at its first invalid row; of two gts on one row p the later one wins
+ * every column, its whole class row included; a gt whose p lies outside [0, P) is dropped (fx, fy are clamped before the cast:
+ * no input stores out of bounds); a class index outside [0, C) writes no 1.  N, M, C >= 1; M <= 512; H, W multiples of 32;
+ * idw in {1, C}; every pointer 4-byte aligned.  No atomics, bit-reproducible. */
+int vd_yolo_targets(const float* gt, const float* ids, int idw, const float* mix, int N, int M, int C, int H, int W, float* obj,
+                    float* ctr, float* scl, float* wgt, float* cls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

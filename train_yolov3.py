@@ -33,6 +33,7 @@ import torch
 
 from viddet_amd import dist as vdist
 from viddet_amd.augment import augment_on_device
+from viddet_amd.device_targets import targets_on_device
 from viddet_amd.data import (SyntheticDetection, MixupDetection, YOLO3VideoTrainTransform, YOLO3VideoInferenceTransform, Loader,
                              FeatureDataset, YOLO3NBVideoTrainTransform, YOLO3NBVideoInferenceTransform)
 from viddet_amd.metrics import VOCMApMetric, VOCMApMetricTemporal, LossMetric
@@ -118,6 +119,10 @@ def parse_flags(argv=None):
       help="(no reference counterpart) the pixels of the training augmentation (colour distortion, expansion, crop, resize, flip, "
            "normalisation) are computed on the GPU by vd_augment_u8_nchw from the raw uint8 frames; the draws, boxes and targets "
            "stay on the host and are the ones the host path takes (DESIGN.md 21); not with --mixup / --features_dir")
+    A("--device_targets", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) the dense prefetch targets (objectness, centre, scale, weight, class) are written on the GPU "
+           "by vd_yolo_targets from the transformed boxes: a sample carries its (M,5) label rows, not five (P,.) tensors, through "
+           "the workers and over PCIe (DESIGN.md 22); the targets are the host path's")
     return ap.parse_args(argv)
 
 
@@ -162,14 +167,15 @@ def get_dataloader(train_dataset, val_dataset, data_shape, batch_size, rank, wor
     """train_yolov3.py:234-286; per-rank batch = batch_size / world (split_and_load, :603-606)."""
     w = h = data_shape
     per_rank = batch_size // world
+    tgt = dict(device_targets=True) if FLAGS.device_targets else {}
     if FLAGS.features_dir is not None:                 # :238-250 the input is pre-saved features
-        train_loader = Loader(train_dataset, YOLO3NBVideoTrainTransform(FLAGS.window[0], w, h, train_dataset.num_class),
+        train_loader = Loader(train_dataset, YOLO3NBVideoTrainTransform(FLAGS.window[0], w, h, train_dataset.num_class, **tgt),
                               per_rank, train=True, shuffle=True, seed=FLAGS.seed, rank=rank, world=world)
         val_loader = Loader(val_dataset, YOLO3NBVideoInferenceTransform(w, h), per_rank, train=False,
                             last_batch="discard", rank=rank, world=world)
         return train_loader, val_loader
     rng = Rng.seeded(FLAGS.seed + rank)
-    dev = dict(device_augment=True) if FLAGS.device_augment else {}
+    dev = dict(tgt, device_augment=True) if FLAGS.device_augment else tgt
     if FLAGS.no_random_shape:                          # :258-262
         tf = YOLO3VideoTrainTransform(w, h, train_dataset.num_class, rng, mixup=FLAGS.mixup, **dev)
     else:                                              # :263-271 the default: a random side of 320 ... 608 every 10 batches
@@ -348,10 +354,16 @@ def train(net, train_data, train_dataset, val_data, eval_metric, save_prefix, st
                 logger.info("Max epoch time of %d minutes reached after completing %d%% of epoch. "
                             "Moving on to next epoch" % (FLAGS.max_epoch_time, int(100 * (i / num_batches))))
                 break
+            if FLAGS.device_targets:                        # the last column is the label rows: the targets are made on the device
+                batch, labels = batch[:-1], batch[-1]
             if FLAGS.device_augment:                        # raw frames + records: the pixels are made on the device
                 dv = [augment_on_device(batch[0])] + [torch.from_numpy(b).cuda() for b in batch[1:]]
             else:
                 dv = [torch.from_numpy(b).cuda() for b in batch]
+            if FLAGS.device_targets:                        # the same columns in the same places: data, five targets, gt
+                th, tw = (FLAGS.data_shape,) * 2 if FLAGS.features_dir is not None else dv[0].shape[-2:]
+                tg = targets_on_device(labels, int(th), int(tw), train_dataset.num_class)
+                dv = dv + list(tg[1:]) + [tg[0]]
             batch_size = dv[0].shape[0] * world
             if FLAGS.features_dir is not None:
                 # net(x1, x2, x3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)  (:595-617)

@@ -13,6 +13,7 @@ import numpy as np
 from . import bbox as tbbox
 from .targets import prefetch_targets
 from .augment import AugmentBatch, AugmentRecord, augment_record, check_source_size
+from .device_targets import label_column
 from .video import Rng, color_distort_params, expand_params, imresize, random_color_distort, random_expand
 
 NUM_CLASSES = {"voc": 20, "coco": 80, "det": 200, "vid": 30, "comb": 285, "synthetic": 20}
@@ -227,10 +228,16 @@ class YOLO3VideoTrainTransform:
     device_augment=True (no reference counterpart) takes the same decisions from the same draws in the same
     order - boxes, targets and the generators' final state are those of the host path - but touches no pixel: in place of the
     pixel column it returns the untouched uint8 frames and a viddet_amd.augment.AugmentRecord (colour affine, tap tables in
-    source coordinates, canvas fill), which Loader collates into an AugmentBatch for augment_on_device."""
+    source coordinates, canvas fill), which Loader collates into an AugmentBatch for augment_on_device.
+
+    device_targets=True (no reference counterpart) takes the same draws and computes the same boxes, but does
+    not run prefetch_targets: in place of the five target columns and the gt column the sample ends in ONE label column, the
+    transformed boxes as fp32 (M,5) `x1, y1, x2, y2, id` rows ((M,6) with the mix ratio last under mixup=True; (t,M,.), padded
+    with -1 per frame, for per-frame labels), which Loader pads like the gt column and
+    viddet_amd.device_targets.targets_on_device turns into the same six tensors on the device."""
 
     def __init__(self, width, height, num_class, rng=None, augment=True, device_normalize=False, mixup=False,
-                 device_augment=False):
+                 device_augment=False, device_targets=False):
         """mixup (transforms.py:166,264-270): the labels carry a last column of mix ratios (MixupDetection), which goes to
         the target generator as gt_mixratio -> the objectness target (yolo_target.py:124-125).  The class id is column 4,
         as in gluoncv's YOLO3DefaultTrainTransform, which this transform was derived from: the reference's own test
@@ -243,7 +250,7 @@ class YOLO3VideoTrainTransform:
         elif isinstance(rng, np.random.Generator):             # an older call form: derive the pair from the generator
             rng = Rng.seeded(int(rng.integers(0, 2 ** 31 - 1)))
         self._rng, self._augment, self._u8 = rng, augment, device_normalize
-        self._dev = bool(device_augment)
+        self._dev, self._dt = bool(device_augment), bool(device_targets)
         if self._dev and (device_normalize or mixup):
             raise ValueError("device_augment=True returns raw frames and a record: it does not combine with "
                              "device_normalize=True (rounded uint8 pixels) or mixup=True (MixupDetection blends float images on "
@@ -309,6 +316,9 @@ class YOLO3VideoTrainTransform:
     def _targets(self, bb):
         """the five target columns and gt of the transformed boxes"""
         bboxs = list(bb) if isinstance(bb, (list, tuple)) else [bb]       # the crop returns a list of per-frame arrays
+        if self._dt:                                                      # device_targets: the label rows alone
+            labs = [label_column(b, self._mixup) for b in bboxs]
+            return (pad_stack(labs) if len(labs) > 1 else labs[0],)
         if len(bboxs) > 1:
             # per-frame labels (--mult_out, transforms.py:252-294): targets of every frame stacked on a leading t axis,
             # gt boxes (t, M, 4) padded with -1
@@ -356,14 +366,17 @@ class FeatureDataset:
 
 class YOLO3NBVideoTrainTransform:
     """transforms.py:353-428: the frames are only used for their size; boxes are resized to the network input and
-    the prefetch targets are generated on the host; the cached features pass through."""
+    the prefetch targets are generated on the host; the cached features pass through.  device_targets=True:
+    the resized boxes travel as one fp32 (M,5) label column in place of the five target columns and gt."""
 
-    def __init__(self, k, width, height, num_class):
-        self._k, self._w, self._h, self._c = k, width, height, num_class
+    def __init__(self, k, width, height, num_class, device_targets=False):
+        self._k, self._w, self._h, self._c, self._dt = k, width, height, num_class, bool(device_targets)
 
     def __call__(self, img, f1, f2, f3, label):
         h, w = img.shape[-3], img.shape[-2]                       # (h,w,c) or (k,h,w,c)  (transforms.py:399-402)
         bb = tbbox.resize(label, (w, h), (self._w, self._h))
+        if self._dt:
+            return f1, f2, f3, label_column(bb)
         gt = bb[np.newaxis, :, :4]
         ids = bb[np.newaxis, :, 4:5]
         obj, ctr, scl, wgt, cls = prefetch_targets(self._h, self._w, gt, ids, self._c)

@@ -171,6 +171,8 @@ SIGNATURES = {
     "vd_resize_u8_nchw": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p]),
     # the pixels of the training augmentation on the device (vd_augment.hip)
     "vd_augment_u8_nchw": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p]),
+    # the prefetch targets of a training batch on the device (vd_targets.hip)
+    "vd_yolo_targets": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -435,6 +435,13 @@ def augment_u8_nchw(raw, src_off, src_hw, color, idx_y, w_y, Ty, idx_x, w_x, Tx,
                                     Tx, ptr(fill), ptr(out), N, K, H, W, _s()), "vd_augment_u8_nchw")
 
 
+def yolo_targets(gt, ids, idw, mix, N, M, C, H, W, obj, ctr, scl, wgt, cls):
+    """vd_yolo_targets: gt (N,M,4), ids (N,M,idw) and mix (N,M) or None are device tensors (fp32); the five outputs are written
+    whole (they may be uninitialised)"""
+    check(_lib().vd_yolo_targets(ptr(gt), ptr(ids), idw, ptr(mix), N, M, C, H, W, ptr(obj), ptr(ctr), ptr(scl), ptr(wgt),
+                                 ptr(cls), _s()), "vd_yolo_targets")
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

@@ -83,6 +83,12 @@ def parse_flags(argv=None):
            "device, inside the kernel that normalises them (net.set_device_resize): the host's imresize leaves the per-frame "
            "path; predictions differ from the host-resized run only where the fp32 resample rounds a grey level the other "
            "way (DESIGN.md 20)")
+    A("--frame_format", default="rgb", choices=["rgb", "nv12"],
+      help="(no reference counterpart) nv12: the frames are NV12, as video decoders hand them out - a luma plane and a "
+           "half-resolution plane of interleaved chroma pairs, (H0*3/2,W0) uint8 - and are converted to RGB inside the kernel "
+           "that resizes them (net.set_device_resize(source='nv12')); needs --device_resize (DESIGN.md 23)")
+    A("--yuv_matrix", default="bt601", choices=["bt601", "bt709"], help="the colour matrix of --frame_format nv12")
+    A("--yuv_range", default="limited", choices=["limited", "full"], help="the range of --frame_format nv12")
     A("--synthetic_videos", type=int, default=None,
       help="(no reference counterpart) the dataset is SyntheticVideo: this many clips of --synthetic_samples frames each, "
            "windows by --window K,step inside a clip (default with --stream: 2; without --stream the windowed path runs on it)")
@@ -122,11 +128,13 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None):
     return boxes
 
 
-def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False):
+def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb"):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
-    the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size."""
+    the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
+    'nv12': as NV12 frames)."""
     net.set_nms(nms_thresh=0.45, nms_topk=400)
-    tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize)
+    tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
+                                      frame_format=frame_format)
     boxes = dict()
     if max_do < 0:
         max_do = len(dataset)
@@ -183,6 +191,13 @@ def check_flags(FLAGS):
     if FLAGS.model_agnostic and FLAGS.rnn_pos == "out":
         raise NotImplementedError("--model_agnostic with --rnn_pos out: the RNN output block is a tail of its own that is not "
                                   "built agnostic")
+    if getattr(FLAGS, "frame_format", "rgb") == "nv12":
+        if not getattr(FLAGS, "device_resize", False):
+            raise NotImplementedError("--frame_format nv12 needs --device_resize: NV12 frames are converted inside the kernel "
+                                      "that resizes them, the host resize has no NV12 path")
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--frame_format nv12 does not combine with several --dataset names: the combined set's "
+                                      "path is left on the host resize")
     if getattr(FLAGS, "device_resize", False) and len(FLAGS.dataset) > 1:
         raise NotImplementedError("--device_resize does not combine with several --dataset names: the combined set's path is "
                                   "left on the host resize")
@@ -240,6 +255,8 @@ def load_predictions(save_dir, dataset, max_do=-1):
 def evaluate(metrics, dataset, predictions, data_shape):
     """detect_yolo3.py:659-695: feed saved predictions and (resized, normalised) ground truth to the metrics."""
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape)
+    if getattr(dataset, "frame_format", "rgb") == "nv12":      # only the resized boxes are used: the NV12 frames pass through
+        tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=True, frame_format="nv12")
     for idx in range(len(dataset)):
         img, label = dataset[idx]
         _, gt, _ = tf(img, label, idx)
@@ -261,20 +278,22 @@ def main(argv=None):
         raise SystemExit("detect_yolo3.py needs an MI355X: the HIP path has no CPU fallback")
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     name = FLAGS.dataset[0]
+    # --frame_format nv12: the synthetic sets hand out their frames as a decoder would (video.rgb_to_nv12)
+    fmt = dict(frame_format="nv12", yuv_matrix=FLAGS.yuv_matrix, yuv_range=FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else {}
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
     elif FLAGS.stream or FLAGS.synthetic_videos is not None:
         # clips: --synthetic_videos of them (given, or 2 with --stream), --synthetic_samples frames each, windows by --window K,step
         dataset = SyntheticVideo(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
                                  frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
-                                 step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1)
+                                 step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1, **fmt)
     else:
         # --window k: a sample is the k-frame window around the frame the rows belong to (as train_yolov3.py's sets)
-        dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples, window=FLAGS.window[0])
+        dataset = SyntheticDetection(name, num_samples=FLAGS.synthetic_samples, window=FLAGS.window[0], **fmt)
     # frames travel as uint8 and are normalised on the device (vd_preprocess_u8_nchw: the transform's own arithmetic)
-    # (--device_resize: at their source size, resized there too - vd_resize_u8_nchw)
+    # (--device_resize: at their source size, resized there too - vd_resize_u8_nchw, NV12 frames vd_resize_nv12_nchw)
     loader = Loader(dataset, YOLO3VideoInferenceTransform(FLAGS.data_shape, FLAGS.data_shape, device_normalize=True,
-                                                          device_resize=FLAGS.device_resize),
+                                                          device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format),
                     FLAGS.batch_size, train=False, last_batch="keep", rank=rank, world=world)
     # detect_yolo3.py:871-892
     if ct is not None:
@@ -289,12 +308,14 @@ def main(argv=None):
     else:
         net.load_parameters(FLAGS.model_path)
     net.set_precision(FLAGS.precision)
-    if FLAGS.device_resize:
+    if FLAGS.device_resize and FLAGS.frame_format == "nv12":
+        net.set_device_resize(FLAGS.data_shape, FLAGS.data_shape, source="nv12", matrix=FLAGS.yuv_matrix, range=FLAGS.yuv_range)
+    elif FLAGS.device_resize:
         net.set_device_resize(FLAGS.data_shape, FLAGS.data_shape)
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic)
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
-                              FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize)
+                              FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None)
     if world > 1:

@@ -590,6 +590,22 @@ int vd_temporal_cat_idx(const float* ring, const int32_t* slots, float* y, int S
 int vd_resize_u8_nchw(const uint8_t* in, float* out, uint8_t* out_u8, int N, int H0, int W0, int H, int W, const int32_t* idx_y,
                       const float* w_y, int Ty, const int32_t* idx_x, const float* w_x, int Tx, void* stream);
 
+/* ---- the same resize on NV12 frames (vd_resize.hip): what video decoders hand out.  A frame starts every
+ * `frame_stride` bytes of `in`: H0 rows of luma Y, and from `uv_offset` bytes into the frame H0/2 rows of interleaved chroma
+ * pairs U V (one pair per 2 x 2 block), `pitch` bytes from row to row in both planes.  Pixel (y, x) takes the pair (y >> 1,
+ * x >> 1) (nearest chroma); C = Y - off, D = U - 128, E = V - 128 and in int32
+ *   R = clip((gain*C + ru*D + rv*E + 128) >> 8, 0, 255), G with (gu, gv), B with (bu, 0)
+ * - an arithmetic (floor) shift, then the clip: viddet_amd/video.py nv12_to_rgb with the seven integers of its NV12_MATRICES
+ * entry.  Everything behind the conversion is vd_resize_u8_nchw: out / out_u8 are bit-equal to that entry point on
+ * nv12_to_rgb of the frames.  H0, W0 even; W0 <= pitch < 2^31; uv_offset >= pitch * H0; uv_offset + pitch * H0 / 2 <=
+ * frame_stride < 2^40; in_bytes >= (N - 1) * frame_stride + uv_offset + pitch * (H0 / 2 - 1) + W0 (the last chroma byte of the
+ * last frame: no slack, padding or whole last pitch need exist behind it).  No byte outside [in, in + in_bytes) is read,
+ * whatever the tables hold; `in` needs no alignment.  Otherwise as vd_resize_u8_nchw.  No atomics, bit-reproducible. */
+int vd_resize_nv12_nchw(const uint8_t* in, int64_t in_bytes, int64_t frame_stride, int64_t pitch, int64_t uv_offset, float* out,
+                        uint8_t* out_u8, int N, int H0, int W0, int H, int W, const int32_t* idx_y, const float* w_y, int Ty,
+                        const int32_t* idx_x, const float* w_x, int Tx, int off, int gain, int ru, int rv, int gu, int gv, int bu,
+                        void* stream);
+
 /* ---- training augmentation on the device (vd_augment.hip): the pixels of colour distortion, expansion,
  * crop, resize and flip in one launch, from decisions taken on the host.  raw: the uint8 frames of N samples, K frames
  * [h0,w0,3] each, sample n at byte src_off[n] with (h0, w0) = src_hw[n]; frames n*K .. n*K+K-1 share record n.

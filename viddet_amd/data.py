@@ -14,7 +14,8 @@ from . import bbox as tbbox
 from .targets import prefetch_targets
 from .augment import AugmentBatch, AugmentRecord, augment_record, check_source_size
 from .device_targets import label_column
-from .video import Rng, color_distort_params, expand_params, imresize, random_color_distort, random_expand
+from .video import Rng, color_distort_params, expand_params, imresize, nv12_frame_size, nv12_matrix, random_color_distort, \
+    random_expand, rgb_to_nv12
 
 NUM_CLASSES = {"voc": 20, "coco": 80, "det": 200, "vid": 30, "comb": 285, "synthetic": 20}
 MEAN = np.array([0.485, 0.456, 0.406], np.float32)     # transforms.py:167
@@ -25,10 +26,16 @@ class SyntheticDetection:
     """Deterministic synthetic dataset: uint8 frames with `max_gt` random boxes."""
 
     def __init__(self, name="synthetic", num_samples=64, size=(480, 360), num_class=None, max_gt=8, seed=233,
-                 window=1, mult_out=False):
+                 window=1, mult_out=False, frame_format="rgb", yuv_matrix="bt601", yuv_range="limited"):
         """window > 1: a sample is a window of `window` frames (k,h,w,3) as the VID dataset yields with
         --window k (datasets/imgnetvid.py); its label is the centre frame's boxes, or with mult_out a list of
-        per-frame box arrays (--mult_out)."""
+        per-frame box arrays (--mult_out).  frame_format='nv12': the same frames as a decoder would hand them out,
+        (h*3/2,w) / (k,h*3/2,w) - video.rgb_to_nv12 of the RGB frames; labels unchanged."""
+        if frame_format not in ("rgb", "nv12"):
+            raise ValueError("frame_format %r is neither 'rgb' nor 'nv12'" % (frame_format,))
+        nv12_matrix(yuv_matrix, yuv_range)
+        self._nv12 = (yuv_matrix, yuv_range) if frame_format == "nv12" else None
+        self.frame_format = frame_format
         self.name = name
         self.num_class = NUM_CLASSES.get(name, 20) if num_class is None else num_class
         self.classes = ["class%d" % i for i in range(self.num_class)]
@@ -40,6 +47,10 @@ class SyntheticDetection:
 
     def sample_path(self, idx):
         return "synthetic/s%d_%06d.jpg" % (self._seed, idx)        # the seed keeps train / val file ids apart
+
+    def _as_format(self, frames):
+        """RGB frames (.., h, w, 3) in the dataset's frame format"""
+        return frames if self._nv12 is None else rgb_to_nv12(frames, *self._nv12)
 
     def _frame(self, rng):
         w, h = self._size
@@ -54,9 +65,10 @@ class SyntheticDetection:
     def __getitem__(self, idx):
         rng = np.random.default_rng(self._seed * 1000003 + idx)
         if self._window <= 1:
-            return self._frame(rng)
+            img, label = self._frame(rng)
+            return self._as_format(img), label
         frames = [self._frame(rng) for _ in range(self._window)]
-        imgs = np.stack([f[0] for f in frames])
+        imgs = self._as_format(np.stack([f[0] for f in frames]))
         if self._mult_out:
             return imgs, [f[1] for f in frames]
         return imgs, frames[self._window // 2][1]
@@ -92,17 +104,17 @@ class SyntheticVideo(SyntheticDetection):
         return self._frame(np.random.default_rng([self._seed, 7919, v, t]))
 
     def video_frames(self, v):
-        """uint8 (T, h, w, 3): the frames of clip v in order"""
+        """uint8 (T, h, w, 3) - frame_format='nv12': (T, h*3/2, w): the frames of clip v in order"""
         self.sample_index(v, 0)
-        return np.stack([self._clip_frame(v, t)[0] for t in range(self.frames_per_video)])
+        return self._as_format(np.stack([self._clip_frame(v, t)[0] for t in range(self.frames_per_video)]))
 
     def __getitem__(self, idx):
         v, t = divmod(int(idx), self.frames_per_video)
         self.sample_index(v, t)
         img, label = self._clip_frame(v, t)
         if self._window <= 1:
-            return img, label
-        return np.stack([img if f == t else self._clip_frame(v, int(f))[0] for f in self.window_frames[t]]), label
+            return self._as_format(img), label
+        return self._as_format(np.stack([img if f == t else self._clip_frame(v, int(f))[0] for f in self.window_frames[t]])), label
 
 
 class SyntheticCombined(SyntheticDetection):
@@ -193,16 +205,23 @@ class YOLO3VideoInferenceTransform:
     frames as uint8 (H,W,3) / (k,H,W,3): the network normalises them on the GPU (vd_preprocess_u8_nchw) - the same
     arithmetic, a quarter of the bytes over PCIe.  device_resize=True (with device_normalize) returns the frames untouched,
     uint8 at their source size: the network resizes them on the GPU too (YOLOV3.set_device_resize, vd_resize_u8_nchw); the
-    boxes are resized to (width,height) as before."""
+    boxes are resized to (width,height) as before.  frame_format='nv12' (with both): the frames are NV12,
+    (H0*3/2,W0) / (k,H0*3/2,W0), and travel untouched too (YOLOV3.set_device_resize(source='nv12'), vd_resize_nv12_nchw)."""
 
-    def __init__(self, width, height, device_normalize=False, device_resize=False):
+    def __init__(self, width, height, device_normalize=False, device_resize=False, frame_format="rgb"):
         if device_resize and not device_normalize:
             raise ValueError("device_resize=True needs device_normalize=True: the device resizes raw uint8 frames inside the "
                              "kernel that normalises them")
+        if frame_format not in ("rgb", "nv12"):
+            raise ValueError("frame_format %r is neither 'rgb' nor 'nv12'" % (frame_format,))
+        if frame_format == "nv12" and not device_resize:
+            raise ValueError("frame_format='nv12' needs device_resize=True: NV12 frames are converted inside the kernel that "
+                             "resizes them, the host transform has no NV12 path")
         self._w, self._h, self._u8, self._raw = width, height, device_normalize, bool(device_resize)
+        self._nv12 = frame_format == "nv12"
 
     def __call__(self, img, label, idx=0):
-        h, w = img.shape[-3], img.shape[-2]
+        h, w = nv12_frame_size(img.shape[-2], img.shape[-1]) if self._nv12 else (img.shape[-3], img.shape[-2])
         if self._raw:
             out = np.asarray(img, dtype=np.uint8)
         else:

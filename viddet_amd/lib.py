@@ -169,6 +169,9 @@ SIGNATURES = {
     "vd_temporal_cat_idx": (_i, [_p, _p, _p, _i, _i, _i, _i64, _i, _p]),
     # raw uint8 frames resized and normalised on the device (vd_resize.hip)
     "vd_resize_u8_nchw": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p]),
+    # the same on NV12 frames: two planes with a pitch, converted to RGB on the way (vd_resize.hip)
+    "vd_resize_nv12_nchw": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i,
+                                 _i, _i, _i, _i, _i, _i, _i, _p]),
     # the pixels of the training augmentation on the device (vd_augment.hip)
     "vd_augment_u8_nchw": (_i, [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p]),
     # the prefetch targets of a training batch on the device (vd_targets.hip)

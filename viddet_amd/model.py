@@ -1218,6 +1218,7 @@ class YOLOV3(object):
         self.precision = 'fp32'        # inference precision: 'fp32' | 'bf16' (set_precision)
         self._dev_resize = None        # (height, width, interp): raw uint8 frames are resized on the device (set_device_resize)
         self._resize_cache = {}        # (H0, W0, H, W, interp) -> the tap tables of that resize, host and device
+        self._dev_nv12 = None          # set_device_resize(source='nv12'): the seven integers of video.NV12_MATRICES[(matrix, range)]
         self.bucketed_allreduce = _os.environ.get('VD_BUCKETED', '1') != '0'
         self.alias_skip_grad = _os.environ.get('VD_ALIAS_SKIP', '1') != '0'    # skip gradients by alias, not by copy
         self.fuse_bn_bwd = _os.environ.get('VD_FUSE_BWD', '1') != '0'          # BN backward reductions in the dgrad epilogue
@@ -1789,6 +1790,11 @@ class YOLOV3(object):
         if self.noback:
             for (nm, _, _), t in zip(ROUTE_TENSORS, x):
                 bufs['in:' + nm].copy_(t.reshape(bufs['in:' + nm].shape))
+        elif x.dtype == torch.uint8 and self._dev_nv12 is not None:
+            # NV12 frames (B,H0*3/2,W0) or windows (B,K,H0*3/2,W0): converted, resized and normalised in one kernel
+            n_ = bufs['in'].shape[0]
+            assert x.numel() == n_ * x.shape[-2] * x.shape[-1], "NV12 input must be (B[,K],H0*3/2,W0)"
+            self._preprocess_u8(self._frames_to_device(x), bufs['in'], n_)
         elif x.dtype == torch.uint8:
             # uint8 frames (B,H,W,3) or windows (B,K,H,W,3) straight from the loader: /255, normalise and NHWC -> planar in
             # one kernel (transforms.py:239-245), a quarter of the host-to-device bytes
@@ -1804,6 +1810,8 @@ class YOLOV3(object):
         """n uint8 frames (..,H0,W0,3) on the device -> the first n rows of the NCHW input tensor `dst`, normalised: one
         vd_preprocess_u8_nchw launch, or - device resize on and the frames not yet the size of dst - one vd_resize_u8_nchw
         launch that resamples them on the way (its output is vd_preprocess_u8_nchw of the resized uint8 frames, bit for bit)"""
+        if self._dev_nv12 is not None:
+            return self._preprocess_nv12(xd, dst, n)
         h, w = dst.shape[2], dst.shape[3]
         h0, w0 = xd.shape[-3], xd.shape[-2]
         if self._dev_resize is None or (h0, w0) == (h, w):       # (imresize returns a copy of a frame of the target size)
@@ -1816,6 +1824,39 @@ class YOLOV3(object):
         L.check(L.load().vd_resize_u8_nchw(xd.data_ptr(), dst.data_ptr(), None, n, h0, w0, h, w, iy.data_ptr(), wy.data_ptr(),
                                            iy.shape[1], ix.data_ptr(), wx.data_ptr(), ix.shape[1], L.stream_ptr()),
                 'vd_resize_u8_nchw')
+
+    def _frames_to_device(self, x):
+        """uint8 frames for _preprocess_u8: on the device and contiguous - NV12 frames (set_device_resize(source='nv12'))
+        keep their layout, _preprocess_nv12 reads a pitched surface through its strides"""
+        x = x.to(self.device)
+        return x if self._dev_nv12 is not None else x.contiguous()
+
+    def _preprocess_nv12(self, xd, dst, n):
+        """n NV12 frames (..,H0*3/2,W0) uint8 on the device -> the first n rows of `dst`: one vd_resize_nv12_nchw launch, a
+        frame already at the target size included (identity tap tables).  A tensor with last stride 1, rows at least W0
+        apart and frames at least a frame's rows apart - a contiguous one, or the view (N,H0*3/2,P)[..., :W0] of a pitched
+        decoder surface - goes to the kernel through its strides as pitch / frame_stride; any other layout is made
+        contiguous first."""
+        from .video import nv12_frame_size
+        hn, w0 = xd.shape[-2], xd.shape[-1]
+        h0, _ = nv12_frame_size(hn, w0)
+        xd = xd.reshape(-1, hn, w0)                               # windows (B,K,..): B*K frames, a view where the strides allow
+        pitch, fstride = xd.stride(1), xd.stride(0)
+        if xd.stride(2) != 1 or pitch < w0 or (xd.shape[0] > 1 and fstride < hn * pitch):
+            xd = xd.contiguous()
+            pitch, fstride = xd.stride(1), xd.stride(0)
+        if xd.shape[0] == 1:                                      # (a single frame's stride says nothing)
+            fstride = hn * pitch
+        assert xd.shape[0] >= n
+        t = self._resize_tables(h0, w0, identity=(h0, w0) == (dst.shape[2], dst.shape[3]))
+        if t['dev'] is None:
+            t['dev'] = [torch.from_numpy(a).to(self.device) for a in t['host']]
+        iy, wy, ix, wx = t['dev']
+        in_bytes = (n - 1) * fstride + (hn - 1) * pitch + w0      # up to the last frame's last chroma byte, nothing behind it
+        L.check(L.load().vd_resize_nv12_nchw(xd.data_ptr(), in_bytes, fstride, pitch, h0 * pitch, dst.data_ptr(), None, n, h0, w0,
+                                             dst.shape[2], dst.shape[3], iy.data_ptr(), wy.data_ptr(), iy.shape[1], ix.data_ptr(),
+                                             wx.data_ptr(), ix.shape[1], *self._dev_nv12, L.stream_ptr()),
+                'vd_resize_nv12_nchw')
 
     def _build_infer(self, B, H, W):
         bufs = self._buffers('infer', B, H, W, False)
@@ -2153,6 +2194,20 @@ class YOLOV3(object):
         if self.noback:
             return x[0].shape[0], x[0].shape[-2] * 8, x[0].shape[-1] * 8
         if self._dev_resize is not None:            # raw (B[,K],H0,W0,3) frames, resized to the target on the device
+            if self._dev_nv12 is not None:          # NV12 (B[,K],H0*3/2,W0): two planes, no channel axis
+                if x.dtype != torch.uint8:
+                    raise ValueError("set_device_resize(source='nv12') is on: the network takes NV12 frames, uint8 "
+                                     "(B[,K],H0*3/2,W0), got a %s tensor %s" % (str(x.dtype).replace("torch.", ""), tuple(x.shape)))
+                if x.dim() >= 4 and x.shape[-1] == 3:
+                    raise ValueError("set_device_resize(source='nv12') is on: the network takes NV12 frames (B[,K],H0*3/2,W0), "
+                                     "got packed RGB frames %s - set source='rgb' for those" % (tuple(x.shape),))
+                if x.dim() not in (3, 4):
+                    raise ValueError("set_device_resize(source='nv12') is on: expected NV12 frames (B[,K],H0*3/2,W0), got %s"
+                                     % (tuple(x.shape),))
+                from .video import nv12_frame_size
+                h0, w0 = nv12_frame_size(x.shape[-2], x.shape[-1])
+                self._resize_tables(h0, w0, identity=(h0, w0) == self._dev_resize[:2])
+                return x.shape[0], self._dev_resize[0], self._dev_resize[1]
             if x.dtype != torch.uint8:
                 raise ValueError("set_device_resize is on: the network takes raw uint8 frames (B[,K],H0,W0,3); a float batch is "
                                  "already normalised at its own size - switch it off with set_device_resize(None)")
@@ -2162,15 +2217,30 @@ class YOLOV3(object):
             return x.shape[0], x.shape[-3], x.shape[-2]
         return x.shape[0], x.shape[-2], x.shape[-1]
 
-    def set_device_resize(self, width, height=None, interp=9):
+    def set_device_resize(self, width, height=None, interp=9, source='rgb', matrix='bt601', range='limited'):
         """Resize raw uint8 frames to (height, width) on the device (vd_resize.hip); width None switches it off
         (the default: every call behaves as without it).  On: uint8 inputs (B,H0,W0,3), (B,K,H0,W0,3) and detect_video's
         (T,H0,W0,3) have any one source size per call and go through video.imresize's resample (interp 9: area when both axes
         shrink, bicubic when both grow, bilinear otherwise) inside the kernel that normalises them; the plans are those of
-        the target size.  Float inputs are refused while it is on."""
+        the target size.  Float inputs are refused while it is on.
+
+        source='nv12' (DESIGN.md 23): the frames are NV12, as video decoders hand them out - uint8 (B,H0*3/2,W0),
+        (B,K,H0*3/2,W0) and detect_video's (T,H0*3/2,W0), on the host or already on the device, a pitched surface through
+        its strides (_preprocess_nv12) - converted to RGB by video.nv12_to_rgb's integer arithmetic with
+        NV12_MATRICES[(matrix, range)] inside the same launch (vd_resize_nv12_nchw); a frame of the target size goes
+        through it too.  The result is bit-equal to source='rgb' on nv12_to_rgb of the frames."""
         if width is None:
-            self._dev_resize = None
+            self._dev_resize = self._dev_nv12 = None
             return
+        if source not in ('rgb', 'nv12'):
+            raise ValueError("set_device_resize: source %r is neither 'rgb' nor 'nv12'" % (source,))
+        coef = None
+        if source == 'nv12':
+            from .video import nv12_matrix
+            try:
+                coef = nv12_matrix(matrix, range)
+            except ValueError as e:
+                raise ValueError("set_device_resize: %s" % e) from None
         if self.noback:
             raise NotImplementedError("set_device_resize with noback: the no-backbone network takes cached feature maps, not "
                                       "frames - there is nothing to resize")
@@ -2183,17 +2253,19 @@ class YOLOV3(object):
             raise ValueError("set_device_resize: interp %r is not a separable interpolation (1 bilinear, 2 area, 3 bicubic, "
                              "4 Lanczos, 9 = by direction)" % (interp,))
         self._dev_resize = (height, width, interp)
+        self._dev_nv12 = coef
 
-    def _resize_tables(self, h0, w0):
+    def _resize_tables(self, h0, w0, identity=False):
         """The tap tables of the (h0, w0) -> target resize, cached on the net per (H0, W0, H, W, interp): {'host': the four
         arrays of video.resize_tables, 'dev': their uploads (made by the first launch that needs them)}.  Refuses, before
-        anything touches the GPU, a resize whose taps the kernel does not take."""
+        anything touches the GPU, a resize whose taps the kernel does not take.  identity: the one-tap tables of a frame
+        already at the target size (the NV12 kernel converts such a frame too), under the key (.., 'identity')."""
         h, w, interp = self._dev_resize
-        key = (int(h0), int(w0), h, w, interp)
+        key = (int(h0), int(w0), h, w, 'identity' if identity else interp)
         t = self._resize_cache.get(key)
         if t is None:
-            from .video import resize_tables
-            tabs = resize_tables(key[0], key[1], h, w, interp)[1:]
+            from .video import resize_tables, identity_tables
+            tabs = identity_tables(h, w) if identity else resize_tables(key[0], key[1], h, w, interp)[1:]
             ty, tx = tabs[0].shape[1], tabs[2].shape[1]
             if ty > 16 or tx > 16:
                 raise ValueError("set_device_resize: a %dx%d -> %dx%d resize has Ty=%d / Tx=%d taps per output pixel, "
@@ -2356,7 +2428,7 @@ class YOLOV3(object):
         behind them repeat the last one (a padded row must hold real data: the fp32 operand scales are per tensor)"""
         n = b - a
         if frames.dtype == torch.uint8:
-            self._preprocess_u8(frames[a:b].to(self.device).contiguous(), dst, n)
+            self._preprocess_u8(self._frames_to_device(frames[a:b]), dst, n)
         else:
             dst[:n].copy_(frames[a:b])
         if n < dst.shape[0]:
@@ -2384,7 +2456,11 @@ class YOLOV3(object):
         if step < 1 or chunk < 1:
             raise ValueError("detect_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
         u8 = frames.dtype == torch.uint8
-        if frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
+        if self._dev_nv12 is not None and u8:                     # an NV12 clip (T,H0*3/2,W0); _in_shape checks the rest
+            if frames.dim() != 3 or frames.shape[0] < 1:
+                raise ValueError("set_device_resize(source='nv12') is on: expected an NV12 clip (T,H0*3/2,W0) uint8, got %s"
+                                 % (tuple(frames.shape),))
+        elif frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
             raise ValueError("expected a clip (T,3,H,W), or (T,H,W,3) uint8, got %s" % (tuple(frames.shape),))
         T, H, W = self._in_shape(frames)
         assert 0 < self.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
@@ -3495,7 +3571,12 @@ class YOLOV3(object):
             if len(args) != 6:
                 raise TypeError("training call takes (x1, x2, x3, gt_boxes, obj_t, centers_t, scales_t, weights_t, clas_t)")
             return self._forward_train(feats, *args)
-        if x.dtype == torch.uint8:
+        if self._dev_nv12 is not None:              # NV12 frames (B[,K],H0*3/2,W0); _in_shape refuses every other mistake by name
+            if x.dtype == torch.uint8 and not (x.dim() >= 4 and x.shape[-1] == 3) and \
+                    (x.dim() != (4 if self._k > 1 else 3) or (self._k > 1 and x.shape[1] != self._k)):
+                raise ValueError("set_device_resize(source='nv12') is on: expected NV12 frames (B,%sH0*3/2,W0), got %s"
+                                 % ("%d," % self._k if self._k > 1 else "", tuple(x.shape)))
+        elif x.dtype == torch.uint8:
             if x.dim() != (5 if self._k > 1 else 4) or x.shape[-1] != 3 or (self._k > 1 and x.shape[1] != self._k):
                 raise ValueError("expected uint8 frames (B,%sH,W,3), got %s" % ("%d," % self._k if self._k > 1 else "", tuple(x.shape)))
         elif self._k > 1:

@@ -274,3 +274,97 @@ def imresize(img, w, h, interp=1, rng=None):
     if img.dtype == np.uint8:
         return np.clip(np.rint(out), 0, 255).astype(np.uint8)
     return out.astype(np.float32)
+
+
+# --------------------------------------------------------------------------------------------
+# NV12 (what video decoders hand out) <-> packed RGB
+# --------------------------------------------------------------------------------------------
+# A frame (H0*3/2, W0) uint8: H0 rows of luma Y, then H0/2 rows of interleaved chroma pairs U V, one pair per 2 x 2 block.
+# NV12_MATRICES[(matrix, range)] = (off, gain, ru, rv, gu, gv, bu): the luma offset and, as round(256 * c) of the
+# standard's real coefficient c, the luma gain and the chroma matrix row by row - R takes (ru, rv) of (U, V), G (gu, gv),
+# B (bu, 0): no standard gives blue a V term.  ONE definition: nv12_to_rgb computes with these integers and the device
+# kernel (vd_resize_nv12_nchw) is handed the same seven, so whatever the table says is what both sides compute.
+# Real coefficients, with (Kr, Kb) = (0.299, 0.114) for BT.601 and (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb:
+#   rv = 2 (1 - Kr), bu = 2 (1 - Kb), gu = -Kb bu / Kg, gv = -Kr rv / Kg, ru = 0; limited range scales the luma gain by
+#   255 / 219 (Y in 16 .. 235) and the chroma coefficients by 255 / 224 (U, V in 16 .. 240).
+NV12_MATRICES = {
+    ("bt601", "limited"): (16, 298, 0, 409, -100, -208, 516),      # 1.164384; 1.596027, -0.391762, -0.812968, 2.017232
+    ("bt601", "full"): (0, 256, 0, 359, -88, -183, 454),           # 1;        1.402,    -0.344136, -0.714136, 1.772
+    ("bt709", "limited"): (16, 298, 0, 459, -55, -136, 541),       # 1.164384; 1.792741, -0.213249, -0.532909, 2.112402
+    ("bt709", "full"): (0, 256, 0, 403, -48, -120, 475),           # 1;        1.5748,   -0.187324, -0.468124, 1.8556
+}
+_KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
+
+
+def nv12_matrix(matrix="bt601", range="limited"):
+    """The seven integers of NV12_MATRICES[(matrix, range)]; an unknown name is refused."""
+    if (matrix, range) not in NV12_MATRICES:
+        raise ValueError("NV12: unknown matrix / range %r / %r (matrix 'bt601' or 'bt709', range 'limited' or 'full')"
+                         % (matrix, range))
+    return NV12_MATRICES[(matrix, range)]
+
+
+def nv12_frame_size(hn, w0):
+    """(H0, W0) of NV12 frames stored as (.., hn, w0): hn = H0 * 3 / 2 with H0 and W0 even; anything else is refused."""
+    if hn < 3 or hn % 3 or w0 < 2 or w0 % 2:                  # (hn = 3 m gives H0 = 2 m: even)
+        raise ValueError("NV12 frames are (.., H0*3/2, W0) with H0 and W0 even (one chroma pair per 2 x 2 block), got "
+                         "%d rows (H0 = %s) of W0 = %d" % (hn, hn * 2 // 3 if hn % 3 == 0 else "%d*2/3" % hn, w0))
+    return hn * 2 // 3, w0
+
+
+def _check_rgb_even(h0, w0):
+    if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
+        raise ValueError("NV12 needs an even frame size (one chroma pair per 2 x 2 block), got H0=%d W0=%d" % (h0, w0))
+
+
+def nv12_to_rgb(frames, matrix="bt601", range="limited"):
+    """(.., H0*3/2, W0) uint8 NV12 -> (.., H0, W0, 3) uint8 RGB in exact integer arithmetic.  Chroma is taken nearest: pixel
+    (y, x) uses the pair at (y >> 1, x >> 1).  C = Y - off, D = U - 128, E = V - 128 and per channel
+    clip((gain * C + cu * D + cv * E + 128) >> 8, 0, 255) in int32: the shift is an arithmetic (floor) shift of the possibly
+    negative sum, and it comes before the clip."""
+    off, gain, ru, rv, gu, gv, bu = nv12_matrix(matrix, range)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim < 2:
+        raise ValueError("nv12_to_rgb takes uint8 frames (.., H0*3/2, W0), got %s %r" % (frames.dtype, frames.shape))
+    h0, w0 = nv12_frame_size(frames.shape[-2], frames.shape[-1])
+    c = frames[..., :h0, :].astype(np.int32) - off
+    uv = frames[..., h0:, :].astype(np.int32) - 128
+    d = np.repeat(np.repeat(uv[..., 0::2], 2, axis=-2), 2, axis=-1)
+    e = np.repeat(np.repeat(uv[..., 1::2], 2, axis=-2), 2, axis=-1)
+    y = gain * c + 128
+    rgb = np.stack([y + ru * d + rv * e, y + gu * d + gv * e, y + bu * d], axis=-1)
+    return np.clip(rgb >> 8, 0, 255).astype(np.uint8)
+
+
+def rgb_to_nv12(frames, matrix="bt601", range="limited"):
+    """The host inverse, for synthetic data and tests: (.., H0, W0, 3) uint8 RGB -> (.., H0*3/2, W0) uint8 NV12 in fp64
+    with the standard's real coefficients; the chroma of a 2 x 2 block is the mean of its four pixels' chroma; rounded
+    (half to even) and clipped to 0 .. 255."""
+    nv12_matrix(matrix, range)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or frames.ndim < 3 or frames.shape[-1] != 3:
+        raise ValueError("rgb_to_nv12 takes uint8 frames (.., H0, W0, 3), got %s %r" % (frames.dtype, frames.shape))
+    h0, w0 = frames.shape[-3], frames.shape[-2]
+    _check_rgb_even(h0, w0)
+    kr, kb = _KR_KB[matrix]
+    off, sy, sc = (16.0, 219.0 / 255.0, 224.0 / 255.0) if range == "limited" else (0.0, 1.0, 1.0)
+    x = frames.astype(np.float64)
+    r, g, b = x[..., 0], x[..., 1], x[..., 2]
+    luma = kr * r + (1.0 - kr - kb) * g + kb * b
+    lead = frames.shape[:-3]
+
+    def chroma(diff, k):                                     # (B - Y') / (2 (1 - Kb)) and its red twin, 2 x 2 means
+        v = 128.0 + sc * diff / (2.0 * (1.0 - k))
+        return v.reshape(lead + (h0 // 2, 2, w0 // 2, 2)).mean(axis=(-3, -1))
+
+    out = np.empty(lead + (h0 * 3 // 2, w0), dtype=np.float64)
+    out[..., :h0, :] = off + sy * luma
+    out[..., h0:, 0::2] = chroma(b - luma, kb)
+    out[..., h0:, 1::2] = chroma(r - luma, kr)
+    return np.clip(np.rint(out), 0, 255).astype(np.uint8)
+
+
+def identity_tables(h, w):
+    """Tap tables, in `resize_tables`' form, of a frame already at its target size: one tap of weight 1 per axis."""
+    return (np.arange(h, dtype=np.int32).reshape(h, 1), np.ones((h, 1), np.float32),
+            np.arange(w, dtype=np.int32).reshape(w, 1), np.ones((w, 1), np.float32))

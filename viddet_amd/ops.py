@@ -339,6 +339,31 @@ def bn_finalize(sums, count, C_, gamma, beta, eps, momentum, rmean, rvar, scale,
                                 ptr(rvar), ptr(scale), ptr(shift), ptr(smean), ptr(sinv), _s()), "vd_bn_finalize")
 
 
+def _nbytes(t):
+    return 0 if t is None else t.numel() * t.element_size()
+
+
+def bn_sum_partials_ws_bytes(nblk, C_):
+    return int(_lib().vd_bn_sum_partials_ws_bytes(nblk, C_))
+
+
+def bn_sum_partials(part, nblk, C_, sums, ws=None):
+    check(_lib().vd_bn_sum_partials(ptr(part), nblk, C_, ptr(sums), ptr(ws), _nbytes(ws), _s()), "vd_bn_sum_partials")
+
+
+def bn_sum_finalize(part, nblk, C_, sums, count, gamma, beta, eps, momentum, rmean, rvar, scale, shift, smean, sinv, ws=None):
+    """vd_bn_sum_partials + vd_bn_finalize of a partial table part[nblk][2C] (one launch up to 1024 rows; ws beyond)"""
+    check(_lib().vd_bn_sum_finalize(ptr(part), nblk, C_, ptr(sums), float(count), ptr(gamma), ptr(beta), eps, momentum,
+                                    ptr(rmean), ptr(rvar), ptr(scale), ptr(shift), ptr(smean), ptr(sinv), ptr(ws), _nbytes(ws),
+                                    _s()), "vd_bn_sum_finalize")
+
+
+def bn_sum_param_grads(part, nblk, C_, sums2, dgamma, dbeta, ws=None):
+    """vd_bn_sum_partials + vd_bn_param_grads of a partial table part[nblk][2C]"""
+    check(_lib().vd_bn_sum_param_grads(ptr(part), nblk, C_, ptr(sums2), ptr(dgamma), ptr(dbeta), ptr(ws), _nbytes(ws), _s()),
+          "vd_bn_sum_param_grads")
+
+
 def bn_fold_eval(gamma, beta, rmean, rvar, eps, scale, shift):
     check(_lib().vd_bn_fold_eval(ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), eps, gamma.numel(), ptr(scale),
                                  ptr(shift), _s()), "vd_bn_fold_eval")
@@ -448,6 +473,16 @@ def temporal_pool(x, y, argmax, B, K, inner, type_):
 
 def temporal_pool_bwd(dy, argmax, dx, B, K, inner, type_):
     check(_lib().vd_temporal_pool_bwd(ptr(dy), ptr(argmax), ptr(dx), B, K, inner, type_, _s()), "vd_temporal_pool_bwd")
+
+
+def frame_slice(x, y, B, K, k0, kc, inner, backward=False):
+    """frames [k0, k0 + kc) of every K-frame window: x [B*K, inner] -> y [B*kc, inner]; backward: x = dy, y = dx (written whole)"""
+    check(_lib().vd_frame_slice(ptr(x), ptr(y), B, K, k0, kc, inner, 1 if backward else 0, _s()), "vd_frame_slice")
+
+
+def temporal_cat(x, y, B, K, hw, C_, backward=False):
+    """'cat' join: x [B*K, hw, C] -> y [B, hw, K*C]; backward: x = the stacked gradient, y = the per-frame one"""
+    check(_lib().vd_temporal_cat(ptr(x), ptr(y), B, K, hw, C_, 1 if backward else 0, _s()), "vd_temporal_cat")
 
 
 def tdw_fwd(x, w, res, y, B, K, HW, C_, amax_out=None):

@@ -637,6 +637,25 @@ int vd_augment_u8_nchw(const uint8_t* raw, const int64_t* src_off, const int32_t
 int vd_yolo_targets(const float* gt, const float* ids, int idw, const float* mix, int N, int M, int C, int H, int W, float* obj,
                     float* ctr, float* scl, float* wgt, float* cls, void* stream);
 
+/* ---- VOC mAP matching on the device (vd_eval.hip): what viddet_amd.metrics.VOCMApMetric.update decides for one
+ * image, one workgroup per image.  det_ids [B][N], det_scores [B][N], det_boxes [B][N][4] fp32 (the network's outputs); gt
+ * [B][M][gt_w] fp32 label rows x1, y1, x2, y2, id (gt_w = 5) + difficult (gt_w = 6).  A detection row with id < 0 is no detection
+ * (rec_cls -1, rec_hit -2); a label row with id < 0 is padding wherever it sits; ids are truncated like astype(int).  clip_hi >= 0:
+ * every DETECTION coordinate is clipped to [0, clip_hi] first (numpy.clip; train_yolov3.py validate() clips the detections, not
+ * the labels); < 0: no clip.  Best ground truth of a detection of class c: among the label rows of class c in row order, the
+ * highest bbox_iou in fp32 without FMA contraction and with correctly rounded division - lo = max, hi = min, overlap = lo < hi
+ * on both axes, inter = ((hi.x-lo.x)*(hi.y-lo.y)) * overlap, iou = inter / ((area_a + area_b) - inter) - chosen as numpy.argmax
+ * chooses (first maximum; the first NaN beats everything) and dropped only where max < iou_thresh is true (a NaN keeps its
+ * match).  rec_hit: -1 for every detection whose best row is difficult; otherwise 1 for the first detection on that row in the
+ * host's visiting order (score descending, then row index) and 0 for every later one; 0 without a best row.  rec_cls [B][N]
+ * int32, rec_score [B][N] fp32 (the scores, copied), rec_hit [B][N] int8: written in full.  npos [C] += the non-difficult and
+ * ndiff [C] (may be NULL) += the difficult label rows per class, by integer atomics; a label id outside [0, C) is counted in
+ * neither and a detection id outside [0, C) is only recorded: no id indexes memory.  0 <= N <= 1024, 0 <= M <= 512, B >= 0,
+ * C >= 1; every pointer but rec_hit 4-byte aligned.  Bit-reproducible. */
+int vd_voc_match(const float* det_ids, const float* det_scores, const float* det_boxes, int B, int N, const float* gt, int M,
+                 int gt_w, float clip_hi, float iou_thresh, int32_t* rec_cls, float* rec_score, int8_t* rec_hit, int32_t* npos,
+                 int32_t* ndiff, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ from viddet_amd.augment import augment_on_device
 from viddet_amd.device_targets import targets_on_device
 from viddet_amd.data import (SyntheticDetection, MixupDetection, YOLO3VideoTrainTransform, YOLO3VideoInferenceTransform, Loader,
                              FeatureDataset, YOLO3NBVideoTrainTransform, YOLO3NBVideoInferenceTransform)
-from viddet_amd.metrics import VOCMApMetric, VOCMApMetricTemporal, LossMetric
+from viddet_amd.metrics import VOCMApMetric, VOCMApMetricTemporal, DeviceVOCMApMetric, DeviceVOCMApMetricTemporal, LossMetric
 from viddet_amd.model import yolo3_darknet53, yolo3_no_backbone, yolo3_3ddarknet, check_conv_types
 from viddet_amd.schedule import LRScheduler, LRSequential
 from viddet_amd.video import Rng
@@ -123,6 +123,11 @@ def parse_flags(argv=None):
       help="(no reference counterpart) the dense prefetch targets (objectness, centre, scale, weight, class) are written on the GPU "
            "by vd_yolo_targets from the transformed boxes: a sample carries its (M,5) label rows, not five (P,.) tensors, through "
            "the workers and over PCIe (DESIGN.md 22); the targets are the host path's")
+    A("--device_metric", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) validation matches detections and ground truth on the GPU (vd_voc_match, one workgroup per "
+           "image) from the network's output tensors: no per-batch download, no per-image host loop, and under data parallelism "
+           "each rank matches only its shard; the sort by score and the AP sums stay on the host (DESIGN.md 24); the mAP is the "
+           "host metric's bit for bit")
     return ap.parse_args(argv)
 
 
@@ -150,10 +155,12 @@ def get_dataset(dataset_name, dataset_val_name, save_prefix=""):
     val_ds = SyntheticDetection(name, num_samples=max(8, FLAGS.synthetic_samples // 4), seed=FLAGS.seed + 1, **win)
     if FLAGS.features_dir is not None:                 # :177-205 datasets built with features_dir
         train_ds, val_ds = FeatureDataset(train_ds, FLAGS.features_dir), FeatureDataset(val_ds, FLAGS.features_dir)
+    # --device_metric: the same metrics with the per-image matching in vd_voc_match (validate() dispatches on the type)
+    metric_t, metric_1 = (DeviceVOCMApMetricTemporal, DeviceVOCMApMetric) if FLAGS.device_metric else (VOCMApMetricTemporal, VOCMApMetric)
     if FLAGS.mult_out:                                 # :207-210
-        val_metric = VOCMApMetricTemporal(t=int(FLAGS.window[0]), iou_thresh=0.5, class_names=val_ds.classes)
+        val_metric = metric_t(t=int(FLAGS.window[0]), iou_thresh=0.5, class_names=val_ds.classes)
     else:
-        val_metric = VOCMApMetric(iou_thresh=0.5, class_names=val_ds.classes)
+        val_metric = metric_1(iou_thresh=0.5, class_names=val_ds.classes)
     if FLAGS.num_samples < 0:
         FLAGS.num_samples = len(train_ds)
     if FLAGS.mixup:                                    # :227-229
@@ -281,20 +288,27 @@ def validate(net, val_data, eval_metric, data_shape):
     eval_metric.reset()
     net.set_nms(nms_thresh=0.45, nms_topk=400)
     records = []
+    on_device = isinstance(eval_metric, (DeviceVOCMApMetric, DeviceVOCMApMetricTemporal))
     for batch in val_data:
         label, sidxs = batch[-2], batch[-1]
         if FLAGS.features_dir is not None:             # :444-461 net(x1, x2, x3)
             ids, scores, bboxes = net(*[torch.from_numpy(f).cuda() for f in batch[:3]])
         else:
             ids, scores, bboxes = net(torch.from_numpy(batch[0]).cuda())
-        det_ids, det_scores = ids.cpu().numpy(), scores.cpu().numpy()
         # :458/:477 clip to "the last dim of batch[0]" - the image width, or (as in the reference) the width of the
         # stride-8 feature map when the batch holds cached features
         width = batch[0].shape[-2] if batch[0].dtype == np.uint8 else batch[0].shape[-1]     # (B,H,W,3) uint8 frames
+        if on_device:                                  # --device_metric: matched where they are; nothing is read back here
+            eval_metric.update_device(ids, scores, bboxes, label, clip=width, sample_ids=sidxs)
+            continue
+        det_ids, det_scores = ids.cpu().numpy(), scores.cpu().numpy()
         det_bboxes = np.clip(bboxes.cpu().numpy(), 0, width)
         for j in range(det_ids.shape[0]):
             records.append((int(sidxs[j]), det_bboxes[j], det_ids[j], det_scores[j], label[j][..., :4], label[j][..., 4:5],
                             label[j][..., 5:6] if label.shape[-1] > 5 else None))
+    if on_device:                                      # the ranks exchange their compact records once; one download in get()
+        validate.last_count = eval_metric.gather()
+        return eval_metric.get()
     validate.last_count = update_metric_sharded(eval_metric, records)
     return eval_metric.get()
 

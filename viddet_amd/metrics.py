@@ -175,3 +175,12 @@ def update_metric_sharded(metric, records, group=None):
     for _, pb, pl, ps, gb, gl, gd in merged:
         metric.update([pb], [pl], [ps], [gb], [gl], None if gd is None else [gd])
     return len(merged)
+
+
+def __getattr__(name):
+    """DeviceVOCMApMetric / DeviceVOCMApMetricTemporal (viddet_amd/device_metric.py, the matching on the device) are handed out
+    from here too.  That module is built on this one, so it is imported on first use, not while this one loads."""
+    if name in ("DeviceVOCMApMetric", "DeviceVOCMApMetricTemporal"):
+        from . import device_metric
+        return getattr(device_metric, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -467,6 +467,37 @@ def yolo_targets(gt, ids, idw, mix, N, M, C, H, W, obj, ctr, scl, wgt, cls):
                                  ptr(cls), _s()), "vd_yolo_targets")
 
 
+def voc_match(det_ids, det_scores, det_boxes, gt, clip_hi, iou_thresh, rec_cls, rec_score, rec_hit, npos, ndiff=None):
+    """vd_voc_match: det_ids (B,N[,1]), det_scores (B,N[,1]), det_boxes (B,N,4) and gt (B,M,5|6) are contiguous fp32 device
+    tensors; rec_cls (B,N) int32, rec_score (B,N) fp32 and rec_hit (B,N) int8 are written whole (they may be uninitialised);
+    npos (C,) and ndiff (C,) or None are int32 and accumulated.  clip_hi < 0: the detections are not clipped."""
+    if det_boxes.dim() != 3 or det_boxes.shape[-1] != 4:
+        raise ValueError("voc_match: det_boxes must be (B,N,4), got %r" % (tuple(det_boxes.shape),))
+    B, N = int(det_boxes.shape[0]), int(det_boxes.shape[1])
+    if gt.dim() != 3 or gt.shape[-1] not in (5, 6):
+        raise ValueError("voc_match: gt must be (B,M,5|6) [x1, y1, x2, y2, id(, difficult)], got %r" % (tuple(gt.shape),))
+    M, gt_w = int(gt.shape[1]), int(gt.shape[2])
+    if N > L.VOC_MATCH_MAX_DET:
+        raise ValueError("voc_match: N=%d detections per image, vd_voc_match takes at most %d" % (N, L.VOC_MATCH_MAX_DET))
+    if M > L.VOC_MATCH_MAX_GT:
+        raise ValueError("voc_match: M=%d label rows per image, vd_voc_match takes at most %d" % (M, L.VOC_MATCH_MAX_GT))
+    if int(gt.shape[0]) != B:
+        raise ValueError("voc_match: gt holds %d images, det_boxes %d" % (int(gt.shape[0]), B))
+    for name, t, n, dt in (("det_ids", det_ids, B * N, torch.float32), ("det_scores", det_scores, B * N, torch.float32),
+                           ("det_boxes", det_boxes, B * N * 4, torch.float32), ("gt", gt, B * M * gt_w, torch.float32),
+                           ("rec_cls", rec_cls, B * N, torch.int32), ("rec_score", rec_score, B * N, torch.float32),
+                           ("rec_hit", rec_hit, B * N, torch.int8), ("npos", npos, npos.numel(), torch.int32),
+                           ("ndiff", ndiff, npos.numel(), torch.int32)):
+        if t is None and name == "ndiff":
+            continue
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("voc_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, dt, n, t.dtype, tuple(t.shape)))
+    check(_lib().vd_voc_match(ptr(det_ids), ptr(det_scores), ptr(det_boxes), B, N, ptr(gt), M, gt_w, float(clip_hi),
+                              float(iou_thresh), ptr(rec_cls), ptr(rec_score), ptr(rec_hit), ptr(npos), ptr(ndiff),
+                              int(npos.numel()), _s()), "vd_voc_match")
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

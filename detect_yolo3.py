@@ -10,7 +10,9 @@ The network underneath is viddet_amd.model.YOLOV3 (hand-written HIP kernels).  F
 no collective on the data path (inference = replicas only); the per-image box lists are gathered to rank 0, which writes
 the prediction files and evaluates.  `--model_agnostic` (:797-798, :861-862, :893, :922-925) detects class-agnostically: one
 candidate per anchor scored by its objectness, plain NMS over the image, predictions under pred_ag, results named *_ag.
-Visualisation / worst-video / COCO+VID metrics are out of scope.
+`--metrics vid` scores the detections with the ImageNet VID motion metric (get_metric :188-190, evaluate :659-695, the result
+files of :920-931; viddet_amd/vid_metric.py) on SyntheticTracks clips, `--device_metric` with the per-image matching on the
+device (vd_vid_match).  Visualisation / worst-video / the COCO metric are out of scope.
 """
 import argparse
 import os
@@ -24,8 +26,10 @@ import numpy as np
 import torch
 
 from viddet_amd import dist as vdist
-from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticVideo, YOLO3VideoInferenceTransform, Loader
+from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticTracks, SyntheticVideo, \
+    YOLO3VideoInferenceTransform, Loader
 from viddet_amd.metrics import VOCMApMetric
+from viddet_amd.vid_metric import VIDDetectionMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
 from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
 from train_yolov3 import _list, _bool
@@ -92,6 +96,9 @@ def parse_flags(argv=None):
     A("--synthetic_videos", type=int, default=None,
       help="(no reference counterpart) the dataset is SyntheticVideo: this many clips of --synthetic_samples frames each, "
            "windows by --window K,step inside a clip (default with --stream: 2; without --stream the windowed path runs on it)")
+    A("--device_metric", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) --metrics vid matches detections and ground truth on the GPU (vd_vid_match, one workgroup "
+           "per image; DeviceVIDDetectionMetric): the same vid.txt as the host metric writes (DESIGN.md 25)")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -155,9 +162,12 @@ def pred_dir(save_dir, save_prefix, agnostic=False):
     return os.path.join(save_dir, save_prefix, "pred_ag" if agnostic else "pred")
 
 
-def result_name(metric_name, model_agnostic=False):
-    """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798, so `_met` is never appended here)"""
-    return metric_name + "_ag" if model_agnostic else metric_name
+def result_name(metric_name, model_agnostic=False, metric_agnostic=False):
+    """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798; `_met` marks a class-agnostic metric over a
+    per-class model, which only the vid metric has)"""
+    if model_agnostic:
+        return metric_name + "_ag"
+    return metric_name + "_ag_met" if metric_agnostic else metric_name
 
 
 def check_flags(FLAGS):
@@ -170,11 +180,17 @@ def check_flags(FLAGS):
         v = getattr(FLAGS, flag)
         if v and not (isinstance(v, str) and not v.strip()):
             raise NotImplementedError("--%s is outside the yolo3_darknet53 hot path" % flag)
+    vid = "vid" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
     if FLAGS.model_agnostic:
         FLAGS.metric_agnostic = True                      # detect_yolo3.py:797-798
-    elif FLAGS.metric_agnostic:
+    elif FLAGS.metric_agnostic and not vid:
         raise NotImplementedError("--metric_agnostic without --model_agnostic only acts inside VIDDetectionMetric "
-                                  "(detect_yolo3.py:189-190), which is not built: the voc metric takes no agnostic argument")
+                                  "(detect_yolo3.py:189-190): it needs --metrics vid, the voc metric takes no agnostic argument")
+    if vid and len(FLAGS.dataset) > 1:
+        raise NotImplementedError("--metrics vid does not combine with several --dataset names: the combined set has no "
+                                  "tracks, so no motion IoUs")
+    if getattr(FLAGS, "device_metric", False) and not vid:
+        raise NotImplementedError("--device_metric acts on --metrics vid only (train_yolov3.py has the voc metric's)")
     # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
     ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
     if ct is not None:
@@ -267,6 +283,19 @@ def evaluate(metrics, dataset, predictions, data_shape):
     return [m.get() for m in metrics]
 
 
+def evaluate_vid(metric, dataset, predictions):
+    """detect_yolo3.py:659-695 for the vid metric: the saved predictions, un-normalised to the source frame (:685-688), filed
+    under the frame's sample id; the metric takes the ground truth from the dataset itself"""
+    w, h = dataset.frame_size
+    for idx, sid in enumerate(dataset.get_sample_ids()):
+        img_path = dataset.sample_path(idx)
+        if img_path in predictions:
+            pred = predictions[img_path]
+            det_bboxes = [[[[b[2] * w, b[3] * h, b[4] * w, b[5] * h] for b in pred]]]          # [1][image][row][4]
+            metric.update(det_bboxes, [[[b[0] for b in pred]]], [[[b[1] for b in pred]]], None, None, None, sid=sid)
+    return metric.get()
+
+
 def main(argv=None):
     FLAGS = parse_flags(argv)
     FLAGS.window = [int(s) for s in FLAGS.window]
@@ -282,6 +311,11 @@ def main(argv=None):
     fmt = dict(frame_format="nv12", yuv_matrix=FLAGS.yuv_matrix, yuv_range=FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else {}
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
+    elif "vid" in [m.lower() for m in FLAGS.metrics]:
+        # the vid metric needs tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
+        dataset = SyntheticTracks(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
+                                  frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
+                                  step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1, **fmt)
     elif FLAGS.stream or FLAGS.synthetic_videos is not None:
         # clips: --synthetic_videos of them (given, or 2 with --stream), --synthetic_samples frames each, windows by --window K,step
         dataset = SyntheticVideo(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
@@ -329,6 +363,20 @@ def main(argv=None):
         if rank != 0:
             return None
     save_predictions(save_dir, dataset, boxes, max_do=FLAGS.max_do)
+    vid_result = None
+    if "vid" in [m.lower() for m in FLAGS.metrics]:
+        if FLAGS.device_metric:
+            from viddet_amd.device_vid_metric import DeviceVIDDetectionMetric as vid_class
+        else:
+            vid_class = VIDDetectionMetric
+        names, values = vid_result = evaluate_vid(vid_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset,
+                                                  load_predictions(save_dir, dataset, FLAGS.max_do))
+        # detect_yolo3.py:920-931: `name value` per line in vid.txt / vid_ag.txt / vid_ag_met.txt
+        with open(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
+                               result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), "w") as f:
+            for k, v in zip(names, values):
+                print(k, v)
+                f.write("{} {}\n".format(k, v))
     if "voc" in FLAGS.metrics:
         preds = load_predictions(save_dir, dataset, FLAGS.max_do)
         if len(FLAGS.dataset) > 1:                                              # detect_yolo3.py:898-899 (class-tree sets)
@@ -343,7 +391,7 @@ def main(argv=None):
                 for k, v in zip(names, values):
                     f.write("{} {}\n".format(k, v))
         return names, values
-    return None
+    return vid_result
 
 
 if __name__ == "__main__":

@@ -656,6 +656,30 @@ int vd_voc_match(const float* det_ids, const float* det_scores, const float* det
                  int gt_w, float clip_hi, float iou_thresh, int32_t* rec_cls, float* rec_score, int8_t* rec_hit, int32_t* npos,
                  int32_t* ndiff, int C, void* stream);
 
+/* ---- ImageNet VID motion metric, matching on the device (vd_vid_eval.hip): what viddet_amd.vid_metric.match_image
+ * decides for one image, one workgroup per image.  All inputs are float64: det [B][N][6] rows label, score, x1, y1, x2, y2 in
+ * source pixels (label < 0: a padded row, wherever it sits); gt [B][M][6] rows x1, y1, x2, y2, label, motion_iou (label < 0:
+ * padded); motion_ranges [4][2], area_ranges [4][2] (lo, hi), on the device too.  Per label row thr = (w*h) / ((w+tol)*(h+tol))
+ * with w = x2-x1+1, h = y2-y1+1, capped at iou_thresh; it is ignored by motion range r where miou < lo | miou > hi (a NaN is
+ * inside every range) and by area range r where (y2-y1+1)*(x2-x1+1) < lo | > hi.  The detections are visited by score
+ * descending (numpy's stable argsort of -score: NaN last, ties by row); each takes the not yet taken label row of its class
+ * (labels truncated like astype(int)) with ov >= thr and the largest ov, the lowest row on ties - ov = iw*ih / ((area_det +
+ * area_gt) - iw*ih) where iw = min(x2) - max(x1) + 1 > 0 and ih > 0, else 0; fp64 without FMA contraction, correctly rounded
+ * division.  Outputs, int32, cell c = 4 * motion + area:
+ *   rec_gt [B][N]   the matched label row, -1 unmatched, -2 a padded row
+ *   rec_tp [B][N]   bit c: matched, and the row is ignored by neither range of the cell
+ *   rec_fp [B][N]   bits 2c, 2c+1, of an unmatched detection: 0 (its own area is outside the area range, or its largest ov over
+ *                   all label rows the motion range ignores exceeds that over those it does not), 1 (the reverse), 2 (the two
+ *                   are equal and the image has no label row: the host's empty_weight), 3 (equal otherwise: the image's ignored
+ *                   fraction img_nig / img_ngt)
+ *   img_nig [B][4]  label rows ignored by motion range r;  img_ngt [B] valid label rows       - these five are written in full
+ *   npos [C] += label rows per class;  nout [16][C] += label rows per class ignored by cell c - integer atomics, the caller zeroes
+ * A label id outside [0, C) is counted in neither; a detection id outside [0, C) is only recorded: no id indexes memory.
+ * 0 <= N <= 1024, 0 <= M <= 512, B >= 0, C >= 1; double pointers 8-byte, int pointers 4-byte aligned.  Bit-reproducible. */
+int vd_vid_match(const double* det, int B, int N, const double* gt, int M, const double* motion_ranges, const double* area_ranges,
+                 double iou_thresh, double pixel_tolerance, int32_t* rec_gt, int32_t* rec_tp, int32_t* rec_fp, int32_t* img_nig,
+                 int32_t* img_ngt, int32_t* npos, int32_t* nout, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

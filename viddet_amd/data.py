@@ -117,6 +117,82 @@ class SyntheticVideo(SyntheticDetection):
         return self._as_format(np.stack([img if f == t else self._clip_frame(v, int(f))[0] for f in self.window_frames[t]])), label
 
 
+class SyntheticTracks(SyntheticVideo):
+    """SyntheticVideo whose labels are TRACKS, for the VID motion metric (viddet_amd/vid_metric.py): a clip
+    holds 2-5 objects, each with one class, a log-uniform size of about 12-260 px, a birth and a death frame and a constant
+    velocity drawn from three speed groups (per frame about 0 / 2 / 9 % of its size), so that the motion IoUs of all three
+    groups (> 0.9, 0.7-0.9, < 0.7) occur; an object bounces off the frame's edges and its box is clipped to the frame.
+    Object j of clip v is drawn from a generator seeded by [seed, v, j].  The pixels, the windows and the sample contract
+    are SyntheticVideo's (column 5 of a sample's label stays the `difficult` zero); beside it stands what the metric reads
+    (metrics/imgnetvid.py:23-27,83-84,184): get_sample_ids(), get_label(sid) with the track id in column 5, motion_ious,
+    wn_classes."""
+
+    SPEEDS = ((0.0, 0.004), (0.015, 0.03), (0.07, 0.12))     # per frame, as a share of the object's size
+
+    def __init__(self, name="synthetic", num_videos=2, frames_per_video=16, window=1, step=1, **kw):
+        super().__init__(name, num_videos=num_videos, frames_per_video=frames_per_video, window=window, step=step, **kw)
+        self.wn_classes = list(self.classes)
+        self._labels = [self._clip_tracks(v) for v in range(self.num_videos)]       # [v][t] -> (n,6) x1,y1,x2,y2,cls,track
+        self._motion_ious = None
+
+    def _clip_tracks(self, v):
+        W, H = self._size
+        T = self.frames_per_video
+        n = int(np.random.default_rng([self._seed, v]).integers(2, 6))
+        rows = [[] for _ in range(T)]
+        for j in range(n):
+            rng = np.random.default_rng([self._seed, v, j])
+            cls = float(rng.integers(0, self.num_class))
+            size = float(np.exp(rng.uniform(np.log(12.0), np.log(260.0))))
+            w = float(np.clip(size * rng.uniform(0.7, 1.4), 12.0, 260.0))
+            h = float(np.clip(size / rng.uniform(0.7, 1.4), 12.0, 260.0))
+            birth = int(rng.integers(0, T // 4 + 1))
+            death = int(rng.integers(T - T // 4, T + 1))                             # exclusive
+            lo, hi = self.SPEEDS[int(rng.integers(0, 3))]
+            speed, angle = rng.uniform(lo, hi) * size, rng.uniform(0, 2 * np.pi)
+            c = rng.uniform(0.1, 0.9, 2) * (W, H)
+            vel = np.array([np.cos(angle), np.sin(angle)]) * speed
+            for t in range(T):
+                if birth <= t < max(death, birth + 1):
+                    p = c + vel * t
+                    p = np.abs(np.mod(p + (W - 1, H - 1), 2.0 * np.array([W - 1, H - 1])) - (W - 1, H - 1))      # bounce
+                    box = [max(p[0] - w / 2, 0.0), max(p[1] - h / 2, 0.0), min(p[0] + w / 2, W - 1.0), min(p[1] + h / 2, H - 1.0)]
+                    rows[t].append(box + [cls, float(j)])
+        return [np.array(r, dtype=np.float64).reshape(-1, 6) for r in rows]
+
+    @property
+    def frame_size(self):
+        """(width, height) of the source frames, the unit of get_label's boxes"""
+        return tuple(self._size)
+
+    def get_sample_ids(self):
+        """1-based ints in sample order (the VID image sets number their frames from 1)"""
+        return list(range(1, len(self) + 1))
+
+    def get_label(self, sid):
+        """(n,6) x1, y1, x2, y2, cls, track of sample id `sid`, in source pixels"""
+        v, t = divmod(int(sid) - 1, self.frames_per_video)
+        self.sample_index(v, t)
+        return self._labels[v][t].copy()
+
+    @property
+    def motion_ious(self):
+        """{str(sid): [motion IoU per label row]} (vid_metric.motion_ious per clip), computed once"""
+        if self._motion_ious is None:
+            from .vid_metric import motion_ious
+            self._motion_ious = {}
+            for v in range(self.num_videos):
+                for t, m in enumerate(motion_ious(self._labels[v])):
+                    self._motion_ious[str(self.sample_index(v, t) + 1)] = m
+        return self._motion_ious
+
+    def _clip_frame(self, v, t):
+        img, _ = super()._clip_frame(v, t)
+        label = self._labels[v][t].copy()
+        label[:, 5] = 0.0                                                            # the sample contract's `difficult`
+        return img, label
+
+
 class SyntheticCombined(SyntheticDetection):
     """Stand-in for CombinedDetection(datasets, class_tree=True) (detect_yolo3.py:167, datasets/combined.py): the label set of
     several datasets arranged in a class tree - one group label per dataset under 'ROOT' (labels are ordered parents first,

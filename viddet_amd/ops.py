@@ -498,6 +498,35 @@ def voc_match(det_ids, det_scores, det_boxes, gt, clip_hi, iou_thresh, rec_cls, 
                               int(npos.numel()), _s()), "vd_voc_match")
 
 
+def vid_match(det, gt, motion_ranges, area_ranges, iou_thresh, pixel_tolerance, rec_gt, rec_tp, rec_fp, img_nig, img_ngt, npos,
+              nout):
+    """vd_vid_match: det (B,N,6) [label, score, x1, y1, x2, y2], gt (B,M,6) [x1, y1, x2, y2, label, motion_iou], motion_ranges
+    (4,2) and area_ranges (4,2) are contiguous fp64 device tensors; rec_gt / rec_tp / rec_fp (B,N), img_nig (B,4) and img_ngt
+    (B,) are int32 and written whole (they may be uninitialised); npos (C,) and nout (16,C) are int32 and accumulated."""
+    if det.dim() != 3 or det.shape[-1] != 6:
+        raise ValueError("vid_match: det must be (B,N,6) [label, score, x1, y1, x2, y2], got %r" % (tuple(det.shape),))
+    if gt.dim() != 3 or gt.shape[-1] != 6:
+        raise ValueError("vid_match: gt must be (B,M,6) [x1, y1, x2, y2, label, motion_iou], got %r" % (tuple(gt.shape),))
+    B, N, M, C = int(det.shape[0]), int(det.shape[1]), int(gt.shape[1]), int(npos.numel())
+    if N > L.VID_MATCH_MAX_DET:
+        raise ValueError("vid_match: det holds N=%d detection rows per image, vd_vid_match takes at most %d" % (N, L.VID_MATCH_MAX_DET))
+    if M > L.VID_MATCH_MAX_GT:
+        raise ValueError("vid_match: gt holds M=%d label rows per image, vd_vid_match takes at most %d" % (M, L.VID_MATCH_MAX_GT))
+    if int(gt.shape[0]) != B:
+        raise ValueError("vid_match: gt holds %d images, det %d" % (int(gt.shape[0]), B))
+    f64, i32 = torch.float64, torch.int32
+    for name, t, n, dt in (("det", det, B * N * 6, f64), ("gt", gt, B * M * 6, f64), ("motion_ranges", motion_ranges, 8, f64),
+                           ("area_ranges", area_ranges, 8, f64), ("rec_gt", rec_gt, B * N, i32), ("rec_tp", rec_tp, B * N, i32),
+                           ("rec_fp", rec_fp, B * N, i32), ("img_nig", img_nig, B * 4, i32), ("img_ngt", img_ngt, B, i32),
+                           ("npos", npos, C, i32), ("nout", nout, 16 * C, i32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("vid_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, dt, n, t.dtype, tuple(t.shape)))
+    check(_lib().vd_vid_match(ptr(det), B, N, ptr(gt), M, ptr(motion_ranges), ptr(area_ranges), float(iou_thresh),
+                              float(pixel_tolerance), ptr(rec_gt), ptr(rec_tp), ptr(rec_fp), ptr(img_nig), ptr(img_ngt), ptr(npos),
+                              ptr(nout), C, _s()), "vd_vid_match")
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

@@ -12,7 +12,10 @@ the prediction files and evaluates.  `--model_agnostic` (:797-798, :861-862, :89
 candidate per anchor scored by its objectness, plain NMS over the image, predictions under pred_ag, results named *_ag.
 `--metrics vid` scores the detections with the ImageNet VID motion metric (get_metric :188-190, evaluate :659-695, the result
 files of :920-931; viddet_amd/vid_metric.py) on SyntheticTracks clips, `--device_metric` with the per-image matching on the
-device (vd_vid_match).  Visualisation / worst-video / the COCO metric are out of scope.
+device (vd_vid_match).  `--metrics coco` (the default's second metric) scores them with the COCO detection metric
+(get_metric :185-186; viddet_amd/coco_metric.py: the behaviour of the reference's wrapper and ground-truth JSON, COCOeval restated) and
+writes coco.txt, `--device_metric` with the per-image matching on the device (vd_coco_match).  Visualisation and
+the worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -30,6 +33,7 @@ from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticTrac
     YOLO3VideoInferenceTransform, Loader
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.vid_metric import VIDDetectionMetric
+from viddet_amd.coco_metric import COCODetectionMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
 from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
 from train_yolov3 import _list, _bool
@@ -97,8 +101,9 @@ def parse_flags(argv=None):
       help="(no reference counterpart) the dataset is SyntheticVideo: this many clips of --synthetic_samples frames each, "
            "windows by --window K,step inside a clip (default with --stream: 2; without --stream the windowed path runs on it)")
     A("--device_metric", type=_bool, nargs="?", const=True, default=False,
-      help="(no reference counterpart) --metrics vid matches detections and ground truth on the GPU (vd_vid_match, one workgroup "
-           "per image; DeviceVIDDetectionMetric): the same vid.txt as the host metric writes (DESIGN.md 25)")
+      help="(no reference counterpart) --metrics vid and --metrics coco match detections and ground truth on the GPU (vd_vid_match, "
+           "vd_coco_match: one workgroup per image; DeviceVIDDetectionMetric, DeviceCOCODetectionMetric): the same vid.txt / "
+           "coco.txt as the host metrics write (DESIGN.md 25, 26)")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -181,6 +186,7 @@ def check_flags(FLAGS):
         if v and not (isinstance(v, str) and not v.strip()):
             raise NotImplementedError("--%s is outside the yolo3_darknet53 hot path" % flag)
     vid = "vid" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
+    coco = "coco" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
     if FLAGS.model_agnostic:
         FLAGS.metric_agnostic = True                      # detect_yolo3.py:797-798
     elif FLAGS.metric_agnostic and not vid:
@@ -189,8 +195,9 @@ def check_flags(FLAGS):
     if vid and len(FLAGS.dataset) > 1:
         raise NotImplementedError("--metrics vid does not combine with several --dataset names: the combined set has no "
                                   "tracks, so no motion IoUs")
-    if getattr(FLAGS, "device_metric", False) and not vid:
-        raise NotImplementedError("--device_metric acts on --metrics vid only (train_yolov3.py has the voc metric's)")
+    if getattr(FLAGS, "device_metric", False) and not (vid or coco):
+        raise NotImplementedError("--device_metric acts on --metrics vid and --metrics coco only (train_yolov3.py has the voc "
+                                  "metric's)")
     # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
     ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
     if ct is not None:
@@ -283,17 +290,30 @@ def evaluate(metrics, dataset, predictions, data_shape):
     return [m.get() for m in metrics]
 
 
-def evaluate_vid(metric, dataset, predictions):
-    """detect_yolo3.py:659-695 for the vid metric: the saved predictions, un-normalised to the source frame (:685-688), filed
-    under the frame's sample id; the metric takes the ground truth from the dataset itself"""
-    w, h = dataset.frame_size
-    for idx, sid in enumerate(dataset.get_sample_ids()):
+def evaluate_by_sample_id(metric, dataset, predictions):
+    """detect_yolo3.py:659-695 for the metrics that take their ground truth from the dataset itself (vid, coco): the saved
+    predictions, un-normalised to the source frame (:685-688), filed under the image's sample id; an image without a saved
+    detection is not visited, as there"""
+    for idx, sid in enumerate(dataset.sample_ids):
         img_path = dataset.sample_path(idx)
         if img_path in predictions:
+            w, h = dataset.image_size(sid)
             pred = predictions[img_path]
             det_bboxes = [[[[b[2] * w, b[3] * h, b[4] * w, b[5] * h] for b in pred]]]          # [1][image][row][4]
             metric.update(det_bboxes, [[[b[0] for b in pred]]], [[[b[1] for b in pred]]], None, None, None, sid=sid)
     return metric.get()
+
+
+evaluate_vid = evaluate_by_sample_id          # its name while vid was the only such metric
+
+
+def write_results(path, names, values, echo=True):
+    """detect_yolo3.py:920-931: `name value` per line"""
+    with open(path, "w") as f:
+        for k, v in zip(names, values):
+            if echo:
+                print(k, v)
+            f.write("{} {}\n".format(k, v))
 
 
 def main(argv=None):
@@ -363,35 +383,42 @@ def main(argv=None):
         if rank != 0:
             return None
     save_predictions(save_dir, dataset, boxes, max_do=FLAGS.max_do)
-    vid_result = None
-    if "vid" in [m.lower() for m in FLAGS.metrics]:
+    metrics = [m.lower() for m in FLAGS.metrics]
+    out_dir = os.path.join(FLAGS.save_dir, FLAGS.save_prefix)
+    preds = load_predictions(save_dir, dataset, FLAGS.max_do) if {"vid", "voc", "coco"} & set(metrics) else None
+    vid_result = voc_result = coco_result = None
+    if "vid" in metrics:
         if FLAGS.device_metric:
             from viddet_amd.device_vid_metric import DeviceVIDDetectionMetric as vid_class
         else:
             vid_class = VIDDetectionMetric
-        names, values = vid_result = evaluate_vid(vid_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset,
-                                                  load_predictions(save_dir, dataset, FLAGS.max_do))
-        # detect_yolo3.py:920-931: `name value` per line in vid.txt / vid_ag.txt / vid_ag_met.txt
-        with open(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
-                               result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), "w") as f:
-            for k, v in zip(names, values):
-                print(k, v)
-                f.write("{} {}\n".format(k, v))
-    if "voc" in FLAGS.metrics:
-        preds = load_predictions(save_dir, dataset, FLAGS.max_do)
-        if len(FLAGS.dataset) > 1:                                              # detect_yolo3.py:898-899 (class-tree sets)
-            preds = hierarchical_nms(preds, dataset, level_thresh=FLAGS.hier_level)
+        vid_result = evaluate_by_sample_id(vid_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset, preds)
+        # vid.txt / vid_ag.txt / vid_ag_met.txt
+        write_results(os.path.join(out_dir, result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), *vid_result)
+    if len(FLAGS.dataset) > 1 and {"voc", "coco"} & set(metrics):              # detect_yolo3.py:898-899 (class-tree sets), ahead of
+        preds = hierarchical_nms(preds, dataset, level_thresh=FLAGS.hier_level)  # the metrics (vid is refused on such a set)
+    if "voc" in metrics:
         (names, values), = evaluate([VOCMApMetric(iou_thresh=0.5, class_names=dataset.classes)], dataset, preds,
                                     FLAGS.data_shape)
         print("{}={:.4f}".format(names[-1], values[-1]))
         if FLAGS.model_agnostic:
-            # detect_yolo3.py:920-931: the per-class and the mean AP, `name value` per line, in <metric>_ag.txt beside pred_ag.
-            # The metric is handed the rows as they are (ids all 0): the reference's voc / coco metrics take no agnostic argument
-            with open(os.path.join(FLAGS.save_dir, FLAGS.save_prefix, result_name("voc", True) + ".txt"), "w") as f:
-                for k, v in zip(names, values):
-                    f.write("{} {}\n".format(k, v))
-        return names, values
-    return vid_result
+            # the per-class and the mean AP in <metric>_ag.txt beside pred_ag.  The metric is handed the rows as they are (ids
+            # all 0): the reference's voc / coco metrics take no agnostic argument
+            write_results(os.path.join(out_dir, result_name("voc", True) + ".txt"), names, values, echo=False)
+        voc_result = names, values
+    if "coco" in metrics:
+        if FLAGS.device_metric:
+            from viddet_amd.device_coco_metric import DeviceCOCODetectionMetric as coco_class
+        else:
+            coco_class = COCODetectionMetric
+        # get_metric :186: the detections' JSON beside pred/, removed again (cleanup); no time stamp in its name
+        metric = coco_class(dataset, os.path.join(out_dir, "coco_results"), use_time=False, cleanup=True, data_shape=None)
+        coco_result = evaluate_by_sample_id(metric, dataset, preds)
+        write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), *coco_result)
+    # what main() hands back is what it handed back before coco was built: voc's where asked for, else vid's; coco's alone
+    if voc_result is not None:
+        return voc_result
+    return vid_result if vid_result is not None else coco_result
 
 
 if __name__ == "__main__":

@@ -680,6 +680,28 @@ int vd_vid_match(const double* det, int B, int N, const double* gt, int M, const
                  double iou_thresh, double pixel_tolerance, int32_t* rec_gt, int32_t* rec_tp, int32_t* rec_fp, int32_t* img_nig,
                  int32_t* img_ngt, int32_t* npos, int32_t* nout, int C, void* stream);
 
+/* ---- COCO detection metric, matching on the device (vd_coco_eval.hip): what viddet_amd.coco_metric.match_image
+ * decides for one image - COCOeval's computeIoU and evaluateImg for every category, 4 area ranges and 10 IoU thresholds - one
+ * workgroup per image.  All inputs are float64 and on the device: det [B][N][6] rows x, y, w, h, score, category; gt [B][M][8]
+ * rows x, y, w, h, area, category, annotation id, iscrowd; iou_thrs [10]; area_rng [4][2] (lo, hi, both inclusive).  A row
+ * whose category is not in [0, K) (-1: a padded row, wherever it sits; NaN) takes no part; categories are truncated like a C
+ * cast.  iou = 0 where w <= 0 or h <= 0 with w = min(dx+dw, gx+gw) - max(dx, gx), h likewise, else w*h / u, u = dw*dh for a
+ * crowd, (dw*dh + gw*gh) - w*h otherwise; fp64 without FMA contraction, correctly rounded division.  A ground truth is ignored
+ * by range r where it is a crowd or area < lo | area > hi.  The detections of a category are ranked by score descending
+ * (numpy's stable argsort of -score: NaN last, ties by row) and the first 100 take part; per range and threshold t each, in
+ * rank order, starts from iou = min(t, 1 - 1e-10) and walks the category's ground truths, the not-ignored ones first, in row
+ * order: one matched at t that is no crowd is skipped, the walk ends before the ignored ones once a not-ignored one is held,
+ * one with ious < iou is skipped, any other is taken and raises iou (on equal IoUs the later one wins).  Outputs, int32:
+ *   rec_rank [B][N]     the rank inside (image, category), -1 for a row beyond the first 100 or one that takes no part
+ *   rec_bits [B][N][4]  per area range: bit t = matched at threshold t to an annotation whose id is not 0 (COCOeval's
+ *                       `dtm != 0`), bit 10 + t = ignored: the match's ground truth is ignored, or the matched bit is clear and
+ *                       the detection's own area dw*dh is outside the range; 0 where rec_rank is -1   - both written in full
+ *   npig [K][4] += the ground truths of category k that range r does not ignore - integer atomics, the caller zeroes
+ * Boxes are finite: a NaN IoU passes `ious < iou` here, which the host's vectorised form does not restate.
+ * 0 <= N <= 1024, 0 <= M <= 512, B >= 0, 1 <= K <= 32767; double pointers 8-byte, int pointers 4-byte aligned.  Bit-reproducible. */
+int vd_coco_match(const double* det, int B, int N, const double* gt, int M, const double* iou_thrs, const double* area_rng,
+                  int32_t* rec_rank, int32_t* rec_bits, int32_t* npig, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,21 @@ class SyntheticDetection:
     def sample_path(self, idx):
         return "synthetic/s%d_%06d.jpg" % (self._seed, idx)        # the seed keeps train / val file ids apart
 
+    # what the COCO metric reads (metrics/mscoco.py:44,200; viddet_amd/coco_metric.py)
+    @property
+    def sample_ids(self):
+        """the id of every sample in sample order: get_sample_ids() where the set numbers its own, else 0 .. len - 1"""
+        return list(self.get_sample_ids()) if hasattr(self, "get_sample_ids") else list(range(len(self)))
+
+    @property
+    def frame_size(self):
+        """(width, height) of the source frames, the unit of the label rows"""
+        return tuple(self._size)
+
+    def image_size(self, sid):
+        """(width, height) of the source frame of sample id `sid`"""
+        return tuple(self._size)
+
     def _as_format(self, frames):
         """RGB frames (.., h, w, 3) in the dataset's frame format"""
         return frames if self._nv12 is None else rgb_to_nv12(frames, *self._nv12)

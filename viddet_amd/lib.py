@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("VD_LIB") or os.path.join(_HERE, "csrc", "libviddet_hi
 ABI_VERSION = 8          # include/viddet_hip.h VD_ABI_VERSION
 VOC_MATCH_MAX_DET, VOC_MATCH_MAX_GT = 1024, 512     # vd_voc_match: detection / label rows per image (vd_eval.hip)
 VID_MATCH_MAX_DET, VID_MATCH_MAX_GT = 1024, 512     # vd_vid_match: the same limits (vd_vid_eval.hip)
+COCO_MATCH_MAX_DET, COCO_MATCH_MAX_GT = 1024, 512   # vd_coco_match: the same limits (vd_coco_eval.hip)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -182,6 +183,8 @@ SIGNATURES = {
     "vd_voc_match": (_i, [_p, _p, _p, _i, _i, _p, _i, _i, _f, _f, _p, _p, _p, _p, _p, _i, _p]),
     # the per-image half of the ImageNet VID motion metric on the device (vd_vid_eval.hip)
     "vd_vid_match": (_i, [_p, _i, _i, _p, _i, _p, _p, _d, _d, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
+    # the per-image half of the COCO detection metric on the device (vd_coco_eval.hip)
+    "vd_coco_match": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
 }
 
 _lib = None

@@ -527,6 +527,35 @@ def vid_match(det, gt, motion_ranges, area_ranges, iou_thresh, pixel_tolerance, 
                               ptr(nout), C, _s()), "vd_vid_match")
 
 
+def coco_match(det, gt, iou_thrs, area_rng, rec_rank, rec_bits, npig):
+    """vd_coco_match: det (B,N,6) [x, y, w, h, score, category], gt (B,M,8) [x, y, w, h, area, category, annotation id, iscrowd],
+    iou_thrs (10,) and area_rng (4,2) are contiguous fp64 device tensors; rec_rank (B,N) and rec_bits (B,N,4) are int32 and
+    written whole (they may be uninitialised); npig (K,4) is int32 and accumulated."""
+    if det.dim() != 3 or det.shape[-1] != 6:
+        raise ValueError("coco_match: det must be (B,N,6) [x, y, w, h, score, category], got %r" % (tuple(det.shape),))
+    if gt.dim() != 3 or gt.shape[-1] != 8:
+        raise ValueError("coco_match: gt must be (B,M,8) [x, y, w, h, area, category, annotation id, iscrowd], got %r"
+                         % (tuple(gt.shape),))
+    if npig.dim() != 2 or npig.shape[-1] != 4:
+        raise ValueError("coco_match: npig must be (K,4), got %r" % (tuple(npig.shape),))
+    B, N, M, K = int(det.shape[0]), int(det.shape[1]), int(gt.shape[1]), int(npig.shape[0])
+    if N > L.COCO_MATCH_MAX_DET:
+        raise ValueError("coco_match: det holds N=%d detection rows per image, vd_coco_match takes at most %d" % (N, L.COCO_MATCH_MAX_DET))
+    if M > L.COCO_MATCH_MAX_GT:
+        raise ValueError("coco_match: gt holds M=%d label rows per image, vd_coco_match takes at most %d" % (M, L.COCO_MATCH_MAX_GT))
+    if int(gt.shape[0]) != B:
+        raise ValueError("coco_match: gt holds %d images, det %d" % (int(gt.shape[0]), B))
+    f64, i32 = torch.float64, torch.int32
+    for name, t, n, dt in (("det", det, B * N * 6, f64), ("gt", gt, B * M * 8, f64), ("iou_thrs", iou_thrs, 10, f64),
+                           ("area_rng", area_rng, 8, f64), ("rec_rank", rec_rank, B * N, i32), ("rec_bits", rec_bits, B * N * 4, i32),
+                           ("npig", npig, K * 4, i32)):
+        if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("coco_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, dt, n, t.dtype, tuple(t.shape)))
+    check(_lib().vd_coco_match(ptr(det), B, N, ptr(gt), M, ptr(iou_thrs), ptr(area_rng), ptr(rec_rank), ptr(rec_bits), ptr(npig),
+                               K, _s()), "vd_coco_match")
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

@@ -14,7 +14,9 @@ candidate per anchor scored by its objectness, plain NMS over the image, predict
 files of :920-931; viddet_amd/vid_metric.py) on SyntheticTracks clips, `--device_metric` with the per-image matching on the
 device (vd_vid_match).  `--metrics coco` (the default's second metric) scores them with the COCO detection metric
 (get_metric :185-186; viddet_amd/coco_metric.py: the behaviour of the reference's wrapper and ground-truth JSON, COCOeval restated) and
-writes coco.txt, `--device_metric` with the per-image matching on the device (vd_coco_match).  Visualisation and
+writes coco.txt, `--device_metric` with the per-image matching on the device (vd_coco_match).  `--seq_nms` (no
+reference counterpart) runs sequence NMS over the detections of every clip on the device (vd_seq_nms): the plain
+predictions and results are written as without it, the rescored ones beside them under pred_seq and *_seq.  Visualisation and
 the worst-video tool are out of scope.
 """
 import argparse
@@ -104,6 +106,16 @@ def parse_flags(argv=None):
       help="(no reference counterpart) --metrics vid and --metrics coco match detections and ground truth on the GPU (vd_vid_match, "
            "vd_coco_match: one workgroup per image; DeviceVIDDetectionMetric, DeviceCOCODetectionMetric): the same vid.txt / "
            "coco.txt as the host metrics write (DESIGN.md 25, 26)")
+    A("--seq_nms", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) sequence NMS (Han et al. 2016) over the detections of every clip, on the device "
+           "(vd_seq_nms): boxes of adjacent frames are linked, the best sequence's rows take its score, what overlaps them is "
+           "suppressed, until every row is decided.  Needs clips (--stream or --synthetic_videos).  The plain predictions and "
+           "results are written as without the flag; the rescored ones go to pred_seq and *_seq files (DESIGN.md 27)")
+    A("--seq_nms_link", type=float, default=0.5, help="--seq_nms: two boxes of adjacent frames link where their IoU exceeds this")
+    A("--seq_nms_thresh", type=float, default=0.3, help="--seq_nms: a sequence's box suppresses the boxes of its frame whose IoU exceeds this")
+    A("--seq_nms_rescore", default="avg", choices=["avg", "max"], help="--seq_nms: the score a sequence gives its boxes")
+    A("--seq_nms_input_nms", type=float, default=0.45,
+      help="--seq_nms: the nms_thresh of the per-frame NMS ahead of it (set_nms): higher lets more candidates through")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -122,62 +134,125 @@ def _collect(boxes, dataset, ids, scores, bboxes, sidxs, W):
             boxes.setdefault(file, []).append([i_, s_] + list(b_))
 
 
-def detect(net, dataset, loader, max_do=-1, data_shape=None):
+def seq_nms_args(FLAGS):
+    """the dict net.detect_video and ops.seq_nms take, None without --seq_nms"""
+    if not getattr(FLAGS, "seq_nms", False):
+        return None
+    return dict(link_thresh=FLAGS.seq_nms_link, nms_thresh=FLAGS.seq_nms_thresh, rescore=FLAGS.seq_nms_rescore)
+
+
+def clip_offsets(sidxs, frames_per_video):
+    """sample indices in ascending order -> the offsets at which a clip starts (and the end): a clip is a run of consecutive
+    frames of one video"""
+    cs = [0]
+    for n in range(1, len(sidxs)):
+        if sidxs[n] != sidxs[n - 1] + 1 or sidxs[n] // frames_per_video != sidxs[n - 1] // frames_per_video:
+            cs.append(n)
+    return cs + [len(sidxs)]
+
+
+def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45):
     """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
-    (--device_resize: raw frames, resized on the device)."""
-    net.set_nms(nms_thresh=0.45, nms_topk=400)
+    (--device_resize: raw frames, resized on the device).  seq_nms (a dict of link_thresh / nms_thresh / rescore): every
+    batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored)."""
+    net.set_nms(nms_thresh=input_nms, nms_topk=400)
     boxes = dict()
     if max_do < 0:
         max_do = len(dataset)
     c = 0
+    kept, W = [], None
     for x, _label, sidxs in loader:
         ids, scores, bboxes = net(torch.from_numpy(x).cuda())
         W = data_shape or (x.shape[-2] if x.dtype == np.uint8 else x.shape[-1])   # uint8 frames are (B,H,W,3)
-        _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        if seq_nms is None:
+            _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        else:                                                              # the plan's output tensors are rewritten by the next batch
+            kept.append((ids.clone(), scores.clone(), bboxes.clone(), [int(i) for i in sidxs]))
         c += x.shape[0]
         if c > max_do:
             break
-    return boxes
+    if seq_nms is None:
+        return boxes
+    from viddet_amd import ops
+    boxes_seq = dict()
+    if kept:
+        sidxs = [i for k in kept for i in k[3]]
+        order = sorted(range(len(sidxs)), key=lambda n: sidxs[n])          # clip order: sample = video * frames + frame
+        sidxs = [sidxs[n] for n in order]
+        gather = torch.tensor(order, device=kept[0][0].device)
+        ids, scores, bboxes = [torch.cat([k[a] for k in kept])[gather].contiguous() for a in range(3)]
+        if ids.shape[1] > 128:
+            raise ValueError("--seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most 128" % ids.shape[1])
+        bboxes = bboxes.clamp(0, W)                                        # Seq-NMS sees the boxes as they are saved (:228)
+        out = ops.seq_nms(ids, scores, bboxes, clip_start=clip_offsets(sidxs, dataset.frames_per_video),
+                          num_class=1 if net.agnostic else net.num_class, **seq_nms)
+        _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
+    return boxes, boxes_seq
 
 
-def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb"):
+def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
+                  seq_nms=None, input_nms=0.45):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
-    'nv12': as NV12 frames)."""
-    net.set_nms(nms_thresh=0.45, nms_topk=400)
+    'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
+    ones detect_video keeps in net.last_plain."""
+    net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
-    boxes = dict()
+    boxes, boxes_seq = dict(), dict()
     if max_do < 0:
         max_do = len(dataset)
     c = 0
     for v in range(rank, dataset.num_videos, world):
         x, _, _ = tf(dataset.video_frames(v), np.zeros((0, 6)))            # uint8 (T,H,W,3), normalised on the device
-        ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk)
-        _collect(boxes, dataset, ids, scores, bboxes, [dataset.sample_index(v, t) for t in range(x.shape[0])],
-                 data_shape if device_resize else x.shape[-2])
+        sidxs = [dataset.sample_index(v, t) for t in range(x.shape[0])]
+        W = data_shape if device_resize else x.shape[-2]
+        if seq_nms is None:
+            ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk)
+        else:
+            # Seq-NMS sees the boxes as they are saved: clipped to the image (:228)
+            out = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, seq_nms=dict(seq_nms, clip=W))
+            _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
+            ids, scores, bboxes = net.last_plain
+        _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         c += x.shape[0]
         if c > max_do:
             break
-    return boxes
+    return boxes if seq_nms is None else (boxes, boxes_seq)
 
 
-def pred_dir(save_dir, save_prefix, agnostic=False):
-    """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag"""
-    return os.path.join(save_dir, save_prefix, "pred_ag" if agnostic else "pred")
+def pred_dir(save_dir, save_prefix, agnostic=False, seq=False):
+    """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag;
+    seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq"""
+    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else ""))
 
 
-def result_name(metric_name, model_agnostic=False, metric_agnostic=False):
+def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=False):
     """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798; `_met` marks a class-agnostic metric over a
-    per-class model, which only the vid metric has)"""
+    per-class model, which only the vid metric has); seq: the metric of the predictions rescored by --seq_nms, `_seq` last"""
+    tail = "_seq" if seq else ""
     if model_agnostic:
-        return metric_name + "_ag"
-    return metric_name + "_ag_met" if metric_agnostic else metric_name
+        return metric_name + "_ag" + tail
+    return (metric_name + "_ag_met" if metric_agnostic else metric_name) + tail
 
 
 def check_flags(FLAGS):
     """What the parsed flags ask for that is not built is refused here, before anything touches the GPU; returns the checked
     conv_types (None: the plain 2-D backbone)."""
+    if getattr(FLAGS, "seq_nms", False):
+        # Seq-NMS links the frames of a clip: a set without clips has nothing to link
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--seq_nms does not combine with several --dataset names: the combined set has no clips")
+        if getattr(FLAGS, "mult_out", False):
+            raise NotImplementedError("--seq_nms does not combine with --mult_out: its rows are not the detections of one frame")
+        if not getattr(FLAGS, "stream", False) and getattr(FLAGS, "synthetic_videos", None) is None:
+            raise NotImplementedError("--seq_nms needs clips: give --stream or --synthetic_videos (the plain synthetic set is "
+                                      "unrelated still images)")
+        if getattr(FLAGS, "seq_nms_rescore", "avg") not in ("avg", "max"):
+            raise NotImplementedError("--seq_nms_rescore must be avg or max, got %r" % (FLAGS.seq_nms_rescore,))
+        if not 0 < getattr(FLAGS, "seq_nms_input_nms", 0.45) < 1:
+            raise NotImplementedError("--seq_nms_input_nms must lie inside (0, 1), got %r" % (FLAGS.seq_nms_input_nms,))
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
     for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
@@ -367,11 +442,20 @@ def main(argv=None):
     elif FLAGS.device_resize:
         net.set_device_resize(FLAGS.data_shape, FLAGS.data_shape)
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic)
+    seq = seq_nms_args(FLAGS)
+    seq_kw = {} if seq is None else dict(seq_nms=seq, input_nms=FLAGS.seq_nms_input_nms)
+    if seq is not None and not FLAGS.stream and world > 1:
+        raise NotImplementedError("--seq_nms without --stream runs on one GPU: the windowed path shards the frames of a clip "
+                                  "over the ranks")
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
-                              FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format)
+                              FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
+                              **seq_kw)
     else:
-        boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None)
+        boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
+    boxes_seq = None
+    if seq is not None:
+        boxes, boxes_seq = boxes
     if world > 1:
         # frames are sharded over the ranks (replicas, no collective on the data path); the per-image box lists (host
         # objects) are merged so that ONE rank writes every file - a rank must never write an (empty) file for an image
@@ -380,8 +464,24 @@ def main(argv=None):
         for part in vdist.all_gather_objects(boxes):
             merged.update(part)
         boxes = merged
+        if boxes_seq is not None:
+            merged = dict()
+            for part in vdist.all_gather_objects(boxes_seq):
+                merged.update(part)
+            boxes_seq = merged
         if rank != 0:
             return None
+    result = save_and_evaluate(FLAGS, dataset, boxes, save_dir)
+    if boxes_seq is not None:
+        # the rescored predictions and their results beside the plain ones: pred_seq, vid_seq.txt, coco_seq.txt, ...
+        save_and_evaluate(FLAGS, dataset, boxes_seq, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=True),
+                          seq=True)
+    return result
+
+
+def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):
+    """The tail of main(): the prediction files under save_dir, then --metrics on what was saved; seq names the result files
+    of the predictions rescored by --seq_nms."""
     save_predictions(save_dir, dataset, boxes, max_do=FLAGS.max_do)
     metrics = [m.lower() for m in FLAGS.metrics]
     out_dir = os.path.join(FLAGS.save_dir, FLAGS.save_prefix)
@@ -394,7 +494,8 @@ def main(argv=None):
             vid_class = VIDDetectionMetric
         vid_result = evaluate_by_sample_id(vid_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset, preds)
         # vid.txt / vid_ag.txt / vid_ag_met.txt
-        write_results(os.path.join(out_dir, result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), *vid_result)
+        write_results(os.path.join(out_dir, result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq) + ".txt"),
+                      *vid_result)
     if len(FLAGS.dataset) > 1 and {"voc", "coco"} & set(metrics):              # detect_yolo3.py:898-899 (class-tree sets), ahead of
         preds = hierarchical_nms(preds, dataset, level_thresh=FLAGS.hier_level)  # the metrics (vid is refused on such a set)
     if "voc" in metrics:
@@ -404,7 +505,7 @@ def main(argv=None):
         if FLAGS.model_agnostic:
             # the per-class and the mean AP in <metric>_ag.txt beside pred_ag.  The metric is handed the rows as they are (ids
             # all 0): the reference's voc / coco metrics take no agnostic argument
-            write_results(os.path.join(out_dir, result_name("voc", True) + ".txt"), names, values, echo=False)
+            write_results(os.path.join(out_dir, result_name("voc", True, seq=seq) + ".txt"), names, values, echo=False)
         voc_result = names, values
     if "coco" in metrics:
         if FLAGS.device_metric:
@@ -412,9 +513,10 @@ def main(argv=None):
         else:
             coco_class = COCODetectionMetric
         # get_metric :186: the detections' JSON beside pred/, removed again (cleanup); no time stamp in its name
-        metric = coco_class(dataset, os.path.join(out_dir, "coco_results"), use_time=False, cleanup=True, data_shape=None)
+        metric = coco_class(dataset, os.path.join(out_dir, "coco_results_seq" if seq else "coco_results"), use_time=False, cleanup=True, data_shape=None)
         coco_result = evaluate_by_sample_id(metric, dataset, preds)
-        write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic) + ".txt"), *coco_result)
+        write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq) + ".txt"),
+                      *coco_result)
     # what main() hands back is what it handed back before coco was built: voc's where asked for, else vid's; coco's alone
     if voc_result is not None:
         return voc_result

@@ -702,6 +702,34 @@ int vd_vid_match(const double* det, int B, int N, const double* gt, int M, const
 int vd_coco_match(const double* det, int B, int N, const double* gt, int M, const double* iou_thrs, const double* area_rng,
                   int32_t* rec_rank, int32_t* rec_bits, int32_t* npig, int K, void* stream);
 
+/* ---- Seq-NMS over the detections of video clips (vd_seq_nms.hip): what viddet_amd.seq_nms.seq_nms_host computes,
+ * bit for bit.  ids [F][N], scores [F][N], bboxes [F][N][4] fp32 (the network's outputs over F frames, corner boxes; a row with
+ * id < 0 is padding); clip_start [V + 1] int32 ON THE DEVICE, ascending offsets into the frame axis from 0 to F (NULL with V = 1:
+ * one clip [0, F)); nothing links across a clip boundary, and an offset outside [0, F] is clamped into it (a frame that no clip
+ * covers comes out as -1 rows): no offset indexes memory.  A row is a candidate iff id >= 0 (NaN is not), its score is finite and
+ * its class - the id truncated like astype(int) - is below num_class; classes are independent.  iou = iw*ih / ((a1 + a2) - iw*ih)
+ * where iw = min(x2) - max(x1) > 0 and ih > 0, else 0 (no +1; min / max propagate a NaN); fp32 without FMA contraction, correctly
+ * rounded division; `iou > thresh` is strict.  Per clip and class, every candidate alive, rounds repeat while a row is alive:
+ * frames t from last to first, alive rows i in row order: b = 0, p = none; over the alive rows j of frame t + 1 in row order with
+ * iou(i, j) > link_thresh and best[t+1][j] > b: b = best[t+1][j], p = j; best[t][i] = score + b (one add), next[t][i] = p.  The
+ * start is the alive row with the largest best, ties to the lowest frame, then the lowest row; the sequence follows next; its
+ * score is (rescore 0, avg) the sum of its rows' scores in frame order, from 0, divided by their number, or (rescore 1, max)
+ * their maximum; its rows are final with that score, and in each of its frames every alive row of the class with
+ * iou > nms_thresh to the sequence's row is dead.  Outputs, written in full: per frame the final rows by new score descending,
+ * stably by old row - out_ids [F][N] (the row's id), out_scores [F][N] (the new score), out_bboxes [F][N][4], out_perm [F][N]
+ * int32 (the old row) - then rows of -1 in all four.  Three launches: the link table (a 128-bit mask per row and threshold), one
+ * wavefront per (clip, class) for the rounds, a stable rank sort per frame.  1 <= N <= 128, F >= 1, V >= 1, 1 <= num_class <=
+ * 65535; ws_bytes >= 48 * F * N; bboxes, out_bboxes and ws 16-byte, every other pointer 4-byte aligned.  The inputs are never
+ * written.  No atomics, bit-reproducible. */
+int vd_seq_nms(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
+               int num_class, float link_thresh, float nms_thresh, int rescore, float* out_ids, float* out_scores,
+               float* out_bboxes, int32_t* out_perm, void* ws, int64_t ws_bytes, void* stream);
+/* For timing the launches apart (tools/seq_nms_probe.py): vd_seq_nms with the same checks (their messages name vd_seq_nms), making
+ * only the first one (stages 1), two (3) or all three (7) launches; with fewer than three the outputs are not written. */
+int vd_seq_nms_stages(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
+                      int num_class, float link_thresh, float nms_thresh, int rescore, float* out_ids, float* out_scores,
+                      float* out_bboxes, int32_t* out_perm, void* ws, int64_t ws_bytes, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

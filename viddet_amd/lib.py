@@ -14,6 +14,8 @@ ABI_VERSION = 8          # include/viddet_hip.h VD_ABI_VERSION
 VOC_MATCH_MAX_DET, VOC_MATCH_MAX_GT = 1024, 512     # vd_voc_match: detection / label rows per image (vd_eval.hip)
 VID_MATCH_MAX_DET, VID_MATCH_MAX_GT = 1024, 512     # vd_vid_match: the same limits (vd_vid_eval.hip)
 COCO_MATCH_MAX_DET, COCO_MATCH_MAX_GT = 1024, 512   # vd_coco_match: the same limits (vd_coco_eval.hip)
+SEQ_NMS_MAX_ROWS = 128                              # vd_seq_nms: rows per frame (vd_seq_nms.hip)
+SEQ_NMS_WS_PER_ROW = 48                             # vd_seq_nms: workspace bytes per (frame, row)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -185,6 +187,9 @@ SIGNATURES = {
     "vd_vid_match": (_i, [_p, _i, _i, _p, _i, _p, _p, _d, _d, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     # the per-image half of the COCO detection metric on the device (vd_coco_eval.hip)
     "vd_coco_match": (_i, [_p, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
+    # Seq-NMS over the detections of video clips (vd_seq_nms.hip)
+    "vd_seq_nms": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    "vd_seq_nms_stages": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
 }
 
 _lib = None

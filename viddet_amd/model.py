@@ -2434,7 +2434,7 @@ class YOLOV3(object):
         if n < dst.shape[0]:
             dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
 
-    def detect_video(self, frames, step=1, chunk=8):
+    def detect_video(self, frames, step=1, chunk=8, seq_nms=None):
         """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
         (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
         (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
@@ -2445,10 +2445,25 @@ class YOLOV3(object):
         shorter last chunk runs the same programs on padded rows (repeats of its last real row) whose outputs are dropped.
         Honours set_precision, set_nms and agnostic; k = 1 is plain batched detection in chunks.  `stream_stats` counts the
         frames that went through each part in the last call; last_rows / last_overflow cover the T frames.  With
-        `stream_keep_heads` set on the net, `stream_heads` keeps the three raw head tensors of the T frames (k > 1)."""
+        `stream_keep_heads` set on the net, `stream_heads` keeps the three raw head tensors of the T frames (k > 1).
+
+        seq_nms: None (the default: the call as it always was), True, or a dict of link_thresh / nms_thresh / rescore - the
+        finished clip's rows go through sequence NMS on the device (ops.seq_nms): the rescored, re-sorted
+        tensors are returned, last_rows follows the permutation and last_plain holds the three tensors ahead of it.  A
+        further key `clip` (a number) clips the boxes to [0, clip] first, as detect_yolo3.py clips the boxes it saves."""
         why = self._stream_refusal()
         if why is not None:
             raise NotImplementedError("detect_video with " + why)
+        seq_kw = None
+        if seq_nms is not None and seq_nms is not False:
+            seq_kw = {} if seq_nms is True else dict(seq_nms)
+            seq_clip = seq_kw.pop("clip", None)
+            unknown = sorted(set(seq_kw) - {"link_thresh", "nms_thresh", "rescore"})
+            if unknown:
+                raise ValueError("detect_video: seq_nms takes link_thresh, nms_thresh and rescore, got %s" % ", ".join(unknown))
+            if self.post_nms > L.SEQ_NMS_MAX_ROWS:
+                raise ValueError("detect_video with seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most %d"
+                                 % (self.post_nms, L.SEQ_NMS_MAX_ROWS))
         if self._k > 1:
             self._stream_split()                                  # the graph's own word, before anything touches the GPU
         from .stream import stream_window_slots, ring_size, chunk_slots
@@ -2533,6 +2548,14 @@ class YOLOV3(object):
         self.stream_stats = stats
         self.stream_heads = [torch.cat(h) for h in zip(*heads)] if heads else None
         self.last_rows, self.last_overflow = out['rows'], out['overflow']
+        if seq_kw is not None:
+            self.last_plain = out['ids'], out['scores'], out['bboxes']        # the rows ahead of Seq-NMS
+            boxes = out['bboxes'] if seq_clip is None else out['bboxes'].clamp(0, float(seq_clip))
+            ids, scores, bboxes, perm = ops.seq_nms(out['ids'], out['scores'], boxes,
+                                                    num_class=1 if self.agnostic else self.num_class, **seq_kw)
+            rows = torch.gather(out['rows'], 1, perm.clamp(min=0).long())          # the old row of every output row
+            self.last_rows = torch.where(perm >= 0, rows, torch.full_like(rows, -1))
+            return ids, scores, bboxes
         return out['ids'], out['scores'], out['bboxes']
 
     def extract_features(self, x):

@@ -556,6 +556,55 @@ def coco_match(det, gt, iou_thrs, area_rng, rec_rank, rec_bits, npig):
                                K, _s()), "vd_coco_match")
 
 
+def seq_nms(ids, scores, bboxes, clip_start=None, num_class=1, link_thresh=0.5, nms_thresh=0.3, rescore="avg", ws=None, stages=None):
+    """vd_seq_nms (viddet_amd/seq_nms.py::seq_nms_host on the device, bit for bit): ids (F,N[,1]), scores (F,N[,1]) and bboxes
+    (F,N,4) are contiguous fp32 device tensors, N <= 128; clip_start: None (one clip), V+1 ascending host offsets from 0 to F
+    (checked here, then uploaded) or an int32 device tensor of them (taken as it is).  Returns (ids, scores, bboxes, perm) as new
+    device tensors of the inputs' shapes, perm (F,N) int32.  Launches on the current stream; nothing is downloaded and nothing
+    waits.  ws: a uint8 device tensor of >= 48*F*N bytes to reuse, else one is allocated.  stages (1 or 3; tools/seq_nms_probe.py):
+    only the first one or two of the three launches are made (vd_seq_nms_stages) and the outputs stay unwritten."""
+    from .seq_nms import RESCORE
+    if rescore not in RESCORE:
+        raise ValueError("seq_nms: rescore must be 'avg' or 'max', got %r" % (rescore,))
+    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("seq_nms: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.SEQ_NMS_MAX_ROWS:
+        raise ValueError("seq_nms: N=%d rows per frame, vd_seq_nms takes at most %d" % (N, L.SEQ_NMS_MAX_ROWS))
+    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("seq_nms: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                             % (name, n, t.dtype, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("seq_nms: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("seq_nms: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.SEQ_NMS_WS_PER_ROW * F * N
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("seq_nms: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    out_ids, out_scores, out_bboxes = torch.empty_like(ids), torch.empty_like(scores), torch.empty_like(bboxes)
+    perm = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    if F == 0 or N == 0:
+        return out_ids, out_scores, out_bboxes, perm
+    args = (ptr(ids), ptr(scores), ptr(bboxes), ptr(clip_start), V, F, N, int(num_class), float(link_thresh), float(nms_thresh),
+            RESCORE[rescore], ptr(out_ids), ptr(out_scores), ptr(out_bboxes), ptr(perm), ptr(ws), int(ws.numel()))
+    if stages is None:
+        check(_lib().vd_seq_nms(*args, _s()), "vd_seq_nms")
+    else:
+        check(_lib().vd_seq_nms_stages(*args, int(stages), _s()), "vd_seq_nms_stages")
+    return out_ids, out_scores, out_bboxes, perm
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

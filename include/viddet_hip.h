@@ -325,6 +325,11 @@ int vd_bn_fold_eval(const float* gamma, const float* beta, const float* running_
  * caller) for the fp16 operand scale of the convs that read y (VD_MATH_F16X2) */
 int vd_bn_apply_leaky(const float* x, const float* scale, const float* shift, const float* residual,
                       float* y, int64_t M, int C, float slope, float* amax_out, void* stream);
+/* Launch geometry of vd_bn_apply_leaky / vd_bn_bwd_apply (and their _bf16 forms) over n_vec vectors of 4 (or, for 16-byte
+ * aligned bf16 tensors with C % 8 == 0, 8) channels in cvec vector columns: the number of 256-thread blocks, and in *unroll
+ * (optional) the vectors U a thread handles.  A group of cvec / gcd(256, cvec) blocks owns one contiguous run of U * 256
+ * vectors per block; the grid is one group per run.  For tests and tools: results never depend on it. */
+int vd_bn_stream_grid(int64_t n_vec, int cvec, int* unroll);
 /* backward, pass 1: partial sums of g=dy*leaky'(.) and g*xhat -> sums2[0..C)=sum g, [C..2C)=sum g*xhat */
 int vd_bn_bwd_reduce(const float* x, const float* dy, const float* scale, const float* shift,
                      const float* save_mean, const float* save_invstd, int64_t M, int C, float slope,

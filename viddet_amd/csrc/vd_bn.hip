@@ -327,7 +327,7 @@ __global__ void k_bn_fold_eval(const float* __restrict__ gamma, const float* __r
 // column col = i % cvec never changes along its grid-stride loop - the per-channel constants are loaded (and the fp64
 // sums converted) once per thread instead of once per element, and the 64-bit modulo leaves the loop.
 template <typename T = float>
-__global__ void k_bn_apply_leaky(const T* __restrict__ x, const float* __restrict__ scale,
+__global__ void k_bn_apply_leaky_v0(const T* __restrict__ x, const float* __restrict__ scale,
                                  const float* __restrict__ shift, const T* __restrict__ res,
                                  T* __restrict__ y, int64_t n4, int cvec, float slope, float* __restrict__ amax) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -351,7 +351,7 @@ __global__ void k_bn_apply_leaky(const T* __restrict__ x, const float* __restric
 }
 
 template <typename T = float>
-__global__ void k_bn_bwd_apply(const T* __restrict__ x, const T* __restrict__ dy,
+__global__ void k_bn_bwd_apply_v0(const T* __restrict__ x, const T* __restrict__ dy,
                                const float* __restrict__ scale, const float* __restrict__ shift,
                                const float* __restrict__ mean, const float* __restrict__ invstd,
                                const double* __restrict__ sums2, double count, int64_t n4, int C,
@@ -385,6 +385,166 @@ __global__ void k_bn_bwd_apply(const T* __restrict__ x, const T* __restrict__ dy
         vd_st4(dx, i, o);
         amx = fmaxf(amx, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
     }
+    if (amax) vd_amax_publish(amax, amx);
+}
+
+// ---- the unrolled forms of the two streaming kernels (the default; VD_BN_STREAM=0 keeps the _v0 bodies above) ---------------
+// V channels per thread and access: 4 (a float4, or 8 bytes of bf16) or 8 (16 bytes of bf16).  No grid-stride loop: a group
+// of `step` blocks owns ONE contiguous run of U * span vectors, span = step * 256 being the smallest multiple of 256 that is
+// a multiple of cvec (step = 1 for every power-of-two channel count up to 1024).  Block r of group g handles the vectors
+//     g * U * span + j * span + r * 256 + threadIdx.x,   j = 0 .. U-1,
+// which share one channel column ((r * 256 + threadIdx.x) % cvec), so the per-channel constants are still loaded once per
+// thread.  All loads of every input stream are issued before the first use; the ragged end is a predicate per j.
+// Measured (profiles/r06_bn_stream_sweep.txt): the unroll on the grid-stride layout of the _v0 bodies, resident or not, gains nothing; contiguous
+// runs on a grid sized by the work reach the rate of torch.add on the same traffic.
+// The per-element arithmetic is that of the _v0 bodies, expression for expression: outputs are bit-identical.
+// NT: x and dy are loaded with the nontemporal policy (read for the last time, or not again for a whole pass); res is not.
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+template <int V> struct bn_vec { typedef f32x4 type; };
+template <> struct bn_vec<8> { typedef f32x8 type; };
+
+template <int V, bool NT> struct bn_io;
+template <bool NT> struct bn_io<4, NT> {
+    static __device__ __forceinline__ f32x4 ld(const float* p, int64_t i) {
+        const f32x4* q = reinterpret_cast<const f32x4*>(p) + i;
+        return NT ? __builtin_nontemporal_load(q) : *q;
+    }
+    static __device__ __forceinline__ f32x4 ld(const __bf16* p, int64_t i) {
+        const u32x2* q = reinterpret_cast<const u32x2*>(p) + i;
+        const vd_bf16x4 v = __builtin_bit_cast(vd_bf16x4, NT ? __builtin_nontemporal_load(q) : *q);
+        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+    }
+    template <typename T> static __device__ __forceinline__ void st(T* p, int64_t i, const f32x4 v) { vd_st4(p, i, v); }
+};
+template <bool NT> struct bn_io<8, NT> {
+    static __device__ __forceinline__ f32x8 ld(const __bf16* p, int64_t i) {
+        const u32x4* q = reinterpret_cast<const u32x4*>(p) + i;
+        const vd_bf16x8 v = __builtin_bit_cast(vd_bf16x8, NT ? __builtin_nontemporal_load(q) : *q);
+        f32x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = (float)v[e];
+        return o;
+    }
+    static __device__ __forceinline__ void st(__bf16* p, int64_t i, const f32x8 v) { vd_st8(p, i, v); }
+};
+
+template <int V, typename VEC> __device__ __forceinline__ float bn_vec_amax(float amx, const VEC o) {
+    float m = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
+    if (V == 8) m = fmaxf(m, fmaxf(fmaxf(fabsf(o[4]), fabsf(o[5])), fmaxf(fabsf(o[6]), fabsf(o[7]))));
+    return fmaxf(amx, m);
+}
+
+// a thread's U vectors; FULL: all of them lie inside the tensor, else each is predicated on its index
+template <typename T, int V, int U, bool NT, bool FULL, typename VEC>
+__device__ __forceinline__ void bn_apply_trip(const T* __restrict__ x, const T* __restrict__ res, T* __restrict__ y, int64_t i,
+                                              int64_t stride, int64_t nv, const VEC sc, const VEC sh, float slope, float& amx) {
+    VEC v[U], r[U];
+    bool ok[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        ok[j] = FULL || i + j * stride < nv;
+        if (ok[j]) v[j] = bn_io<V, NT>::ld(x, i + j * stride);
+    }
+    if (res) {
+#pragma unroll
+        for (int j = 0; j < U; ++j)
+            if (ok[j]) r[j] = bn_io<V, false>::ld(res, i + j * stride);
+    }
+    __builtin_amdgcn_sched_barrier(0);      // keep every load of the trip ahead of the first use (the scheduler sinks them)
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        if (!ok[j]) continue;
+        VEC o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float u = v[j][e] * sc[e] + sh[e];
+            o[e] = u > 0.f ? u : u * slope;
+        }
+        if (res) o += r[j];
+        bn_io<V, false>::st(y, i + j * stride, o);
+        amx = bn_vec_amax<V>(amx, o);
+    }
+}
+
+template <typename T, int V, int U, bool NT>
+__global__ __launch_bounds__(256) void k_bn_apply_leaky(const T* __restrict__ x, const float* __restrict__ scale,
+                                                        const float* __restrict__ shift, const T* __restrict__ res,
+                                                        T* __restrict__ y, int64_t nv, int cvec, float slope,
+                                                        float* __restrict__ amax, int step) {
+    typedef typename bn_vec<V>::type VEC;
+    const int64_t span = (int64_t)step * 256;
+    const int64_t i = (int64_t)(blockIdx.x / step) * U * span + (blockIdx.x % step) * 256 + threadIdx.x;
+    const int col = (int)(i % cvec);
+    VEC sc, sh;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        sc[e] = scale[col * V + e];
+        sh[e] = shift[col * V + e];
+    }
+    float amx = 0.f;
+    if (i + (U - 1) * span < nv) bn_apply_trip<T, V, U, NT, true>(x, res, y, i, span, nv, sc, sh, slope, amx);
+    else if (i < nv) bn_apply_trip<T, V, U, NT, false>(x, res, y, i, span, nv, sc, sh, slope, amx);
+    if (amax) vd_amax_publish(amax, amx);
+}
+
+template <typename VEC> struct bn_bwd_consts { VEC sc, sh, mu, is, mg, mgx; };
+
+template <typename T, int V, int U, bool NT, bool FULL, typename VEC>
+__device__ __forceinline__ void bn_bwd_trip(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, int64_t i,
+                                            int64_t stride, int64_t nv, const bn_bwd_consts<VEC>& k, float slope, float& amx) {
+    VEC v[U], d[U];
+    bool ok[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        ok[j] = FULL || i + j * stride < nv;
+        if (ok[j]) {
+            v[j] = bn_io<V, NT>::ld(x, i + j * stride);
+            d[j] = bn_io<V, NT>::ld(dy, i + j * stride);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);      // keep every load of the trip ahead of the first use (the scheduler sinks them)
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+        if (!ok[j]) continue;
+        VEC o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            const float u = v[j][e] * k.sc[e] + k.sh[e];
+            const float g = u > 0.f ? d[j][e] : d[j][e] * slope;
+            const float xh = (v[j][e] - k.mu[e]) * k.is[e];
+            o[e] = k.sc[e] * (g - k.mg[e] - xh * k.mgx[e]);
+        }
+        bn_io<V, false>::st(dx, i + j * stride, o);
+        amx = bn_vec_amax<V>(amx, o);
+    }
+}
+
+template <typename T, int V, int U, bool NT>
+__global__ __launch_bounds__(256) void k_bn_bwd_apply(const T* __restrict__ x, const T* __restrict__ dy,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift,
+                                                      const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                      const double* __restrict__ sums2, double count, int64_t nv, int C,
+                                                      float slope, T* __restrict__ dx, float* __restrict__ amax, int step) {
+    typedef typename bn_vec<V>::type VEC;
+    const int cvec = C / V;
+    const float inv_count = (float)(1.0 / count);
+    const int64_t span = (int64_t)step * 256;
+    const int64_t i = (int64_t)(blockIdx.x / step) * U * span + (blockIdx.x % step) * 256 + threadIdx.x;
+    const int col = (int)(i % cvec);
+    bn_bwd_consts<VEC> k;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        k.sc[e] = scale[col * V + e];
+        k.sh[e] = shift[col * V + e];
+        k.mu[e] = mean[col * V + e];
+        k.is[e] = invstd[col * V + e];
+        k.mg[e] = (float)sums2[col * V + e] * inv_count;
+        k.mgx[e] = (float)sums2[C + col * V + e] * inv_count;
+    }
+    float amx = 0.f;
+    if (i + (U - 1) * span < nv) bn_bwd_trip<T, V, U, NT, true>(x, dy, dx, i, span, nv, k, slope, amx);
+    else if (i < nv) bn_bwd_trip<T, V, U, NT, false>(x, dy, dx, i, span, nv, k, slope, amx);
     if (amax) vd_amax_publish(amax, amx);
 }
 
@@ -424,6 +584,60 @@ int fixed_col_blocks(int64_t n4, int cvec) {
     int64_t nb = stream_blocks(n4);
     nb = vd_cdiv(nb, step) * step;
     return (int)nb;
+}
+
+// developer A/B switch: VD_BN_STREAM=0 runs the one-vector-per-trip _v0 bodies on the fixed_col_blocks grid (read once)
+bool bn_stream_enabled() {
+    static const int v = getenv("VD_BN_STREAM") ? atoi(getenv("VD_BN_STREAM")) : 1;
+    return v != 0;
+}
+
+// tensors from which size on x and dy are loaded nontemporal: below it the streams of a pass fit the 256 MiB Infinity Cache
+// together and the nontemporal loads lose; above it they win alone and in the step
+constexpr int64_t BN_NT_MIN_BYTES = (int64_t)128 << 20;
+constexpr int BN_UNROLL = 4;              // vectors per thread (2 and 4 measured equal; 4 halves the block count)
+
+// blocks per group of the unrolled forms: span = step * 256 is the smallest multiple of 256 that cvec divides
+int stream_step(int cvec) {
+    int a = 256, b = cvec;
+    while (b) { const int t = a % b; a = b; b = t; }          // a = gcd(256, cvec)
+    return cvec / a;
+}
+
+// grid of the unrolled forms over nv vectors: one group of `step` blocks per run of U * step * 256 vectors
+int64_t stream_grid(int64_t nv, int cvec) {
+    const int64_t step = stream_step(cvec);
+    return vd_cdiv(nv, BN_UNROLL * step * 256) * step;
+}
+
+bool aligned16(const void* a, const void* b, const void* c) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+template <typename T, int V>
+void launch_apply(const T* x, const float* scale, const float* shift, const T* res, T* y, int64_t M, int C, float slope,
+                  float* amax, hipStream_t s) {
+    const int cvec = C / V;
+    const int64_t nv = M * cvec;
+    const int step = stream_step(cvec);
+    const dim3 g((unsigned)stream_grid(nv, cvec)), b(256);
+    const bool nt = nv * V * (int64_t)sizeof(T) >= BN_NT_MIN_BYTES;
+#define VD_GO(NT_) hipLaunchKernelGGL((k_bn_apply_leaky<T, V, BN_UNROLL, NT_>), g, b, 0, s, x, scale, shift, res, y, nv, cvec, slope, amax, step)
+    if (nt) VD_GO(true); else VD_GO(false);
+#undef VD_GO
+}
+
+template <typename T, int V>
+void launch_bwd_apply(const T* x, const T* dy, const float* scale, const float* shift, const float* mean, const float* invstd,
+                      const double* sums2, double count, int64_t M, int C, float slope, T* dx, float* amax, hipStream_t s) {
+    const int cvec = C / V;
+    const int64_t nv = M * cvec;
+    const int step = stream_step(cvec);
+    const dim3 g((unsigned)stream_grid(nv, cvec)), b(256);
+    const bool nt = nv * V * (int64_t)sizeof(T) >= BN_NT_MIN_BYTES;
+#define VD_GO(NT_) hipLaunchKernelGGL((k_bn_bwd_apply<T, V, BN_UNROLL, NT_>), g, b, 0, s, x, dy, scale, shift, mean, invstd, sums2, count, nv, C, slope, dx, amax, step)
+    if (nt) VD_GO(true); else VD_GO(false);
+#undef VD_GO
 }
 
 // ---- operand-range guard of the fp16-split arithmetic (VD_MATH_F16X2, include/viddet_hip.h vd_range_guard) ------------
@@ -575,12 +789,21 @@ int vd_bn_fold_eval(const float* gamma, const float* beta, const float* running_
     return VD_OK;
 }
 
+int vd_bn_stream_grid(int64_t n_vec, int cvec, int* unroll) {
+    if (n_vec <= 0 || cvec <= 0) return -1;
+    if (unroll) *unroll = bn_stream_enabled() ? BN_UNROLL : 1;
+    return (int)(bn_stream_enabled() ? stream_grid(n_vec, cvec) : fixed_col_blocks(n_vec, cvec));
+}
+
 int vd_bn_apply_leaky(const float* x, const float* scale, const float* shift, const float* residual, float* y,
                       int64_t M, int C, float slope, float* amax_out, void* stream) {
     VD_REQUIRE(x && scale && shift && y && M > 0 && C > 0 && C % 4 == 0, "vd_bn_apply_leaky: bad args");
     const int64_t n4 = M * (C / 4);
-    hipLaunchKernelGGL(k_bn_apply_leaky<float>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, x, scale, shift,
-                       residual, y, n4, C / 4, slope, amax_out);
+    if (bn_stream_enabled())
+        launch_apply<float, 4>(x, scale, shift, residual, y, M, C, slope, amax_out, (hipStream_t)stream);
+    else
+        hipLaunchKernelGGL(k_bn_apply_leaky_v0<float>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, x, scale,
+                           shift, residual, y, n4, C / 4, slope, amax_out);
     VD_CHECK_LAUNCH("vd_bn_apply_leaky");
     return VD_OK;
 }
@@ -619,8 +842,12 @@ int vd_bn_bwd_apply(const float* x, const float* dy, const float* scale, const f
     VD_REQUIRE(x && dy && scale && shift && save_mean && save_invstd && sums2 && dx && count > 0 && C % 4 == 0,
                "vd_bn_bwd_apply: bad args");
     const int64_t n4 = M * (C / 4);
-    hipLaunchKernelGGL(k_bn_bwd_apply<float>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, x, dy, scale, shift,
-                       save_mean, save_invstd, sums2, count, n4, C, slope, dx, amax_out);
+    if (bn_stream_enabled())
+        launch_bwd_apply<float, 4>(x, dy, scale, shift, save_mean, save_invstd, sums2, count, M, C, slope, dx, amax_out,
+                                   (hipStream_t)stream);
+    else
+        hipLaunchKernelGGL(k_bn_bwd_apply_v0<float>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, x, dy, scale,
+                           shift, save_mean, save_invstd, sums2, count, n4, C, slope, dx, amax_out);
     VD_CHECK_LAUNCH("vd_bn_bwd_apply");
     return VD_OK;
 }
@@ -651,8 +878,14 @@ int vd_bn_apply_leaky_bf16(const void* x, const float* scale, const float* shift
                            int64_t M, int C, float slope, void* stream) {
     VD_REQUIRE(x && scale && shift && y && M > 0 && C > 0 && C % 4 == 0, "vd_bn_apply_leaky_bf16: bad args");
     const int64_t n4 = M * (C / 4);
-    hipLaunchKernelGGL(k_bn_apply_leaky<__bf16>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x,
-                       scale, shift, (const __bf16*)residual, (__bf16*)y, n4, C / 4, slope, (float*)nullptr);
+    const __bf16 *xb = (const __bf16*)x, *rb = (const __bf16*)residual;
+    if (!bn_stream_enabled())
+        hipLaunchKernelGGL(k_bn_apply_leaky_v0<__bf16>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, xb, scale,
+                           shift, rb, (__bf16*)y, n4, C / 4, slope, (float*)nullptr);
+    else if (bf16x8_enabled() && C % 8 == 0 && aligned16(x, residual, y))      // 16 bytes per lane, as the bf16 reductions
+        launch_apply<__bf16, 8>(xb, scale, shift, rb, (__bf16*)y, M, C, slope, (float*)nullptr, (hipStream_t)stream);
+    else
+        launch_apply<__bf16, 4>(xb, scale, shift, rb, (__bf16*)y, M, C, slope, (float*)nullptr, (hipStream_t)stream);
     VD_CHECK_LAUNCH("vd_bn_apply_leaky_bf16");
     return VD_OK;
 }
@@ -686,9 +919,16 @@ int vd_bn_bwd_apply_bf16(const void* x, const void* dy, const float* scale, cons
     VD_REQUIRE(x && dy && scale && shift && save_mean && save_invstd && sums2 && dx && count > 0 && C % 4 == 0,
                "vd_bn_bwd_apply_bf16: bad args");
     const int64_t n4 = M * (C / 4);
-    hipLaunchKernelGGL(k_bn_bwd_apply<__bf16>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, (const __bf16*)x,
-                       (const __bf16*)dy, scale, shift, save_mean, save_invstd, sums2, count, n4, C, slope, (__bf16*)dx,
-                       (float*)nullptr);
+    const __bf16 *xb = (const __bf16*)x, *db = (const __bf16*)dy;
+    if (!bn_stream_enabled())
+        hipLaunchKernelGGL(k_bn_bwd_apply_v0<__bf16>, dim3(fixed_col_blocks(n4, C / 4)), dim3(256), 0, (hipStream_t)stream, xb, db, scale,
+                           shift, save_mean, save_invstd, sums2, count, n4, C, slope, (__bf16*)dx, (float*)nullptr);
+    else if (bf16x8_enabled() && C % 8 == 0 && aligned16(x, dy, dx))
+        launch_bwd_apply<__bf16, 8>(xb, db, scale, shift, save_mean, save_invstd, sums2, count, M, C, slope, (__bf16*)dx,
+                                    (float*)nullptr, (hipStream_t)stream);
+    else
+        launch_bwd_apply<__bf16, 4>(xb, db, scale, shift, save_mean, save_invstd, sums2, count, M, C, slope, (__bf16*)dx,
+                                    (float*)nullptr, (hipStream_t)stream);
     VD_CHECK_LAUNCH("vd_bn_bwd_apply_bf16");
     return VD_OK;
 }

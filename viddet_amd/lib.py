@@ -30,6 +30,7 @@ CONV_PARITY4 = 2048    # vd_conv_desc.flags: a 3x3 / stride-2 data gradient as O
 SK_HEADER_BYTES = 32768
 AMAX_SLOTS, AMAX_STRIDE = 32, 64
 AMAX_FLOATS = AMAX_SLOTS * AMAX_STRIDE      # floats of one tensor's max-abs slots (include/viddet_hip.h)
+BN_STREAM_UNROLL = 4     # vd_bn_stream_grid: vectors per thread of the streaming BatchNorm launches (vd_bn.hip)
 
 _fp = C.c_void_p
 
@@ -111,6 +112,7 @@ SIGNATURES = {
     "vd_bn_sum_finalize": (_i, [_p, _i, _i, _p, _d, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "vd_bn_sum_param_grads": (_i, [_p, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "vd_bn_fold_eval": (_i, [_p, _p, _p, _p, _f, _i, _p, _p, _p]),
+    "vd_bn_stream_grid": (_i, [_i64, _i, _p]),
     "vd_bn_apply_leaky": (_i, [_p, _p, _p, _p, _p, _i64, _i, _f, _p, _p]),
     "vd_bn_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _f, _p, _p, _i64, _p]),
     "vd_bn_param_grads": (_i, [_p, _i, _p, _p, _p]),

@@ -16,8 +16,10 @@ device (vd_vid_match).  `--metrics coco` (the default's second met
 (get_metric :185-186; viddet_amd/coco_metric.py: the behaviour of the reference's wrapper and ground-truth JSON, COCOeval restated) and
 writes coco.txt, `--device_metric` with the per-image matching on the device (vd_coco_match).  `--seq_nms` (no
 reference counterpart) runs sequence NMS over the detections of every clip on the device (vd_seq_nms): the plain
-predictions and results are written as without it, the rescored ones beside them under pred_seq and *_seq.  Visualisation and
-the worst-video tool are out of scope.
+predictions and results are written as without it, the rescored ones beside them under pred_seq and *_seq.  `--track` (no
+reference counterpart) links the detections of every clip into tracks on the device (vd_track): every prediction
+set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
+clip; everything else is written as without the flag.  Visualisation and the worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -116,6 +118,18 @@ def parse_flags(argv=None):
     A("--seq_nms_rescore", default="avg", choices=["avg", "max"], help="--seq_nms: the score a sequence gives its boxes")
     A("--seq_nms_input_nms", type=float, default=0.45,
       help="--seq_nms: the nms_thresh of the per-frame NMS ahead of it (set_nms): higher lets more candidates through")
+    A("--track", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) link the detections of every clip into tracks on the device (vd_track): the IOU tracker of "
+           "Bochinski et al. 2017 - a track takes the unclaimed box of its class with the largest IoU to its last box.  Needs clips "
+           "(--stream or --synthetic_videos).  Every prediction set gets a twin (pred_trk, pred_seq_trk) whose lines end in the "
+           "row's track id (-1: none), and tracks.txt / tracks_seq.txt hold `clip tracks rows mean_len` per clip; everything "
+           "else is written as without the flag (DESIGN.md 28)")
+    A("--track_iou", type=float, default=0.5, help="--track: a box joins a track where its IoU to the track's last box is at least this")
+    A("--track_low", type=float, default=0.0, help="--track: detections scored below this take no part")
+    A("--track_high", type=float, default=0.5, help="--track: a track is kept where its best score is at least this")
+    A("--track_min_len", type=int, default=2, help="--track: a track is kept where it holds at least this many boxes")
+    A("--track_max_age", type=int, default=0,
+      help="--track: the frames in a row a track may go without a box before it is closed, 0 (the paper) to 7")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -141,6 +155,22 @@ def seq_nms_args(FLAGS):
     return dict(link_thresh=FLAGS.seq_nms_link, nms_thresh=FLAGS.seq_nms_thresh, rescore=FLAGS.seq_nms_rescore)
 
 
+def track_args(FLAGS):
+    """the dict net.detect_video and ops.track take, None without --track"""
+    if not getattr(FLAGS, "track", False):
+        return None
+    return dict(sigma_iou=FLAGS.track_iou, sigma_l=FLAGS.track_low, sigma_h=FLAGS.track_high, t_min=FLAGS.track_min_len,
+                max_age=FLAGS.track_max_age)
+
+
+def _collect_tracks(tracks, dataset, ids, track, sidxs):
+    """the track id of every row _collect files, in its order, under the same image path"""
+    ids, track = ids.cpu().numpy(), track.cpu().numpy()
+    for id_, tr, sidx in zip(ids, track, sidxs):
+        valid = np.where(id_.flat >= 0)[0]
+        tracks.setdefault(dataset.sample_path(int(sidx)), []).extend(int(v) for v in tr[valid])
+
+
 def clip_offsets(sidxs, frames_per_video):
     """sample indices in ascending order -> the offsets at which a clip starts (and the end): a clip is a run of consecutive
     frames of one video"""
@@ -151,10 +181,12 @@ def clip_offsets(sidxs, frames_per_video):
     return cs + [len(sidxs)]
 
 
-def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45):
+def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None):
     """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
     (--device_resize: raw frames, resized on the device).  seq_nms (a dict of link_thresh / nms_thresh / rescore): every
-    batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored)."""
+    batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored).
+    track (a dict of ops.track's parameters): the outputs stay on the device likewise and ONE ops.track call per prediction set
+    follows; returns (boxes, rescored or None, tracks, tracks of the rescored or None)."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     boxes = dict()
     if max_do < 0:
@@ -164,17 +196,18 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
     for x, _label, sidxs in loader:
         ids, scores, bboxes = net(torch.from_numpy(x).cuda())
         W = data_shape or (x.shape[-2] if x.dtype == np.uint8 else x.shape[-1])   # uint8 frames are (B,H,W,3)
-        if seq_nms is None:
+        if seq_nms is None and track is None:
             _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         else:                                                              # the plan's output tensors are rewritten by the next batch
             kept.append((ids.clone(), scores.clone(), bboxes.clone(), [int(i) for i in sidxs]))
         c += x.shape[0]
         if c > max_do:
             break
-    if seq_nms is None:
+    if seq_nms is None and track is None:
         return boxes
     from viddet_amd import ops
     boxes_seq = dict()
+    tracks, tracks_seq = dict(), dict()
     if kept:
         sidxs = [i for k in kept for i in k[3]]
         order = sorted(range(len(sidxs)), key=lambda n: sidxs[n])          # clip order: sample = video * frames + frame
@@ -182,25 +215,39 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
         gather = torch.tensor(order, device=kept[0][0].device)
         ids, scores, bboxes = [torch.cat([k[a] for k in kept])[gather].contiguous() for a in range(3)]
         if ids.shape[1] > 128:
-            raise ValueError("--seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most 128" % ids.shape[1])
-        bboxes = bboxes.clamp(0, W)                                        # Seq-NMS sees the boxes as they are saved (:228)
-        out = ops.seq_nms(ids, scores, bboxes, clip_start=clip_offsets(sidxs, dataset.frames_per_video),
-                          num_class=1 if net.agnostic else net.num_class, **seq_nms)
+            raise ValueError("%s: post_nms=%d rows per frame, %s at most 128"
+                             % (("--track", ids.shape[1], "the tracker takes") if seq_nms is None else
+                                ("--seq_nms", ids.shape[1], "Seq-NMS takes")))
+        bboxes = bboxes.clamp(0, W)                                        # Seq-NMS and the tracker see the boxes as they are saved (:228)
+        cs = clip_offsets(sidxs, dataset.frames_per_video)
+        C = 1 if net.agnostic else net.num_class
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
-        _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
-    return boxes, boxes_seq
+        if track is not None:
+            _collect_tracks(tracks, dataset, ids, ops.track(ids, scores, bboxes, clip_start=cs, num_class=C, **track)[0], sidxs)
+        if seq_nms is not None:
+            out = ops.seq_nms(ids, scores, bboxes, clip_start=cs, num_class=C, **seq_nms)
+            _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
+            if track is not None:
+                _collect_tracks(tracks_seq, dataset, out[0], ops.track(out[0], out[1], out[2], clip_start=cs, num_class=C, **track)[0],
+                                sidxs)
+    if track is None:
+        return boxes, boxes_seq
+    return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45):
+                  seq_nms=None, input_nms=0.45, track=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
-    ones detect_video keeps in net.last_plain."""
+    ones detect_video keeps in net.last_plain.  track (a dict): handed to detect_video too, which links the rows it returns;
+    the plain rows ahead of Seq-NMS are linked by a call of their own; returns (boxes, rescored or None, tracks, tracks of the
+    rescored or None)."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
     boxes, boxes_seq = dict(), dict()
+    tracks, tracks_seq = dict(), dict()
     if max_do < 0:
         max_do = len(dataset)
     c = 0
@@ -208,24 +255,35 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         x, _, _ = tf(dataset.video_frames(v), np.zeros((0, 6)))            # uint8 (T,H,W,3), normalised on the device
         sidxs = [dataset.sample_index(v, t) for t in range(x.shape[0])]
         W = data_shape if device_resize else x.shape[-2]
+        trk_kw = {} if track is None else dict(track=dict(track, clip=W))  # the tracker sees the boxes as they are saved too
         if seq_nms is None:
-            ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk)
+            ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, **trk_kw)
+            if track is not None:
+                _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
         else:
             # Seq-NMS sees the boxes as they are saved: clipped to the image (:228)
-            out = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, seq_nms=dict(seq_nms, clip=W))
+            out = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, seq_nms=dict(seq_nms, clip=W), **trk_kw)
             _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
             ids, scores, bboxes = net.last_plain
+            if track is not None:
+                from viddet_amd import ops
+                _collect_tracks(tracks_seq, dataset, out[0], net.last_tracks[0], sidxs)
+                plain = ops.track(ids, scores, bboxes.clamp(0, W), num_class=1 if net.agnostic else net.num_class, **track)
+                _collect_tracks(tracks, dataset, ids, plain[0], sidxs)
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         c += x.shape[0]
         if c > max_do:
             break
+    if track is not None:
+        return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
     return boxes if seq_nms is None else (boxes, boxes_seq)
 
 
-def pred_dir(save_dir, save_prefix, agnostic=False, seq=False):
+def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False):
     """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag;
-    seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq"""
-    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else ""))
+    seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq; trk: the twin of either whose lines end in the
+    track id of --track, `_trk` last"""
+    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + ("_trk" if trk else ""))
 
 
 def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=False):
@@ -253,6 +311,25 @@ def check_flags(FLAGS):
             raise NotImplementedError("--seq_nms_rescore must be avg or max, got %r" % (FLAGS.seq_nms_rescore,))
         if not 0 < getattr(FLAGS, "seq_nms_input_nms", 0.45) < 1:
             raise NotImplementedError("--seq_nms_input_nms must lie inside (0, 1), got %r" % (FLAGS.seq_nms_input_nms,))
+    if getattr(FLAGS, "track", False):
+        # the tracker links the frames of a clip: refused where --seq_nms is, for its reasons
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--track does not combine with several --dataset names: the combined set has no clips")
+        if getattr(FLAGS, "mult_out", False):
+            raise NotImplementedError("--track does not combine with --mult_out: its rows are not the detections of one frame")
+        if not getattr(FLAGS, "stream", False) and getattr(FLAGS, "synthetic_videos", None) is None:
+            raise NotImplementedError("--track needs clips: give --stream or --synthetic_videos (the plain synthetic set is "
+                                      "unrelated still images)")
+        from viddet_amd.track import check_params
+        try:
+            check_params(who="--track", **track_args(FLAGS))
+        except ValueError as e:
+            names = dict(sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high", t_min="--track_min_len",
+                         max_age="--track_max_age")
+            msg = str(e)
+            for k, flag in names.items():
+                msg = msg.replace("--track: " + k, flag)
+            raise NotImplementedError(msg)
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
     for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
@@ -447,14 +524,22 @@ def main(argv=None):
     if seq is not None and not FLAGS.stream and world > 1:
         raise NotImplementedError("--seq_nms without --stream runs on one GPU: the windowed path shards the frames of a clip "
                                   "over the ranks")
+    trk = track_args(FLAGS)
+    if trk is not None:
+        seq_kw = dict(seq_kw, track=trk)
+        if not FLAGS.stream and world > 1:
+            raise NotImplementedError("--track without --stream runs on one GPU: the windowed path shards the frames of a clip "
+                                      "over the ranks")
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
                               **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
-    boxes_seq = None
-    if seq is not None:
+    boxes_seq = tracks = tracks_seq = None
+    if trk is not None:
+        boxes, boxes_seq, tracks, tracks_seq = boxes
+    elif seq is not None:
         boxes, boxes_seq = boxes
     if world > 1:
         # frames are sharded over the ranks (replicas, no collective on the data path); the per-image box lists (host
@@ -469,6 +554,16 @@ def main(argv=None):
             for part in vdist.all_gather_objects(boxes_seq):
                 merged.update(part)
             boxes_seq = merged
+        if trk is not None:
+            gathered = []
+            for part_of in (tracks, tracks_seq):
+                merged = None
+                if part_of is not None:
+                    merged = dict()
+                    for part in vdist.all_gather_objects(part_of):
+                        merged.update(part)
+                gathered.append(merged)
+            tracks, tracks_seq = gathered
         if rank != 0:
             return None
     result = save_and_evaluate(FLAGS, dataset, boxes, save_dir)
@@ -476,7 +571,36 @@ def main(argv=None):
         # the rescored predictions and their results beside the plain ones: pred_seq, vid_seq.txt, coco_seq.txt, ...
         save_and_evaluate(FLAGS, dataset, boxes_seq, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=True),
                           seq=True)
+    if trk is not None:
+        # the tracked twins, after everything a run without --track writes: pred_trk / tracks.txt, pred_seq_trk / tracks_seq.txt
+        for bx, tr, is_seq in ((boxes, tracks, False), (boxes_seq, tracks_seq, True)):
+            if bx is not None:
+                save_tracks(FLAGS, dataset, bx, tr, is_seq)
     return result
+
+
+def save_tracks(FLAGS, dataset, boxes, tracks, seq=False):
+    """--track: the twin of a prediction set - its files' lines with `,track` appended (every row, -1 too) - and one line
+    `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt"""
+    save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=seq, trk=True)
+    os.makedirs(save_dir, exist_ok=True)
+    n = len(dataset) if FLAGS.max_do < 0 else min(FLAGS.max_do, len(dataset))
+    per_clip = [[set(), 0] for _ in range(dataset.num_videos)]
+    for idx in range(n):
+        img_path = dataset.sample_path(idx)
+        file_id = os.path.split(img_path)[1].split(".")[0]
+        rows, ids = boxes.get(img_path, []), tracks.get(img_path, [])
+        assert len(rows) == len(ids), "a track id per saved row"
+        with open(os.path.join(save_dir, file_id + ".txt"), "w") as f:
+            for box, tid in zip(rows, ids):
+                f.write("{},{},{},{},{},{},{},{}\n".format(img_path, box[0], box[1], box[2], box[3], box[4], box[5], tid))
+                if tid >= 0:
+                    per_clip[idx // dataset.frames_per_video][0].add(tid)
+                    per_clip[idx // dataset.frames_per_video][1] += 1
+    out = os.path.join(FLAGS.save_dir, FLAGS.save_prefix, result_name("tracks", FLAGS.model_agnostic, seq=seq) + ".txt")
+    with open(out, "w") as f:
+        for v, (ids, rows) in enumerate(per_clip):
+            f.write("{} {} {} {:.4f}\n".format(v, len(ids), rows, rows / len(ids) if ids else 0.0))
 
 
 def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):

@@ -735,6 +735,27 @@ int vd_seq_nms_stages(const float* ids, const float* scores, const float* bboxes
                       int num_class, float link_thresh, float nms_thresh, int rescore, float* out_ids, float* out_scores,
                       float* out_bboxes, int32_t* out_perm, void* ws, int64_t ws_bytes, int stages, void* stream);
 
+/* ---- The detections of video clips linked into tracks (vd_track.hip): what viddet_amd.track.track_host computes,
+ * bit for bit - the IOU tracker of Bochinski, Eiselein and Sikora (AVSS 2017) with a max_age extension (0 is the paper).  ids,
+ * scores, bboxes, clip_start, V, F, N, num_class: as vd_seq_nms takes them, and a row is a candidate iff it is one there and
+ * score >= sigma_l.  Per clip, frames in order.  Extend: the active tracks in order of creation; a track of class c takes, among
+ * the candidates of class c of the frame that no track has taken, the one with the largest IoU (vd_seq_nms's arithmetic) to the
+ * track's last matched box, ties to the lowest row (a NaN IoU ranks first and matches nothing); where that IoU >= sigma_iou the
+ * row joins, the track's last box is the row's, its miss count 0, its maximum score max(maximum, score); otherwise, or with no
+ * candidate left, the miss count grows by one and the track is closed once it exceeds max_age.  Start: every candidate not taken
+ * starts a track, in row order; a track's id is its creation number within the clip, from 0, one counter for all classes.
+ * Decide, at the clip's end: a track is kept iff its maximum score >= sigma_h and it holds at least t_min rows; ids are not
+ * renumbered.  Outputs, written in full: out_track [F][N] int32 (the row's track id; -1 for a row that is no candidate, of a
+ * dropped track or of a frame that no clip covers), out_len [F][N] int32 (the rows of its track, 0 beside -1), out_score [F][N]
+ * (the track's maximum score, -1 beside -1).  One workgroup per clip, the active tracks (at most N * (max_age + 1) <= 1024) in
+ * LDS; ws holds the length and the maximum of every track made, VD_TRACK_WS_PER_ROW bytes per (frame, row).  1 <= N <= 128,
+ * F >= 1, V >= 1, num_class >= 1, t_min >= 1, 0 <= max_age <= 7, no threshold NaN; bboxes 16-byte, every other pointer 4-byte
+ * aligned.  The inputs are never written.  No atomics, bit-reproducible. */
+#define VD_TRACK_WS_PER_ROW 8
+int vd_track(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
+             int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
+             int32_t* out_len, float* out_score, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@ VID_MATCH_MAX_DET, VID_MATCH_MAX_GT = 1024, 512     # vd_vid_match: the same lim
 COCO_MATCH_MAX_DET, COCO_MATCH_MAX_GT = 1024, 512   # vd_coco_match: the same limits (vd_coco_eval.hip)
 SEQ_NMS_MAX_ROWS = 128                              # vd_seq_nms: rows per frame (vd_seq_nms.hip)
 SEQ_NMS_WS_PER_ROW = 48                             # vd_seq_nms: workspace bytes per (frame, row)
+TRACK_MAX_ROWS, TRACK_MAX_ACTIVE = 128, 1024        # vd_track: rows per frame, active tracks = rows * (max_age + 1) (vd_track.hip)
+TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes per (frame, row) (VD_TRACK_WS_PER_ROW)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -192,6 +194,8 @@ SIGNATURES = {
     # Seq-NMS over the detections of video clips (vd_seq_nms.hip)
     "vd_seq_nms": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),
     "vd_seq_nms_stages": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _i64, _i, _p]),
+    # the detections of video clips linked into tracks (vd_track.hip)
+    "vd_track": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -2434,7 +2434,7 @@ class YOLOV3(object):
         if n < dst.shape[0]:
             dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
 
-    def detect_video(self, frames, step=1, chunk=8, seq_nms=None):
+    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None):
         """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
         (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
         (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
@@ -2450,7 +2450,12 @@ class YOLOV3(object):
         seq_nms: None (the default: the call as it always was), True, or a dict of link_thresh / nms_thresh / rescore - the
         finished clip's rows go through sequence NMS on the device (ops.seq_nms): the rescored, re-sorted
         tensors are returned, last_rows follows the permutation and last_plain holds the three tensors ahead of it.  A
-        further key `clip` (a number) clips the boxes to [0, clip] first, as detect_yolo3.py clips the boxes it saves."""
+        further key `clip` (a number) clips the boxes to [0, clip] first, as detect_yolo3.py clips the boxes it saves.
+
+        track: None (the default), True, or a dict of sigma_l / sigma_h / sigma_iou / t_min / max_age (and `clip`, as above) -
+        the rows the call returns are linked into tracks on the device (ops.track; with seq_nms: the rescored,
+        re-sorted rows).  The returned tensors are what the call returns without it; last_tracks = (track, tlen, tscore),
+        each (T,post_nms), holds the result and is None after a call without `track`."""
         why = self._stream_refusal()
         if why is not None:
             raise NotImplementedError("detect_video with " + why)
@@ -2464,6 +2469,19 @@ class YOLOV3(object):
             if self.post_nms > L.SEQ_NMS_MAX_ROWS:
                 raise ValueError("detect_video with seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most %d"
                                  % (self.post_nms, L.SEQ_NMS_MAX_ROWS))
+        trk_kw = None
+        if track is not None and track is not False:
+            from .track import DEFAULTS, check_params
+            trk_kw = {} if track is True else dict(track)
+            trk_clip = trk_kw.pop("clip", None)
+            unknown = sorted(set(trk_kw) - set(DEFAULTS))
+            if unknown:
+                raise ValueError("detect_video: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age, got %s" % ", ".join(unknown))
+            check_params(who="detect_video with track", **trk_kw)
+            if self.post_nms > L.TRACK_MAX_ROWS:
+                raise ValueError("detect_video with track: post_nms=%d rows per frame, the tracker takes at most %d"
+                                 % (self.post_nms, L.TRACK_MAX_ROWS))
+        self.last_tracks = None
         if self._k > 1:
             self._stream_split()                                  # the graph's own word, before anything touches the GPU
         from .stream import stream_window_slots, ring_size, chunk_slots
@@ -2555,8 +2573,13 @@ class YOLOV3(object):
                                                     num_class=1 if self.agnostic else self.num_class, **seq_kw)
             rows = torch.gather(out['rows'], 1, perm.clamp(min=0).long())          # the old row of every output row
             self.last_rows = torch.where(perm >= 0, rows, torch.full_like(rows, -1))
-            return ids, scores, bboxes
-        return out['ids'], out['scores'], out['bboxes']
+            res = ids, scores, bboxes
+        else:
+            res = out['ids'], out['scores'], out['bboxes']
+        if trk_kw is not None:
+            boxes = res[2] if trk_clip is None else res[2].clamp(0, float(trk_clip))
+            self.last_tracks = ops.track(res[0], res[1], boxes, num_class=1 if self.agnostic else self.num_class, **trk_kw)
+        return res
 
     def extract_features(self, x):
         """extract_base_features.py:127-130: f1 = features[:15](x), f2 = features[15:24](f1), f3 = features[24:](f2) in

@@ -605,6 +605,51 @@ def seq_nms(ids, scores, bboxes, clip_start=None, num_class=1, link_thresh=0.5, 
     return out_ids, out_scores, out_bboxes, perm
 
 
+def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0, ws=None):
+    """vd_track (viddet_amd/track.py::track_host on the device, bit for bit): ids (F,N[,1]), scores (F,N[,1]) and bboxes (F,N,4)
+    are contiguous fp32 device tensors, N <= 128; clip_start as ops.seq_nms takes it.  Returns (track, tlen, tscore), new device
+    tensors (F,N): int32 track ids (-1: no candidate, or a dropped track), int32 track lengths, fp32 track maxima.  Launches on
+    the current stream; nothing is downloaded and nothing waits.  ws: a uint8 device tensor of >= 8*F*N bytes to reuse, else
+    one is allocated."""
+    from .track import check_params
+    sl, sh, si, t_min, max_age = check_params(sigma_l, sigma_h, sigma_iou, t_min, max_age, "track")
+    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("track: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TRACK_MAX_ROWS:
+        raise ValueError("track: N=%d rows per frame, vd_track takes at most %d" % (N, L.TRACK_MAX_ROWS))
+    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("track: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                             % (name, n, t.dtype, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("track: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("track: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TRACK_WS_PER_ROW * F * N
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("track: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    out_track = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    out_len = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    out_score = torch.empty(F, N, dtype=torch.float32, device=bboxes.device)
+    if F == 0 or N == 0:
+        return out_track, out_len, out_score
+    check(_lib().vd_track(ptr(ids), ptr(scores), ptr(bboxes), ptr(clip_start), V, F, N, int(num_class), float(sl), float(sh),
+                          float(si), t_min, max_age, ptr(out_track), ptr(out_len), ptr(out_score), ptr(ws), int(ws.numel()),
+                          _s()), "vd_track")
+    return out_track, out_len, out_score
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

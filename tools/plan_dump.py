@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """The launch records of one training plan as canonical JSON, to show that a change to the plan builder
-(YOLOV3._build_train) leaves every launch as it was: build with one revision, then with the other, compare the files.
+(YOLOV3._build_train, train_plan.TrainPlan) leaves every launch as it was: build with one revision, then with the other, compare the files.
 
-usage: python tools/plan_dump.py ROOT OUT.json [--storage bf16] [--k 3 --join max --pos late] [...]
+usage: python tools/plan_dump.py ROOT OUT.json [--storage bf16] [--k 3 --join max --pos late] [--conv-types 21,21,2,2,2,2] [...]
 
 ROOT is the directory that holds the `viddet_amd` package to import: this tree, or another revision's package staged
 beside it (VD_LIB names the kernel library when that copy has none).  Needs the GPU: the builder allocates its buffers
@@ -10,7 +10,8 @@ there and the autotuner times launch records the tuning table does not hold.
 
 Every record of every segment is written with its entry point, its arguments (scalars as they are, descriptor structs
 field by field), its `meta` and the stream it runs on (main, side or parity i); a python record as `py` or `collective`
-with what its closure holds (events by first appearance, a gradient bucket's lo / hi).  Which arguments are pointers comes
+in one form for every revision's closures: record / wait with the event (by first appearance) and the stream's role, a
+gradient bucket with its lo / hi and stream, a collective with the tensor it reduces.  Which arguments are pointers comes
 from lib.SIGNATURES.  A pointer is written as a named tensor plus a byte offset (the plan's buffers, the weight and gradient
 arenas, the nodes' tensors), any other pointer as a label given at its first appearance.  Run both revisions under one
 copy of the tuning table (VD_TUNE_CACHE): `--expect-tuned 0` on the second run fails when its build added table entries,
@@ -38,6 +39,7 @@ def main():
     ap.add_argument("--corr-d", type=int, default=None)
     ap.add_argument("--rnn-pos", default=None, choices=["late", "out"], help="bidirectional ConvGRU over the window")
     ap.add_argument("--t-out", action="store_true", help="per-frame outputs (k = 5)")
+    ap.add_argument("--conv-types", default=None, help="e.g. 21,21,2,2,2,2 with --k 3: yolo3_3ddarknet (the TdwNode passes)")
     ap.add_argument("--noback", action="store_true")
     ap.add_argument("--freeze-base", action="store_true")
     ap.add_argument("--range-exact", action="store_true", help="two tensors in net._range_exact")
@@ -58,6 +60,9 @@ def main():
     norm = dict(norm_layer="syncbn", norm_kwargs=dict(scope=a.syncbn)) if a.syncbn else {}
     if a.noback:
         net = M.yolo3_no_backbone(classes, **norm)
+    elif a.conv_types:
+        net = M.yolo3_3ddarknet(classes, freeze_base=a.freeze_base, k=a.k, conv_types=[int(c) for c in a.conv_types.split(",")],
+                                **norm)
     else:
         net = M.yolo3_darknet53(classes, freeze_base=a.freeze_base, k=a.k, k_join_type=a.join, k_join_pos=a.pos,
                                 block_conv_type=a.block, t_out=a.t_out, corr_pos=a.corr_pos, corr_d=a.corr_d,
@@ -117,18 +122,28 @@ def main():
         return v
 
     def py(fn, kind):
+        """One description of a python record, whichever revision made its closure: an event record / wait as the event
+        (by first appearance) and the role of the stream it is recorded on / of the stream that waits; a gradient bucket as
+        its arena range and the stream its all-reduce is queued behind; anything else (a collective) as what it holds."""
         code = fn.__code__
         held = dict(zip(code.co_freevars, [c.cell_contents for c in fn.__closure__ or ()]))
         if fn.__defaults__:
             held.update(zip(code.co_varnames[code.co_argcount - len(fn.__defaults__):code.co_argcount], fn.__defaults__))
-        out = {kind: "record" if "record" in code.co_names else "wait" if "wait_event" in code.co_names else "call"}
+        events = [v for v in held.values() if isinstance(v, torch.cuda.Event)]
+        streams = [v for v in held.values() if isinstance(v, torch.cuda.Stream)]
+        assert len(events) <= 1 and len(streams) <= 1, sorted(held)
+        # (closures of older revisions hold the side stream and a flag `on_side` that says whether it is the one meant)
+        st = role(streams[0]) if streams and held.get("on_side", True) else "main"
+        if events:
+            what = "record" if "record" in code.co_names else "wait" if "wait_event" in code.co_names else None
+            assert what, code.co_names
+            return {kind: what, "event": labels.setdefault(("event", id(events[0])), "event%d" % len(labels)), "stream": st}
+        if "lo" in held and "hi" in held:
+            return {kind: "bucket", "lo": held["lo"], "hi": held["hi"], "stream": st}
+        out = {kind: "call", "stream": st}
         for k in sorted(held):
             v = held[k]
-            if isinstance(v, torch.cuda.Event):
-                out[k] = labels.setdefault(("event", id(v)), "event%d" % len(labels))
-            elif isinstance(v, torch.cuda.Stream):
-                out[k] = role(v)
-            elif torch.is_tensor(v):
+            if torch.is_tensor(v):
                 out[k] = ptr(v.data_ptr())
             elif isinstance(v, (bool, int, float)):
                 out[k] = v

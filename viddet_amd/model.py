@@ -282,15 +282,18 @@ class TuneCache(dict):
 _TUNE_CACHE = TuneCache()
 
 
-def _parity_streams():
-    """the four parity launches of a stride-2 data gradient on four streams (+1 % in same-box A/B); read when a plan is
-    built, so a test can build both forms in one process"""
-    return __import__('os').environ.get('VD_PARITY_STREAMS', '1') == '1'
+def ev_record(e, st=None):
+    """python record of a Program: record event e on stream st (None = the stream the program runs on)"""
+    def f():
+        e.record(st if st is not None else torch.cuda.current_stream())
+    return f
 
 
-def _fuse_bwd_s2():
-    """A/B switch: fused BN-backward reductions in stride-2 data gradients (read at plan-build time)"""
-    return __import__('os').environ.get('VD_FUSE_BWD_S2', '1') == '1'
+def ev_wait(e, st=None):
+    """python record of a Program: stream st (None = the stream the program runs on) waits for event e"""
+    def f():
+        (st if st is not None else torch.cuda.current_stream()).wait_event(e)
+    return f
 
 
 def _bf16_pitch(c):
@@ -820,6 +823,60 @@ class TdwNode:
     def __init__(self, name, pname, src, dst, C_, div, K, residual=None):
         self.name, self.pname, self.src, self.dst, self.C, self.div, self.K, self.residual = name, pname, src, dst, C_, div, K, residual
         self.fr = K
+
+
+# ---- graph analysis: pure functions of the node list (no device)
+def node_inputs(n):
+    """The tensors node n reads, in the order its operands are named."""
+    if isinstance(n, (ConvNode, TdwNode)):
+        ins = [n.src, n.residual]
+    elif isinstance(n, UpcatNode):
+        ins = [n.up, n.route]
+    elif isinstance(n, AddNode):
+        ins = [n.a, n.b]
+    else:                                          # PoolNode, CorrNode, SelNode, GruNode
+        ins = [n.src]
+    return [t for t in ins if t]
+
+
+def consumers_of(nodes):
+    """tensor -> the nodes that read it, in node order (the first entry is the earliest forward consumer)"""
+    out = {}
+    for m in nodes:
+        for t in node_inputs(m):
+            out.setdefault(t, []).append(m)
+    return out
+
+
+def single_conv_consumers(nodes):
+    """the rule of YOLOV3.single_conv_consumer_tensors: BatchNorm cells without residual (the stem and the routes apart)
+    whose output has exactly one read, as the operand of a convolution"""
+    use = consumers_of(nodes)
+    return {n.dst for n in nodes if isinstance(n, ConvNode) and n.bn and not n.residual and not n.stem
+            and len(use.get(n.dst, ())) == 1 and isinstance(use[n.dst][0], ConvNode) and use[n.dst][0].src == n.dst
+            and n.dst not in [r[0] for r in ROUTE_TENSORS]}
+
+
+def grad_required(nodes, trainable, is_input):
+    """tensor -> whether backward has to produce its gradient.  grad_req 'null' (wrappers.py:55-57): a tensor needs a
+    gradient only if a trainable parameter sits in its producer or anywhere upstream of it.  With the backbone frozen
+    nothing below the three route tensors does, so the whole backbone drops out of the backward schedule (as MXNet's
+    autograd prunes it) and its weight-gradient launches never run.  `trainable(c)`: a ConvNode (a GruNode's cell convs
+    included) or a TdwNode owns a trainable parameter; `is_input(t)`: t is a network input, the only tensors that may be
+    read without a producer."""
+    need = {}
+    for m in nodes:
+        ins = node_inputs(m)
+        for t in ins:
+            if t not in need:
+                assert is_input(t), "%s reads %s, which nothing produces" % (m.name, t)
+                need[t] = False
+        if isinstance(m, GruNode):
+            own = any(trainable(cn) for _, i2h, h2h in m.cells for cn in (i2h, h2h))
+        else:
+            own = isinstance(m, (ConvNode, TdwNode)) and trainable(m)
+        need[m.dst] = bool(own or any(need[t] for t in ins))
+    return need
 
 
 def check_conv_types(conv_types, k):
@@ -1717,7 +1774,7 @@ class YOLOV3(object):
         return dict(kind=kind, node=cn.name, k=cn.k, stride=1, flops=2.0 * cn.cin * cn.cout * cn.k * cn.k * px,
                     bytes=4.0 * (px * cn.cin + px * cn.cout + cn.cout * cn.cin * cn.k * cn.k))
 
-    def _add_gru_fwd(self, prog, g, bufs, B, H, W, train, side=None, ev_record=None, ev_wait=None):
+    def _add_gru_fwd(self, prog, g, bufs, B, H, W, train, side=None):
         """Forward launches of a GruNode.  Per direction ONE i2h conv over the B*K folded frames, then per step one h2h conv
         on the B frames of the previous state (none at the first step: the state is zero, the gate kernel takes the h2h
         bias) and one gate launch; then the average of the two directions into the folded output.  Training: the reverse
@@ -1728,8 +1785,8 @@ class YOLOV3(object):
         par = train and side is not None
         if par:
             e_x, e_r = torch.cuda.Event(), torch.cuda.Event()
-            prog.add_py(ev_record(e_x, False))
-            prog.add_py(ev_wait(e_x, True))
+            prog.add_py(ev_record(e_x))
+            prog.add_py(ev_wait(e_x, side))
             prog.hold(e_x, e_r)
         for di, (cname, i2h, h2h) in reversed(list(enumerate(g.cells))):      # the side stream's chain is queued first
             st = side if (par and di == 1) else None
@@ -1751,9 +1808,9 @@ class YOLOV3(object):
                          meta=dict(kind='gru_gate_fwd', node=g.name, flops=14.0 * B * hw * g.chp,
                                    bytes=4.0 * B * hw * g.chp * (8 if s_ > 0 else 4)), stream=st)
             if st is not None:
-                prog.add_py(ev_record(e_r, True))
+                prog.add_py(ev_record(e_r, side))
         if par:
-            prog.add_py(ev_wait(e_r, False))
+            prog.add_py(ev_wait(e_r))
         y = bufs[g.dst]
         prog.add('vd_gru_avg', bufs[g.key('l_cell', 'h')].data_ptr(), bufs[g.key('r_cell', 'h')].data_ptr(), y.data_ptr(), B, K,
                  hw * g.chp, bufs['amax:' + g.dst].data_ptr(),
@@ -2086,9 +2143,7 @@ class YOLOV3(object):
                 # the stem and the stride-2 conv behind it as ONE launch (vd_stem_conv_c32_bf16: the stem's 32-channel map is
                 # computed inside the first-stage patch kernel and never stored; same bits) where that conv is the stem's only
                 # reader; VD_STEM_FUSED=0: two launches
-                users = [m for m in nodes if isinstance(m, ConvNode) and (m.src == n.dst or m.residual == n.dst)] + \
-                        [m for m in nodes if not isinstance(m, ConvNode) and n.dst in
-                         [getattr(m, a, None) for a in ('src', 'up', 'route', 'a', 'b')]]
+                users = [m for m in nodes if n.dst in node_inputs(m)]
                 import os
                 fuse_stem = None
                 if (os.environ.get("VD_STEM_FUSED", "1") != "0" and len(users) == 1 and isinstance(users[0], ConvNode)
@@ -2626,772 +2681,9 @@ class YOLOV3(object):
         return n.stem or n.stride == 2
 
     def _build_train(self, B, H, W):
-        """The training plan: forward with the BatchNorm statistics, the loss, then the fixed reverse pass with the
-        weight-gradient GEMMs on a side stream and the bucketed gradient all-reduce queued behind them.  The storage of the
-        activations and their gradients (set_storage) changes the leaves of the schedule only: bf16 storage runs the `_bf16`
-        twins of the elementwise kernels, has no max-abs slots (the fp16-split arithmetic is fp32's) and runs every
-        convolution as vd_conv_igemm_bf16 on bf16 weight images (packed by _refresh_dgrad)."""
-        bf16 = getattr(self, 'storage', 'fp32') == 'bf16'
-        sfx, esz = ('_bf16', 2) if bf16 else ('', 4)
-        dt = torch.bfloat16 if bf16 else torch.float32
-        bufs = self._buffers('train', B, H, W, True, bf16=bf16)
-        dev, lib = self.device, L.load()
-        amx = lambda t: bufs['amax:' + t].data_ptr()
-        amx_arg = lambda t: () if bf16 else (None if t is None else amx(t),)   # the fp32 kernels' trailing max-abs slots
-        ws_bytes = 1 << 20
-        for n in self.conv_nodes:
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            if n.stem:
-                ws_bytes = max(ws_bytes, int(lib.vd_stem_wgrad_ws_bytes(B * n.fr, Hi, Wi)))
-            elif bf16:
-                wd_ = WgradDesc()
-                wd_.N, wd_.Hi, wd_.Wi, wd_.Ci, wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.co_pad
-                ops._set_taps(wd_, n.taps())
-                for fl_ in (0, L.WGRAD_HALO):          # the halo-ring kernel picks its own split count
-                    wd_.in_stride, wd_.Kfr, wd_.flags = n.stride, (n.fr if n.kd > 1 else 1), L.STORE_BF16 | L.MATH_BF16 | fl_
-                    ws_bytes = max(ws_bytes, int(lib.vd_conv_wgrad_ws_bytes(C.byref(wd_))))
-            else:
-                ws_bytes = max(ws_bytes, ops.wgrad_ws_bytes(B * n.fr, Hi, Wi, n.cin, Ho, Wo, n.co_pad, n.k, n.stride,
-                                                            n.pad, n.kd, n.pad_d))
-            ws_bytes = max(ws_bytes, ops.bn_stats_ws_bytes(B * n.fr * Ho * Wo, _bf16_pitch(n.co_pad) if bf16 else n.co_pad))
-        for n in self.tdw_nodes:
-            ws_bytes = max(ws_bytes, int(lib.vd_tdw_bwd_ws_bytes(B, n.K, (H // n.div) * (W // n.div), n.C)))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        world = 1
-        if torch.distributed.is_available() and torch.distributed.is_initialized():
-            world = torch.distributed.get_world_size(self.process_group)
-            # With SyncBN the statistics all-reduces sit on the critical path of backward; on one communicator they
-            # would queue behind a gradient bucket in flight (one RCCL stream per communicator).  The buckets get
-            # their own communicator (new_group is collective: every rank builds its training plan at the same point).
-            if (world > 1 and self.syncbn_scope and self.bucketed_allreduce and self._bucket_group is None
-                    and self.process_group is None):
-                self._bucket_group = torch.distributed.new_group()
-
-        # partial-sum table of the fused BN statistics: rows = M tiles (>= 64 rows each), 2*Cout floats per row
-        smax = 16
-        for n in self.conv_nodes:
-            if n.bn:
-                # (+ 8 rows: the four parity launches of a stride-2 data gradient round their tile counts up separately)
-                # (+ 8 + 4 x 64 rows: every parity launch of every frame chunk rounds its tile count up separately)
-                smax = max(smax, ((B * n.fr * (H // n.div_out) * (W // n.div_out) + 63) // 64 + 8 + 256) * 2 * n.cout)
-        stats_ws = torch.empty(smax, device=dev)
-        # bf16 storage: the forward weight images.  The conv weights live fwd-packed [co_pad][T * Ci] in the arena and need
-        # no padding here (every Ci is 32 or a multiple of 64), so ONE conversion of the arena's weight range makes all of them
-        wb_arena = torch.empty(self.n_weight, dtype=dt, device=dev) if bf16 else None
-
-        def tune(d, of32=0):
-            """fix the tile (and arithmetic) of a conv record, hence its number of M tiles"""
-            if bf16:
-                self._tune_bf16_desc(d, of32)
-            else:
-                autotune_desc(d)
-        mtiles = lib.vd_conv_igemm_bf16_mtiles if bf16 else lib.vd_conv_igemm_mtiles
-
-        def add_conv(d, of32=0, **kw):
-            if bf16:
-                seg.add('vd_conv_igemm_bf16', C.byref(d), of32, **kw)
-            else:
-                seg.add('vd_conv_igemm', C.byref(d), **kw)
-
-        def fwd_desc(n, out):
-            """the forward conv record of node n into `out`"""
-            if not bf16:
-                d = self._conv_desc(n, bufs, B, H, W, out, shift=n.bias if n.head else None)
-                seg.hold(d)
-                return d
-            wb = wb_arena[n.w_off:n.w_off + n.w_numel]
-            assert n.w_numel == n.co_pad * n.T * n.cin and n.w_off % 8 == 0
-            Ho, Wo = H // n.div_out, W // n.div_out
-            d = ConvDesc()
-            self._set_streamk(d, 0)
-            d.in_, d.wp, d.out = bufs[n.src].data_ptr(), wb.data_ptr(), out.data_ptr()
-            d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = B * n.fr, H // n.div_in, W // n.div_in, n.cin, Ho, Wo, n.stride
-            ops._set_taps(d, n.taps())
-            d.Kfr, d.Ho, d.Wo, d.Co = (n.fr if n.kd > 1 else 1), Ho, Wo, n.co_pad
-            d.out_stride, d.out_oy, d.out_ox, d.slope = 1, 0, 0, LEAKY_SLOPE
-            d.ldo = d.ldr = out.shape[-1]                  # (the head: its bf16 pitch)
-            if n.head:
-                d.flags, d.shift = EPI_AFFINE, n.bias.data_ptr()
-            seg.hold(d, wb)
-            return d
-
-        side = torch.cuda.Stream(priority=int(__import__('os').environ.get('VD_SIDE_PRIO', '0'))) if self.overlap_wgrad else None
-
-        def ev_record(e, on_side):
-            def f():
-                e.record(side if on_side else torch.cuda.current_stream())
-            return f
-
-        def ev_wait(e, on_side):
-            def f():
-                (side if on_side else torch.cuda.current_stream()).wait_event(e)
-            return f
-
-        # ---- forward: list of segments; a segment is a Program or a python callable (collectives)
-        fwd, seg = [], Program()
-        if not bf16:
-            self._add_input_stage(seg, bufs, B, H, W)
-        cw_ = 2 if bf16 else 1                             # bf16: the copy kernels move 4-byte words, two channels each
-        for n in self.nodes:
-            if isinstance(n, UpcatNode):
-                o = bufs[n.dst]
-                cw = cw_
-                seg.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
-                        o.shape[1], o.shape[2], n.cu // cw, n.cr // cw)
-                if not bf16:
-                    seg.add('vd_amax_merge', amx(n.up), amx(n.route), amx(n.dst))
-                continue
-            if bf16 and isinstance(n, (SelNode, AddNode)):     # (they occur in the temporal_out / temporal_side nets only)
-                raise NotImplementedError("bf16-storage training: node type %s" % type(n).__name__)
-            if isinstance(n, PoolNode):
-                o, xs = bufs[n.dst], bufs[n.src]
-                if n.type == 2:
-                    # a copy of 16-byte units: bf16 channels go as 4-byte words, two channels each
-                    assert xs.shape[3] % (4 * cw_) == 0, "cat join: C = %d must keep 16-byte units" % xs.shape[3]
-                    seg.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3] // cw_, 0)
-                else:
-                    am = bufs['am:' + n.dst].data_ptr() if n.type == 0 else None
-                    seg.add('vd_temporal_pool_train_bf16' if bf16 else 'vd_temporal_pool', xs.data_ptr(), o.data_ptr(), am, B, n.K,
-                            o[0].numel(), n.type)
-                if not bf16:
-                    seg.add('vd_amax_merge', amx(n.src), None, amx(n.dst))
-                continue
-            if isinstance(n, CorrNode):
-                xs = bufs[n.src]
-                assert xs.shape[3] == n.C and bufs[n.dst].shape[3] == n.ldy
-                seg.add('vd_corr_fwd' + sfx, xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
-                        meta=self._corr_meta(n, B, xs, 'fwd', esz))
-                continue
-            if isinstance(n, (SelNode, AddNode)):
-                self._add_sel_add_fwd(seg, n, bufs, B)
-                continue
-            if isinstance(n, GruNode):
-                self._add_gru_fwd(seg, n, bufs, B, H, W, True, side, ev_record, ev_wait)
-                continue
-            if isinstance(n, TdwNode):
-                self._add_tdw_fwd(seg, n, bufs, B, H, W)
-                continue
-            Ho, Wo = H // n.div_out, W // n.div_out
-            tvalid = getattr(n, 'tvalid', False)
-            M = B * (n.fr - 2 if tvalid else n.fr) * Ho * Wo
-            meta = self._flops(n, B, H, W, 'fwd', esz)
-            if n.head:
-                d = fwd_desc(n, bufs[n.dst])
-                if bf16:
-                    tune(d, 1)
-                add_conv(d, 1, meta=meta)
-                continue
-            z = bufs['z:' + n.dst]
-            if n.stem:
-                # raw conv output + one row of BatchNorm partial sums per 256-pixel block (vd_stem.hip)
-                table_rows = lib.vd_stem_conv_blocks(B * n.fr, H, W)
-                assert table_rows * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
-                self._add_stem(seg, n, bufs, B, H, W, z, bf16=bf16, stats=stats_ws.data_ptr())
-            elif tvalid:
-                # 'same'-padded temporal conv on all frames, the valid ones sliced out, statistics over those
-                zf = bufs['zf:' + n.dst]
-                add_conv(fwd_desc(n, zf), meta=meta)
-                seg.add('vd_frame_slice', zf.data_ptr(), z.data_ptr(), B, n.fr, 1, n.fr - 2, zf[0].numel(), 0)
-                seg.add('vd_bn_stats', z.data_ptr(), M, n.cout, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                table_rows = None
-            elif bf16 or self.fuse_bn_stats:
-                # BN statistics ride in the conv epilogue: one row of partial sums per M tile, reduced in fp64
-                d = fwd_desc(n, z)
-                d.stats_part = stats_ws.data_ptr()
-                tune(d)
-                table_rows = mtiles(C.byref(d))
-                assert table_rows * 2 * n.cout <= stats_ws.numel(), "stats workspace too small"
-                add_conv(d, meta=meta)
-            else:
-                add_conv(fwd_desc(n, z), meta=meta)
-                seg.add('vd_bn_stats', z.data_ptr(), M, n.cout, n.sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                table_rows = None
-            count = float(M)
-            fin = (n.gamma.data_ptr(), n.beta.data_ptr(), BN_EPS, BN_MOMENTUM, n.rmean.data_ptr(), n.rvar.data_ptr(),
-                   n.b_scale.data_ptr(), n.b_shift.data_ptr(), n.b_mean.data_ptr(), n.b_invstd.data_ptr())
-            if table_rows is not None and not self._syncbn(n):
-                # partial table -> fp64 sums -> scale / shift / running statistics in ONE launch (short tables)
-                seg.add('vd_bn_sum_finalize', stats_ws.data_ptr(), table_rows, n.cout, n.sums.data_ptr(), count, *fin,
-                        ws.data_ptr(), ws_bytes)
-            else:
-                if table_rows is not None:
-                    seg.add('vd_bn_sum_partials', stats_ws.data_ptr(), table_rows, n.cout, n.sums.data_ptr(), ws.data_ptr(),
-                            ws_bytes)
-                if self._syncbn(n):
-                    # SyncBN (train_yolov3.py:347-354): the fp64 [sum x, sum x^2] summed over the ranks, then one finalize
-                    # on the global count
-                    seg.add_coll(self._syncbn_exchange(n.sums))
-                    count = float(M * world)
-                seg.add('vd_bn_finalize', n.sums.data_ptr(), count, n.cout, *fin)
-            res = bufs[n.residual].data_ptr() if n.residual else None
-            seg.add('vd_bn_apply_leaky' + sfx, z.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(), res,
-                    bufs[n.dst].data_ptr(), M, n.cout, LEAKY_SLOPE, *amx_arg(n.dst),
-                    meta=dict(node=n.name, bytes=float(esz) * M * n.cout * (3 if n.residual else 2),
-                              single_conv_consumer=not bf16 and n.dst in self.single_conv_consumer_tensors()))
-        # loss (targets are late-bound)
-        grids = self._grid(H, W)
-        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, bufs[self.head_names[0]].shape[-1],
-                                STRIDES[::-1], ANCHORS[::-1], B * self._head_frames, self.num_class)
-        slots = dict(gt=Slot(), M=Slot(), obj=Slot(), ctr=Slot(), scl=Slot(), wgt=Slot(), cls=Slot(), smooth=Slot())
-        losses = torch.zeros(B * self._head_frames, 4, device=dev)
-        dh = (C.c_void_p * 3)(*[bufs['d:' + h].data_ptr() for h in self.head_names])
-        head_node = {m.dst: m for m in self.conv_nodes if m.head}
-        # (an rnn_pos='out' network has no prediction convs: nothing reads the loss gradient as a conv operand)
-        dha = None if (bf16 or not head_node) else (C.c_void_p * 3)(*[amx('dz:' + head_node[h].name) for h in self.head_names])   # max-abs of the three dhead
-        lws = torch.empty(max(16, ops.yolo_loss_ws_bytes(hd)), dtype=torch.uint8, device=dev)
-        seg.hold(hd, dh, dha, lws)
-        seg.add('vd_yolo_loss_fwd_bwd' + sfx, C.byref(hd), slots['gt'], slots['M'], slots['obj'], slots['ctr'], slots['scl'],
-                slots['wgt'], slots['cls'], float(self._ignore_iou_thresh), slots['smooth'], losses.data_ptr(),
-                C.byref(dh), None, *([] if bf16 else [C.byref(dha) if dha is not None else None]), lws.data_ptr(), lws.numel())
-        fwd.append(seg)
-
-        # ---- backward
-        # The weight-gradient GEMMs (MFMA-bound) run on a side stream beside the main-stream chain
-        # [BN backward (HBM-bound) -> data gradient]: nothing in the backward pass consumes a weight gradient,
-        # so the only edges are  dz ready -> wgrad  (event) and  wgrad done -> dz scratch reuse  (event; the dz
-        # scratch is double-buffered), plus one join before the optimiser.  Tails of one GEMM fill with the other.
-        bwd, seg = [], Program()
-        ws_w = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if side is not None else ws
-        dz_bufs = [bufs['dz'], bufs['dz2']]
-        dz_free = [None, None]             # event after which dz_bufs[i] may be overwritten
-        n_dz = [0]
-        last_side = [None]
-        bucket_hi, bucket_acc = [self.n_wconv], [0]     # (the temporal depthwise weights behind n_wconv: allreduce_grads)
-        written = set(self.head_names)     # gradients already produced (the loss kernel wrote d:head*)
-        dgrad_packs = []                   # (node, plan, packed weight buffer) re-packed when weights change
-
-        # d:x of a residual block input x is  dy_block (skip)  +  dgrad(first conv of the block).  The skip term is not
-        # copied: it stays an alias of the block's dy until the dgrad, which reads it as its epilogue residual and
-        # writes d:x out of place (saves a read + write of every block output per step).
-        alias = {}
-        # BatchNorm backward reductions (sum g, sum g*xhat over dy and z) ride in the epilogue of the data-gradient conv
-        # that writes the FINAL dy of a BatchNorm output - the earliest forward consumer, processed last here - when
-        # that conv is a single stride-1 launch; the standalone two-tensor reduction pass is then skipped.
-        producers = {m.dst: m for m in self.conv_nodes if m.bn}
-        consumers = {}
-        for m in self.nodes:
-            srcs = [m.src, m.residual] if isinstance(m, (ConvNode, TdwNode)) else ([m.up, m.route] if isinstance(m, UpcatNode) else
-                                                                          ([m.a, m.b] if isinstance(m, AddNode) else [m.src]))
-            for t in srcs:
-                if t:
-                    consumers.setdefault(t, []).append(m)
-        fused_bwd = set()
-        # grad_req 'null' (wrappers.py:55-57): a tensor needs a gradient only if a trainable parameter sits in its
-        # producer or anywhere upstream of it.  With the backbone frozen nothing below the three route tensors does, so
-        # the whole backbone drops out of the backward schedule (as MXNet's autograd prunes it) and its weight-gradient
-        # launches never run.
-        tgrad = {t: False for t in self.tensors}
-        for m in self.nodes:
-            if isinstance(m, ConvNode):
-                tgrad[m.dst] = any(self._node_trainable(m)) or tgrad[m.src] or bool(m.residual and tgrad[m.residual])
-            elif isinstance(m, UpcatNode):
-                tgrad[m.dst] = tgrad[m.up] or tgrad[m.route]
-            elif isinstance(m, AddNode):
-                tgrad[m.dst] = tgrad[m.a] or tgrad[m.b]
-            elif isinstance(m, TdwNode):
-                tgrad[m.dst] = self._params[m.pname].grad_req != 'null' or tgrad[m.src] or bool(m.residual and tgrad[m.residual])
-            elif isinstance(m, GruNode):
-                tgrad[m.dst] = tgrad[m.src] or any(any(self._node_trainable(cn)) for _, a_, b_ in m.cells for cn in (a_, b_))
-            else:
-                tgrad[m.dst] = tgrad[m.src]
-        wtrain = [m for m in self.conv_nodes if self._node_trainable(m)[0]]
-        first_wtrain = wtrain[0] if wtrain else None       # its weight gradient is the last one backward produces
-
-        def copy_grad(src, dst):
-            """dst = src (the identity form of the BatchNorm apply kernel)"""
-            seg.add('vd_bn_apply_leaky' + sfx, src.data_ptr(), self._ones(src.shape[-1]).data_ptr(),
-                    self._zeros(src.shape[-1]).data_ptr(), None, dst.data_ptr(), src.numel() // src.shape[-1], src.shape[-1],
-                    1.0, *amx_arg(None))
-
-        def materialize(name):
-            if name in alias:
-                copy_grad(alias.pop(name), bufs['d:' + name])
-
-        def grad_into(name, can_alias=False):
-            """Return (dst_ptr, accumulate?) for a producer of d:name."""
-            if name in written:
-                if not can_alias:
-                    materialize(name)
-                return bufs['d:' + name], True
-            written.add(name)
-            return bufs['d:' + name], False
-
-        def add_grad(dsrc, acc, launch):
-            """launch(ptr) writes a gradient contribution to d:src: straight into dsrc, or into tmp then added to dsrc"""
-            target = bufs['tmp'][:dsrc.numel()] if acc else dsrc
-            launch(target.data_ptr())
-            if acc:
-                seg.add('vd_add' + sfx, dsrc.data_ptr(), target.data_ptr(), dsrc.data_ptr(), dsrc.numel())
-
-        def fuse_bn_bwd(d, m, z_off, part_off):
-            """the BatchNorm-backward reductions of node m in the epilogue of data-gradient record d"""
-            d.bs_z = bufs['z:' + m.dst].data_ptr() + z_off
-            d.bs_scale, d.bs_shift = m.b_scale.data_ptr(), m.b_shift.data_ptr()
-            d.bs_mean, d.bs_invstd = m.b_mean.data_ptr(), m.b_invstd.data_ptr()
-            d.bs_part, d.bs_slope = stats_ws.data_ptr() + part_off, LEAKY_SLOPE
-
-        def gru_dgrad(cn, din, nfr, dout, acc, sidx, st, packs):
-            """data gradient of a GRU conv over nfr frames: din [nfr, h, w, 3 chp] -> dout [nfr, h, w, cn.cin] (+= when acc)"""
-            Hc, Wc = H // cn.div_in, W // cn.div_in
-            if cn not in packs:
-                plan = dgrad_plans(cn.k, cn.pad, 1, Hc, Wc)[0]
-                wpk = torch.empty(cn.cin * len(plan['taps']) * cn.co_pad, device=dev)
-                dgrad_packs.append((cn, plan, wpk))
-                packs[cn] = (plan, wpk)
-            plan, wpk = packs[cn]
-            d = ConvDesc()
-            d.in_, d.wp, d.out = din.data_ptr(), wpk.data_ptr(), dout.data_ptr()
-            d.N, d.Hi, d.Wi, d.Ci = nfr, Hc, Wc, cn.co_pad
-            d.Hg, d.Wg, d.in_stride = plan['Hg'], plan['Wg'], 1
-            ops._set_taps(d, plan['taps'])
-            d.Kfr, d.Ho, d.Wo, d.Co = 1, Hc, Wc, cn.cin
-            d.out_stride, d.out_oy, d.out_ox = 1, plan['py'], plan['px']
-            d.ldo = d.ldr = cn.cin
-            d.flags, d.slope = (EPI_RESIDUAL if acc else 0), LEAKY_SLOPE
-            # gate gradients are saturated like the loss gradient: no max-abs slots, so autotune_program (end of the build)
-            # can only choose the fp32 MFMA or the 3-way bf16 split for this record, never the fp16 split
-            d.amax_in, d.amax_w = None, cn.wamax.data_ptr()
-            if acc:
-                d.residual = dout.data_ptr()
-            self._set_streamk(d, sidx)
-            seg.hold(d, wpk)
-            seg.add('vd_conv_igemm', C.byref(d), meta=self._gru_meta(cn, nfr, H, W, 'dgrad'), stream=st)
-
-        def gru_wgrad(cn, xin, dout, nfr, amax_in):
-            """weight gradient of a GRU conv over nfr frames, on the side stream like every weight gradient"""
-            Hc, Wc = H // cn.div_in, W // cn.div_in
-            wd_ = WgradDesc()
-            wd_.in_, wd_.dout, wd_.dwp = xin.data_ptr(), dout.data_ptr(), cn.gwp.data_ptr()
-            wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = nfr, Hc, Wc, cn.cin
-            wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Hc, Wc, cn.co_pad, cn.co_pad
-            wd_.in_stride = 1
-            ops._set_taps(wd_, cn.taps())
-            wd_.Kfr, wd_.splits = 1, 0
-            wd_.amax_in, wd_.amax_dout = amax_in, None
-            autotune_wgrad(wd_, ws.data_ptr(), ws_bytes)
-            seg.hold(wd_)
-            meta = self._gru_meta(cn, nfr, H, W, 'wgrad')
-            if side is not None:
-                e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
-                seg.add_py(ev_record(e_ready, False))
-                seg.add_py(ev_wait(e_ready, True))
-                seg.add('vd_conv_wgrad', C.byref(wd_), ws_w.data_ptr(), ws_bytes, meta=meta, stream=side)
-                seg.add_py(ev_record(e_done, True))
-                seg.hold(e_ready, e_done)
-                last_side[0] = e_done
-            else:
-                seg.add('vd_conv_wgrad', C.byref(wd_), ws.data_ptr(), ws_bytes, meta=meta)
-            bucket_acc[0] += cn.w_numel
-            if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or cn is first_wtrain):
-                lo, hi = cn.w_off, bucket_hi[0]
-                seg.add_py(self._bucket_launcher(lo, hi, side))
-                bucket_hi[0], bucket_acc[0] = lo, 0
-
-        def gru_backward(g):
-            """Backward through time of a GruNode: per direction, steps in reverse - gate backward (dI, dH in place, the
-            state gradient scaled by z), then the h2h data gradient ADDED into that state gradient by its residual epilogue;
-            the reverse direction's chain on the side stream.  Then, batched over time: one i2h data gradient and one i2h
-            weight gradient per direction over the B*K frames, one h2h weight gradient over the B*(K-1) frames that had a
-            state, and the bias gradients as column sums of dI / dH (the head bias's path)."""
-            K, hw = g.K, (H // g.div) * (W // g.div)
-            dy = bufs['d:' + g.dst]
-            packs = {}
-            if side is not None:
-                e_dy, e_r = torch.cuda.Event(), torch.cuda.Event()
-                seg.add_py(ev_record(e_dy, False))
-                seg.add_py(ev_wait(e_dy, True))
-                seg.hold(e_dy, e_r)
-            for di, (cname, i2h, h2h) in reversed(list(enumerate(g.cells))):
-                st = side if (side is not None and di == 1) else None
-                sidx = 4 if st is not None else 0
-                I, Hb, hs, dh = bufs[i2h.dst], bufs[h2h.dst], bufs[g.key(cname, 'h')], bufs[g.key(cname, 'dh')]
-                for s_ in reversed(range(K)):
-                    t = s_ if di == 0 else K - 1 - s_
-                    Hs = Hb[s_ * B:(s_ + 1) * B]
-                    seg.add('vd_gru_gate_bwd', I.data_ptr(), Hs.data_ptr(), 1 if s_ > 0 else 0, h2h.bias.data_ptr(),
-                            hs[(s_ - 1) * B:].data_ptr() if s_ > 0 else None, dy.data_ptr(), 0.5, dh.data_ptr(),
-                            1 if s_ < K - 1 else 0, B, K, t, hw, g.chp,
-                            meta=dict(kind='gru_gate_bwd', node=g.name, flops=30.0 * B * hw * g.chp,
-                                      bytes=4.0 * B * hw * g.chp * (16 if s_ > 0 else 11)), stream=st)
-                    if s_ > 0:
-                        gru_dgrad(h2h, Hs, B, dh, True, sidx, st, packs)
-                if st is not None:
-                    seg.add_py(ev_record(e_r, True))
-            if side is not None:
-                seg.add_py(ev_wait(e_r, False))
-            if tgrad[g.src]:
-                dsrc, acc = grad_into(g.src)
-                for di, (cname, i2h, h2h) in enumerate(g.cells):
-                    gru_dgrad(i2h, bufs[i2h.dst], B * K, dsrc, acc or di > 0, 0, None, packs)
-            for cname, i2h, h2h in g.cells:
-                for cn in (i2h, h2h):
-                    if self._node_trainable(cn)[1]:
-                        dz_ = bufs[cn.dst]
-                        seg.add('vd_bn_stats', dz_.data_ptr(), B * K * hw, cn.co_pad, cn.sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                        seg.add('vd_bn_param_grads', cn.sums.data_ptr(), cn.co_pad, bufs['tmp'].data_ptr(), cn.gbias.data_ptr())
-            for cname, i2h, h2h in reversed(g.cells):                # reverse arena order (the gradient buckets)
-                hs, Hb = bufs[g.key(cname, 'h')], bufs[h2h.dst]
-                if self._node_trainable(h2h)[0]:
-                    gru_wgrad(h2h, hs, Hb[B:], B * (K - 1), None)
-                if self._node_trainable(i2h)[0]:
-                    gru_wgrad(i2h, bufs[g.src], bufs[i2h.dst], B * K, self._amax_or_none(bufs, g.src))
-
-        for n in reversed(self.nodes):
-            if isinstance(n, TdwNode):
-                # backward of the temporal conv, in front of its spatial cell's BatchNorm backward: the skip gradient of a
-                # block is dy itself (alias, as for a 2-D block); ONE launch then writes dx = d:src and the weight
-                # gradient's partial rows, a second folds them (vd_tdw.hip).  dx is left out when nothing upstream needs a
-                # gradient, dw under grad_req 'null'.  It runs on the main stream: its dx is on the critical path and the
-                # weight gradient falls out of the same read of dy.
-                if not tgrad[n.dst]:
-                    continue
-                assert n.dst in written, n.name
-                materialize(n.dst)
-                dy = bufs['d:' + n.dst]
-                if n.residual and tgrad[n.residual]:
-                    dres, acc = grad_into(n.residual)
-                    if acc:
-                        seg.add('vd_add', dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
-                    else:
-                        alias[n.residual] = dy
-                        if not self.alias_skip_grad:
-                            materialize(n.residual)
-                t_train = self._params[n.pname].grad_req != 'null'
-                dxp = None
-                if tgrad[n.src]:
-                    dsrc, acc = grad_into(n.src)
-                    assert not acc, n.name           # the temporal conv is the only reader of its spatial cell
-                    dxp = dsrc.data_ptr()
-                if dxp is not None or t_train:
-                    hw = (H // n.div) * (W // n.div)
-                    seg.add('vd_tdw_bwd', dy.data_ptr(), bufs[n.src].data_ptr(), n.w.data_ptr(), dxp,
-                            n.gw.data_ptr() if t_train else None, B, n.K, hw, n.C, ws.data_ptr(), ws_bytes,
-                            meta=dict(kind='tdw_bwd', node=n.name, flops=(12.0 if t_train else 6.0) * B * n.K * hw * n.C,
-                                      bytes=4.0 * B * n.K * hw * n.C * (1 + (dxp is not None) + t_train)))
-                continue
-            if isinstance(n, GruNode):
-                if tgrad[n.dst]:
-                    assert n.dst in written, n.name
-                    materialize(n.dst)
-                    gru_backward(n)
-                continue
-            if isinstance(n, UpcatNode):
-                if not tgrad[n.dst]:
-                    continue
-                dout = bufs['d:' + n.dst]
-                dup_p = None                               # NULL = that half is not needed (frozen upstream)
-                if tgrad[n.up]:
-                    dup, acc_u = grad_into(n.up)
-                    assert not acc_u
-                    dup_p = dup.data_ptr()
-                launch = lambda p: seg.add('vd_upsample2x_concat_bwd' + sfx, dout.data_ptr(), dup_p, p, B * n.fr,
-                                           dout.shape[1], dout.shape[2], n.cu, n.cr)
-                if tgrad[n.route]:
-                    add_grad(*grad_into(n.route), launch)
-                elif dup_p:
-                    launch(None)
-                continue
-            if isinstance(n, SelNode):
-                if not tgrad[n.src]:
-                    continue
-                assert n.dst in written, n.name
-                materialize(n.dst)
-                dout = bufs['d:' + n.dst]
-                dsrc, acc = grad_into(n.src)
-                add_grad(dsrc, acc, lambda p: seg.add('vd_frame_slice', dout.data_ptr(), p, B, n.K, n.k0, n.kc,
-                                                      dsrc[0].numel(), 1))
-                continue
-            if isinstance(n, AddNode):
-                if not tgrad[n.dst]:
-                    continue
-                assert n.dst in written, n.name
-                materialize(n.dst)
-                dout = bufs['d:' + n.dst]
-                for t_ in (n.a, n.b):
-                    if not tgrad[t_]:
-                        continue
-                    dsrc, acc = grad_into(t_)
-                    if acc:
-                        seg.add('vd_add', dsrc.data_ptr(), dout.data_ptr(), dsrc.data_ptr(), dsrc.numel())
-                    else:
-                        copy_grad(dout, dsrc)
-                continue
-            if isinstance(n, PoolNode):
-                if not tgrad[n.src]:
-                    continue
-                dout = bufs['d:' + n.dst]
-                assert n.dst in written, n.name
-                dsrc, acc = grad_into(n.src)
-                am = bufs['am:' + n.dst].data_ptr() if n.type == 0 else None
-                if n.type == 2:
-                    launch = lambda p: seg.add('vd_temporal_cat', dout.data_ptr(), p, B, n.K, dsrc.shape[1] * dsrc.shape[2],
-                                               dsrc.shape[3] // cw_, 1)
-                else:
-                    launch = lambda p: seg.add('vd_temporal_pool_bwd' + sfx, dout.data_ptr(), am, p, B, n.K, dout[0].numel(), n.type)
-                add_grad(dsrc, acc, launch)
-                continue
-            if isinstance(n, CorrNode):
-                if not tgrad[n.src]:
-                    continue
-                assert n.dst in written, n.name
-                materialize(n.dst)
-                dout, xs = bufs['d:' + n.dst], bufs[n.src]
-                dsrc, acc = grad_into(n.src)
-                # columns [Cc, ldy) of d:dst are never read (vd_corr.hip), and what writes them is an exact zero: the consumers'
-                # pad weight rows are exact zeros in fp32, so in their bf16 images, so in the data gradient made from those
-                add_grad(dsrc, acc, lambda p: seg.add('vd_corr_bwd' + sfx, dout.data_ptr(), xs.data_ptr(), p, B, n.K, xs.shape[1],
-                                                      xs.shape[2], n.C, n.d, n.ldy, meta=self._corr_meta(n, B, xs, 'bwd', esz)))
-                continue
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            tvalid = getattr(n, 'tvalid', False)
-            M = B * (n.fr - 2 if tvalid else n.fr) * Ho * Wo
-            if not tgrad[n.dst]:
-                continue                   # frozen, and nothing trainable upstream: no gradient is needed here
-            w_train, v_train = self._node_trainable(n)
-            dy = bufs['d:' + n.dst]
-            assert n.dst in written, n.name
-            materialize(n.dst)
-            if n.head:
-                dz = dy
-                # bias gradient = per-channel sum of dz over its row pitch (reuses the BN column-sum kernels); the dgamma
-                # slot of the parameter-gradient kernel is scratch
-                sums = n.sums
-                if bf16:                   # (the bf16 pitch may be wider than n.sums)
-                    if getattr(n, 'sums_b', None) is None or n.sums_b.numel() != 2 * dz.shape[-1]:
-                        n.sums_b = torch.zeros(2 * dz.shape[-1], dtype=torch.float64, device=dev)
-                    sums = n.sums_b
-                seg.add('vd_bn_stats' + sfx, dz.data_ptr(), M, dz.shape[-1], sums.data_ptr(), ws.data_ptr(), ws_bytes)
-                seg.add('vd_bn_param_grads', sums.data_ptr(), n.co_pad, bufs['tmp'].data_ptr(), n.gbias.data_ptr())
-            else:
-                if n.residual and tgrad[n.residual]:
-                    dres, acc = grad_into(n.residual)
-                    if acc:
-                        seg.add('vd_add' + sfx, dres.data_ptr(), dy.data_ptr(), dres.data_ptr(), dy.numel())
-                    else:
-                        alias[n.residual] = dy     # first producer of the skip gradient: it IS dy (no copy, see alias)
-                        if not self.alias_skip_grad:
-                            materialize(n.residual)
-                z = bufs['z:' + n.dst]
-                slot = n_dz[0] % 2
-                n_dz[0] += 1
-                dz = dz_bufs[slot][:M * n.cout].view(-1, Ho, Wo, n.cout)
-                if n.name not in fused_bwd:      # (fused: sums and gamma / beta gradients came with the table reduction)
-                    seg.add('vd_bn_bwd_reduce' + sfx, z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
-                            n.b_mean.data_ptr(), n.b_invstd.data_ptr(), M, n.cout, LEAKY_SLOPE, n.sums2.data_ptr(),
-                            ws.data_ptr(), ws_bytes)
-                    seg.add('vd_bn_param_grads', n.sums2.data_ptr(), n.cout, n.ggamma.data_ptr(), n.gbeta.data_ptr())
-                count = float(M)
-                if self._syncbn(n):          # [sum g, sum g xhat] over the ranks (the local gamma / beta gradients came first)
-                    seg.add_coll(self._syncbn_exchange(n.sums2))
-                    count = float(M * world)
-                if side is not None and dz_free[slot] is not None:
-                    seg.add_py(ev_wait(dz_free[slot], False))       # the wgrad that read this scratch has finished
-                seg.add('vd_bn_bwd_apply' + sfx, z.data_ptr(), dy.data_ptr(), n.b_scale.data_ptr(), n.b_shift.data_ptr(),
-                        n.b_mean.data_ptr(), n.b_invstd.data_ptr(), n.sums2.data_ptr(), count, M, n.cout, LEAKY_SLOPE,
-                        dz.data_ptr(), *amx_arg('dz:' + n.name))
-                if tvalid:
-                    # the gradient of the frame slice: dz of the valid frames, zeros on the two border frames; the conv's
-                    # weight / data gradients then are those of the 'same'-padded conv
-                    dzf = bufs['dzf:' + n.dst]
-                    seg.add('vd_frame_slice', dz.data_ptr(), dzf.data_ptr(), B, n.fr, 1, n.fr - 2, dzf[0].numel(), 1)
-                    dz = dzf
-            # weight gradient straight into the gradient arena (same fwd-packed layout as the weights)
-            if w_train:
-                if n.stem:
-                    # both operands straight from global memory: the NCHW batch and dz (vd_stem.hip)
-                    wargs = ('vd_stem_wgrad' + sfx, bufs['in'].data_ptr(), dz.data_ptr(), n.co_pad, n.gwp.data_ptr(),
-                             B * n.fr, Hi, Wi)
-                else:
-                    wd_ = WgradDesc()
-                    wd_.in_, wd_.dout, wd_.dwp = bufs[n.src].data_ptr(), dz.data_ptr(), n.gwp.data_ptr()
-                    wd_.N, wd_.Hi, wd_.Wi, wd_.Ci = B * n.fr, Hi, Wi, n.ci_eff
-                    wd_.Hg, wd_.Wg, wd_.Co, wd_.ldd = Ho, Wo, n.co_pad, dz.shape[-1]
-                    wd_.in_stride = n.stride
-                    ops._set_taps(wd_, n.taps())
-                    wd_.Kfr, wd_.splits = (n.fr if n.kd > 1 else 1), 0
-                    if bf16:
-                        wd_.flags = L.STORE_BF16 | L.MATH_BF16
-                        autotune_wgrad_bf16(wd_, ws.data_ptr(), ws_bytes)
-                    else:
-                        wd_.amax_in, wd_.amax_dout = self._amax_or_none(bufs, n.src), self._amax_or_none(bufs, 'dz:' + n.name)
-                        autotune_wgrad(wd_, ws.data_ptr(), ws_bytes)
-                    seg.hold(wd_)
-                    wargs = ('vd_conv_wgrad', C.byref(wd_))
-                meta = self._flops(n, B, H, W, 'wgrad', esz)
-                if side is not None:
-                    e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
-                    seg.add_py(ev_record(e_ready, False))
-                    seg.add_py(ev_wait(e_ready, True))
-                    seg.add(*wargs, ws_w.data_ptr(), ws_bytes, meta=meta, stream=side)
-                    seg.add_py(ev_record(e_done, True))
-                    seg.hold(e_ready, e_done)
-                    if not n.head:
-                        dz_free[slot] = e_done
-                    last_side[0] = e_done
-                else:
-                    seg.add(*wargs, ws.data_ptr(), ws_bytes, meta=meta)
-                # bucketed gradient all-reduce, overlapped with the rest of the backward pass: weight gradients complete
-                # in reverse arena order on the stream that runs the wgrad GEMMs, so every time a bucket (~32 MB) of the arena tail
-                # is final an async all-reduce of that contiguous range is queued behind them (RCCL syncs with that
-                # stream); allreduce_grads() later waits for the handles and reduces the small gamma/beta/bias range.
-                # The stem is the first conv: its bucket closes the arena.
-                bucket_acc[0] += n.w_numel
-                if self.bucketed_allreduce and (bucket_acc[0] >= self.bucket_elems or n is first_wtrain or n.stem):
-                    lo, hi = n.w_off, bucket_hi[0]
-                    seg.add_py(self._bucket_launcher(lo, hi, side))
-                    bucket_hi[0], bucket_acc[0] = lo, 0
-            if n.stem or n.src in self.input_tensors or not tgrad[n.src]:     # no gradient flows into the network inputs,
-                continue                                                       # nor below the last trainable parameter
-            # data gradient into d:src
-            dsrc, acc = grad_into(n.src, can_alias=True)
-            res_src = alias.pop(n.src) if n.src in alias else dsrc      # the skip gradient, still living in the block's dy
-            plans = dgrad_plans(n.k, n.pad, n.stride, Hi, Wi, n.kd, n.pad_d)
-            pm = producers.get(n.src)
-            # the producer's BatchNorm-backward reductions ride in this data gradient's epilogue when it is the launch (or, for a
-            # stride-2 conv, the four parity launches) that completes dy of the producer's output.  (bf16 storage: off by
-            # default, VD_FUSE_BWD_BF16=1: measured on one box, 416 / batch 64, 1992 frames/s with the stand-alone reduction
-            # passes against 1958 fused - the HBM-bound pass runs beside the side stream's MFMA-bound weight gradients, the
-            # fused epilogue lengthens the data gradients on the critical path)
-            fuse_m = pm if (pm is not None and consumers[n.src][0] is n and
-                            (__import__('os').environ.get('VD_FUSE_BWD_BF16', '0') == '1' if bf16 else
-                             self.fuse_bn_bwd and (len(plans) == 1 or (n.kd == 1 and _fuse_bwd_s2())) and pm.fr == n.fr)) else None
-            bs_rows = 0
-            # ---- a 3x3 / stride-2 data gradient as ONE launch (VD_CONV_PARITY4, vd_conv_par.hip) instead of four parity
-            # launches that each gather and stage the whole dz: rows = positions of dz's grid, columns = (parity class,
-            # channel), taps = the four offsets of a 2x2 window, zero (offset, class) weight blocks skipped.
-            # VD_S2_FUSED=0 keeps the four launches (also: odd maps, other arithmetics, range-exact operands, pinned kernels).
-            import os as _os
-            fused_s2 = (not bf16 and len(plans) == 4 and n.k == 3 and n.stride == 2 and n.pad == 1 and n.kd == 1 and
-                        Hi % 2 == 0 and Wi % 2 == 0 and _os.environ.get('VD_S2_FUSED', '1') == '1' and n.cin % 32 == 0 and
-                        # (measured per layer, batch 64 / 416x416, four launches -> one: 32 channels 1.51 -> 1.12 ms, 64: 0.80 ->
-                        # 0.80, 128: 0.55 -> 0.66, 256: 0.53 -> 0.59, 512: 0.47 -> 0.53 - the one launch stages all sixteen
-                        # (offset, class) weight blocks for nine useful ones, which only pays where a parity launch has too few
-                        # output channels to fill a tile; VD_S2_FUSED_MAX_CIN moves the limit)
-                        n.cin <= int(_os.environ.get('VD_S2_FUSED_MAX_CIN', '64')) and
-                        self._amax_or_none(bufs, 'dz:' + n.name) is not None and
-                        (fp32_math() == 'split2' or (fp32_math() == 'auto' and _os.environ.get('VD_AUTOTUNE', '1') != '0')))
-            if fused_s2:
-                wp4 = torch.empty(16 * n.cin * n.co_pad, device=dev)
-                dgrad_packs.append((n, dict(fused_s2=True), wp4))
-                d = ConvDesc()
-                d.in_, d.wp, d.out = dz.data_ptr(), wp4.data_ptr(), dsrc.data_ptr()
-                d.N, d.Hi, d.Wi, d.Ci = B * n.fr, Ho, Wo, n.co_pad
-                d.Hg, d.Wg, d.in_stride = Ho, Wo, 1
-                ops._set_taps(d, ops.PARITY4_TAPS)
-                d.Kfr, d.Ho, d.Wo, d.Co = 1, Hi, Wi, 4 * n.cin
-                d.out_stride, d.out_oy, d.out_ox = 2, 0, 0
-                d.ldo = d.ldr = n.cin
-                d.par_cin, d.par_mask = n.cin, ops.PARITY4_MASK   # (offset, class) blocks that hold a kernel tap
-                d.flags, d.slope = (EPI_RESIDUAL if acc else 0) | L.MATH_F16X2 | L.CONV_PARITY4, LEAKY_SLOPE
-                d.amax_in, d.amax_w = self._amax_or_none(bufs, 'dz:' + n.name), n.wamax.data_ptr()
-                if acc:
-                    d.residual = res_src.data_ptr()
-                seg.hold(d, wp4)
-                if fuse_m is not None:
-                    fuse_bn_bwd(d, fuse_m, 0, 0)
-                autotune_desc(d)                                   # fixes the tile, hence the rows of the partial table
-                if fuse_m is not None:
-                    mt = lib.vd_conv_igemm_mtiles(C.byref(d))
-                    assert mt * 2 * fuse_m.cout <= stats_ws.numel(), "stats workspace too small"
-                    seg.add('vd_fill', stats_ws.data_ptr(), 0.0, mt * 2 * fuse_m.cout)     # column tiles narrower than Cin fill part of a row
-                seg.add('vd_conv_igemm', C.byref(d), meta=dict(
-                    kind='dgrad', node=n.name, k=n.k, stride=n.stride, fused_s2=True,
-                    flops=2.0 * n.cin * n.cout * 9 * Ho * Wo * B * n.fr, bytes=self._flops(n, B, H, W, 'dgrad')['bytes']))
-                if fuse_m is not None:
-                    seg.add('vd_bn_sum_param_grads', stats_ws.data_ptr(), mt, fuse_m.cout, fuse_m.sums2.data_ptr(),
-                            fuse_m.ggamma.data_ptr(), fuse_m.gbeta.data_ptr(), ws.data_ptr(), ws_bytes)
-                    fused_bwd.add(fuse_m.name)
-                continue
-            # Frame chunks of a stride-2 data gradient (VD_S2_CHUNK_MB > 0; default 0 = one launch per parity class): each of
-            # the four parity launches streams the WHOLE incoming gradient dz - 709 MB at 208 x 208 x 64 channels, batch 64 - and
-            # is HBM-bound on it (isolated: 5.9 TB/s on the one-tap class).  Cut into chunks of frames whose dz fits the 256 MB
-            # Infinity Cache beside the outputs, the second to fourth class of a chunk find dz there: one HBM read instead of four.
-            NF = B * n.fr
-            nchunks = 1
-            # (measured, same box, batch 64 / 416x416: off 1022.0 frames/s, 192 MB 1021.9, 96 MB 1018.6, 48 MB 991.5 - the
-            # four launches already share most of dz through the L2s / Infinity Cache when they run side by side on their
-            # four streams; the default stays off, the switch and its parity test stay as the record of the experiment)
-            chunk_mb = float(__import__('os').environ.get('VD_S2_CHUNK_MB', '0'))
-            if not bf16 and len(plans) == 4 and n.kd == 1 and chunk_mb > 0:
-                dz_mb = 4.0 * NF * Ho * Wo * n.co_pad / 1e6
-                nchunks = max(1, min(NF, int(math.ceil(dz_mb / chunk_mb))))
-            fchunk = (NF + nchunks - 1) // nchunks
-            nchunks = (NF + fchunk - 1) // fchunk
-            kp = dz.shape[-1]                                   # K dimension of the data gradient (the bf16 head: its pitch)
-            wpks = []
-            for plan in plans:
-                assert plan['taps'], "a parity class without taps would leave its gradient unwritten"
-                wpk = torch.empty(n.cin * len(plan['taps']) * kp, dtype=dt, device=dev)
-                dgrad_packs.append((n, plan, wpk))
-                wpks.append(wpk)
-            in_img, out_img = Ho * Wo * kp * esz, Hi * Wi * n.cin * esz        # bytes per frame of dz / of d:src
-            for ch in range(nchunks):
-              f0 = ch * fchunk
-              fn_ = min(NF, f0 + fchunk) - f0
-              # the four parity launches of a stride-2 data gradient write disjoint pixels and read the same dz: run them
-              # side by side on their own streams (VD_PARITY_STREAMS=1) so that they share dz in the L2s and fill each other's tails
-              par = None
-              if not bf16 and _parity_streams() and len(plans) == 4 and self.overlap_wgrad:
-                if getattr(self, '_par_streams', None) is None:
-                    self._par_streams = [torch.cuda.Stream() for _ in range(3)]
-                par = self._par_streams
-                e_fork = torch.cuda.Event()
-                seg.add_py(lambda e=e_fork: e.record(torch.cuda.current_stream()))
-                for st in par:
-                    seg.add_py(lambda e=e_fork, st=st: st.wait_event(e))
-              for pi, plan in enumerate(plans):
-                wpk = wpks[pi]
-                d = ConvDesc()
-                d.in_, d.wp, d.out = dz.data_ptr() + f0 * in_img, wpk.data_ptr(), dsrc.data_ptr() + f0 * out_img
-                d.N, d.Hi, d.Wi, d.Ci = fn_, Ho, Wo, kp
-                d.Hg, d.Wg, d.in_stride = plan['Hg'], plan['Wg'], 1
-                ops._set_taps(d, plan['taps'])
-                d.Kfr = n.fr if n.kd > 1 else 1
-                d.Ho, d.Wo, d.Co = Hi, Wi, n.cin
-                d.out_stride, d.out_oy, d.out_ox = n.stride, plan['py'], plan['px']
-                d.ldo = d.ldr = n.cin
-                d.flags, d.slope = (EPI_RESIDUAL if acc else 0), LEAKY_SLOPE
-                if not bf16:
-                    d.amax_in, d.amax_w = self._amax_or_none(bufs, 'dz:' + n.name), n.wamax.data_ptr()
-                self._set_streamk(d, pi if (par is not None) else 0)
-                if acc:
-                    d.residual = res_src.data_ptr() + f0 * out_img
-                seg.hold(d, wpk)
-                nplans = n.stride * n.stride
-                if fuse_m is not None:
-                    fuse_bn_bwd(d, fuse_m, f0 * out_img, bs_rows * 2 * fuse_m.cout * 4)
-                if bf16 or fuse_m is not None:
-                    tune(d)
-                if fuse_m is not None:
-                    bs_rows += mtiles(C.byref(d))
-                    assert bs_rows * 2 * fuse_m.cout <= stats_ws.numel(), "stats workspace too small"
-                add_conv(d, meta=dict(
-                    kind='dgrad', node=n.name, k=n.k, stride=n.stride,
-                    flops=2.0 * n.cin * n.cout * len(plan['taps']) * plan['Hg'] * plan['Wg'] * fn_,
-                    bytes=self._flops(n, B, H, W, 'dgrad', esz)['bytes'] / nplans * fn_ / NF),
-                    stream=(par[pi - 1] if (par is not None and pi > 0) else None))
-                if par is not None and pi == len(plans) - 1:
-                    for st in par:                                  # join before anything reads d:src or the partial table
-                        e_join = torch.cuda.Event()
-                        seg.add_py(lambda e=e_join, st=st: e.record(st))
-                        seg.add_py(lambda e=e_join: torch.cuda.current_stream().wait_event(e))
-                if fuse_m is not None and pi == len(plans) - 1 and ch == nchunks - 1:
-                    seg.add('vd_bn_sum_param_grads', stats_ws.data_ptr(), bs_rows, fuse_m.cout, fuse_m.sums2.data_ptr(),
-                            fuse_m.ggamma.data_ptr(), fuse_m.gbeta.data_ptr(), ws.data_ptr(), ws_bytes)
-                    fused_bwd.add(fuse_m.name)
-        if side is not None and last_side[0] is not None:
-            seg.add_py(ev_wait(last_side[0], False))          # join: the optimiser / all-reduce see every gradient
-        seg.hold(ws_w, side, stats_ws)
-        bwd.append(seg)
-        for sg in fwd + bwd:
-            if isinstance(sg, Program):
-                autotune_program(sg)
-        _TUNE_CACHE.save()
-        return dict(fwd=fwd, bwd=bwd, bufs=bufs, slots=slots, losses=losses, dgrad_packs=dgrad_packs, ws=ws,
-                    wb_arena=wb_arena, storage='bf16' if bf16 else 'fp32')
-
+        """The training plan at one shape (train_plan.TrainPlan): forward with the BatchNorm statistics, the loss, then the
+        fixed reverse pass, as segments of launch records, with the buffers and workspaces they point into."""
+        return train_plan.TrainPlan(self, B, H, W).build()
 
     # ------------------------------------------------------------------ bf16-STORAGE training (BASELINE configs[4])
     def set_storage(self, storage):
@@ -3454,6 +2746,9 @@ class YOLOV3(object):
         return dict(kind='corr_' + kind, flops=flops, bytes=byt)
 
     def _ones(self, c):
+        """c ones (_zeros: c zeros): the first c elements of one 1024-element constant, wide enough for every tensor of
+        today's networks (1024 channels); a wider one fails here, when the plan is built"""
+        assert c <= 1024, "constant vectors hold 1024 channels, asked for %d" % c
         if not hasattr(self, '_const'):
             self._const = (torch.ones(1024, device=self.device), torch.zeros(1024, device=self.device))
         return self._const[0]
@@ -3514,17 +2809,7 @@ class YOLOV3(object):
         """Outputs of Conv+BN+LeakyReLU cells (no residual) that are read by exactly one node, a convolution: the cells whose
         forward BatchNorm apply could move into the consumer's operand gather (bench.py reports their share)."""
         if getattr(self, '_scc', None) is None:
-            use = {}
-            for n in self.nodes:
-                srcs = []
-                if isinstance(n, ConvNode):
-                    srcs = [(n.src, True)] + ([(n.residual, False)] if n.residual else [])
-                else:
-                    srcs = [(getattr(n, a), False) for a in ('src', 'up', 'route', 'a', 'b') if getattr(n, a, None)]
-                for t, conv in srcs:
-                    use.setdefault(t, []).append(conv)
-            self._scc = {n.dst for n in self.conv_nodes if n.bn and not n.residual and not n.stem
-                         and use.get(n.dst) == [True] and n.dst not in [r[0] for r in ROUTE_TENSORS]}
+            self._scc = single_conv_consumers(self.nodes)
         return self._scc
 
     def _drop_plans(self, keep=None):
@@ -3867,3 +3152,6 @@ def yolo3_no_backbone(classes, norm_layer=None, norm_kwargs=None, **kwargs):
     if norm_layer == 'syncbn':
         scope = (norm_kwargs or {}).get('scope', 'all')
     return YOLOV3(classes, syncbn_scope=scope, noback=True, **kwargs)
+
+
+from . import train_plan  # noqa: E402  (last: train_plan imports the node classes, Program and the tuners from this module)

@@ -18,6 +18,7 @@ reverse schedule of this one graph.
 """
 import ctypes as C
 import math
+import os
 import re
 from collections import OrderedDict
 
@@ -29,7 +30,7 @@ from . import ops
 from .lib import ConvDesc, WgradDesc, EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL
 from .ops import round_up, fwd_taps, dgrad_plans
 
-from .consts import ANCHORS, STRIDES, BN_EPS, BN_MOMENTUM, LEAKY_SLOPE   # wrappers.py:80-84, layers.py:68-69
+from .consts import BN_EPS, BN_MOMENTUM, LEAKY_SLOPE   # layers.py:68-69
 
 
 class Slot:
@@ -146,7 +147,6 @@ class TuneCache(dict):
     @staticmethod
     def library_id():
         import hashlib
-        import os
         here = os.path.dirname(os.path.abspath(__file__))
         # the conv kernels' sources (the public header is not part of it: declarations of other entry points change there
         # without touching a tile; descriptor layouts are guarded by the ABI revision)
@@ -166,7 +166,6 @@ class TuneCache(dict):
         return h.hexdigest()[:12]
 
     def path(self):
-        import os
         p = os.environ.get("VD_TUNE_CACHE", "")
         if p.lower() in ("off", "0", "none"):
             return None
@@ -190,7 +189,6 @@ class TuneCache(dict):
     def _read_file(self):
         import ast
         import json
-        import os
         out = {}
         p = self.path()
         if p is None or not os.path.exists(p):
@@ -214,7 +212,6 @@ class TuneCache(dict):
         broadcast at first use): ranks that read their own copies - another node's file system, another VD_TUNE_CACHE,
         a file rank 0 has rewritten since - would disagree on hit or miss, and the ranks that miss would enter `agree`'s
         broadcast alone.  After this every lookup gives the same answer on every rank, so `agree` is entered by all or none."""
-        import os
         self._loaded = True
         world = self._world()
         self._synced_world = world
@@ -248,7 +245,6 @@ class TuneCache(dict):
 
     def agree(self, best):
         """rank 0's choice for a new entry, on every rank (all ranks build the same plans in the same order)."""
-        import os
         if os.environ.get("VD_TUNE_AGREE", "1") == "0" or not torch.distributed.is_available() or \
                 not torch.distributed.is_initialized() or torch.distributed.get_world_size() == 1:
             return best
@@ -258,7 +254,6 @@ class TuneCache(dict):
 
     def save(self):
         import json
-        import os
         if not self._dirty:
             return
         self._dirty = False
@@ -306,7 +301,6 @@ def fp32_math():
     """Arithmetic of the fp32 convolution products (include/viddet_hip.h VD_MATH_SPLIT): 'native' = fp32 MFMA,
     'split' = three-way bf16 operand split on the bf16 matrix pipe (fp32-accurate), 'auto' = the
     plan-time autotuner times both per launch record and keeps the faster."""
-    import os
     m = _MATH_OVERRIDE[0] or os.environ.get("VD_FP32_MATH", "auto")
     if m not in _MATH_MODES:
         raise ValueError("VD_FP32_MATH must be one of %s, got %r" % ("|".join(_MATH_MODES), m))
@@ -323,7 +317,7 @@ _ALL_MATH = L.MATH_SPLIT | L.MATH_BF16 | L.MATH_F16X2 | L.MATH_NOHALO | L.CONV_S
 def _streamk_on():
     """VD_STREAMK=0: never the persistent stream-K form of k_conv_igemm (read when a plan is built).  The form changes how a
     launch is cut into workgroups, not one bit of what it computes (vd_conv_sk.hip), so this is a speed switch only."""
-    return __import__('os').environ.get('VD_STREAMK', '1') != '0'
+    return os.environ.get('VD_STREAMK', '1') != '0'
 
 
 def _streamk_applies(d, fl, tile):
@@ -348,7 +342,6 @@ def set_conv_math(mode):
 
 def _tile_candidates(d, math):
     """(flags bit, tile) candidates of one launch record."""
-    import os
     if d.flags & L.CONV_PARITY4:            # the parity-fused stride-2 data gradient: fp16 split, the tiles it is built for
         return [(L.MATH_F16X2, t) for t in (5, 1, 6, 2, 12, 11)]
     cands = []
@@ -381,11 +374,25 @@ def _tile_candidates(d, math):
     return cands
 
 
+def _bf16_tile_candidates(d, of32, *, patch_kernel, tall_tiles, halo):
+    """(tiles, halo_geo) of one vd_conv_igemm_bf16 launch record for _tune_bf16_record.  What the inference and the training
+    plans decide differently is the caller's word: patch_kernel - tile 16, the first-stage patch kernel of
+    vd_conv_c32_bf16.hip (3x3, 32 -> 64 channels; the library falls back to the default tile where it does not apply);
+    tall_tiles - the 256-row tiles 8 / 9 of wide layers; halo - whether the halo-staged loop may be timed at all."""
+    one = d.T == 1           # 14 / 15: the small four-wave tiles (64x64 / 128x32, four or five workgroups per CU) for the HBM-bound 1x1 layers
+    tiles = ((10, 11, 13) + ((14,) if one else ()) + ((16,) if (d.T == 9 and d.Co == 64 and patch_kernel and not of32) else ()) if d.Ci == 32
+             else (12, 10, 11, 13) + ((15,) if one else ()) if d.Co <= 32
+             else (10, 11, 13, 2, 3, 4, 5) + ((14,) if one else ()) if d.Co <= 64
+             else (1, 2, 3, 4, 5, 6, 7) + ((8, 9) if (d.Co > 128 and tall_tiles) else ()) + ((14,) if one else ()))
+    # 3x3 stride-1 'same' geometry: the halo-staged loop (8-wave tiles; the library falls back by itself where it does not
+    # apply) is timed against the generic one
+    return tiles, bool(halo and d.T == 9 and d.in_stride == 1 and d.Hg == d.Hi and d.Ci % 64 == 0)
+
+
 def autotune_desc(d, reps=3):
     """Pick the fastest k_conv_igemm variant (product arithmetic x tile shape) for one launch descriptor (timed in
     place on its own buffers with events on the launch stream; cached per problem signature).  VD_AUTOTUNE=0 keeps
     the kernel's heuristic tile.  Tuning launches only rewrite buffers every real run rewrites first."""
-    import os
     math = fp32_math()
     base = d.flags & ~_ALL_MATH
     if os.environ.get("VD_AUTOTUNE", "1") == "0":
@@ -454,7 +461,6 @@ def _wgrad_halo_applies(d, flags):
 
 def autotune_wgrad_bf16(d, ws_ptr, ws_bytes, reps=2):
     """bf16-stored operands: generic kernel vs the halo ring, timed in place (the flag is ignored where it does not apply)"""
-    import os
     d.flags = L.STORE_BF16 | L.MATH_BF16
     if os.environ.get("VD_WGRAD_HALO", "1") != "1" or not _wgrad_halo_applies(d, L.STORE_BF16 | L.MATH_BF16):
         return
@@ -486,7 +492,6 @@ def autotune_wgrad_bf16(d, ws_ptr, ws_bytes, reps=2):
 
 def autotune_wgrad(d, ws_ptr, ws_bytes, reps=2):
     """Product arithmetic of one weight-gradient launch record (fp32 MFMA vs the split forms), timed in place."""
-    import os
     math = fp32_math()
     d.flags = 0
     if d.Co < 64 or math == "native":
@@ -529,7 +534,6 @@ def _tune_bf16_record(d, of32, key, tiles, halo_geo, splitk=False):
     (tile, flag bits) under `key`.  splitk (inference plans only - the form is deterministic but has another summation
     order than the one-tile launch): launches with too few tiles for the chip also time the split-K grid (VD_CONV_SPLITK)
     of every tile that has one."""
-    import os
     lib = L.load()
     s = L.stream_ptr()
     mask = L.MATH_NOHALO | L.CONV_STREAMK | L.CONV_SPLITK
@@ -1209,7 +1213,7 @@ class YOLOV3(object):
         # class-agnostic detection (YOLOOutputV3(agnostic=True), yolo3.py:184-188): inference emits one candidate per anchor
         # (id 0, score = sigmoid(objectness)) into the same box_nms.  The branch sits behind `if autograd.is_training()`, so
         # the graph, the parameters and training are those of agnostic=False; only the decode + NMS tail of the inference
-        # plans differs (_add_agnostic_tail)
+        # plans differs (infer_plan.InferPlan.detect_tail)
         self.agnostic = bool(agnostic)
         if self.agnostic:
             if conv_types is not None and check_conv_types(conv_types, k) is not None:
@@ -1269,20 +1273,19 @@ class YOLOV3(object):
         self._pack_event = None
         self._graph_cache = {}
         self.use_graphs = False
-        import os as _os
-        self.overlap_wgrad = _os.environ.get('VD_OVERLAP', '1') != '0'   # wgrad GEMMs on a side stream (_build_train)
-        self.fuse_bn_stats = _os.environ.get('VD_FUSE_STATS', '1') != '0'  # BN statistics in the conv epilogue
+        self.overlap_wgrad = os.environ.get('VD_OVERLAP', '1') != '0'   # wgrad GEMMs on a side stream (_build_train)
+        self.fuse_bn_stats = os.environ.get('VD_FUSE_STATS', '1') != '0'  # BN statistics in the conv epilogue
         self.precision = 'fp32'        # inference precision: 'fp32' | 'bf16' (set_precision)
         self._dev_resize = None        # (height, width, interp): raw uint8 frames are resized on the device (set_device_resize)
         self._resize_cache = {}        # (H0, W0, H, W, interp) -> the tap tables of that resize, host and device
         self._dev_nv12 = None          # set_device_resize(source='nv12'): the seven integers of video.NV12_MATRICES[(matrix, range)]
-        self.bucketed_allreduce = _os.environ.get('VD_BUCKETED', '1') != '0'
-        self.alias_skip_grad = _os.environ.get('VD_ALIAS_SKIP', '1') != '0'    # skip gradients by alias, not by copy
-        self.fuse_bn_bwd = _os.environ.get('VD_FUSE_BWD', '1') != '0'          # BN backward reductions in the dgrad epilogue
+        self.bucketed_allreduce = os.environ.get('VD_BUCKETED', '1') != '0'
+        self.alias_skip_grad = os.environ.get('VD_ALIAS_SKIP', '1') != '0'    # skip gradients by alias, not by copy
+        self.fuse_bn_bwd = os.environ.get('VD_FUSE_BWD', '1') != '0'          # BN backward reductions in the dgrad epilogue
         # fp32 gradients per all-reduce.  The tail bucket (everything below stage 4: ~15 M parameters, the layers whose
         # gradients come last) closes with the stem and is the one collective nothing overlaps, so buckets are kept at
         # 32 MB: large enough for the ring to reach its bandwidth, small enough that the exposed tail stays ~30 MB.
-        self.bucket_elems = int(float(_os.environ.get('VD_BUCKET_MB', '32')) * (1 << 18))
+        self.bucket_elems = int(float(os.environ.get('VD_BUCKET_MB', '32')) * (1 << 18))
         self._pending_reduces = []
         self._reduced_from = 1 << 62
         self._dp_stats = {'buckets': 0, 'bucket_bytes': 0}     # all-reduce buckets queued since the last reset (bench.py)
@@ -1735,17 +1738,20 @@ class YOLOV3(object):
                 self._dp_stats['syncbn_exchanges'] = self._dp_stats.get('syncbn_exchanges', 0) + 1
         return f
 
-    def _add_sel_add_fwd(self, prog, n, bufs, B):
-        """Forward launches of a SelNode / AddNode (the same in inference and training)."""
+    def _add_sel_add_fwd(self, prog, n, bufs, B, bf16=False):
+        """Forward launches of a SelNode / AddNode (the same in inference and training).  bf16 (inference only): the slice
+        copies 4-byte words, two elements each, and no max-abs records follow."""
         am = lambda t: bufs['amax:' + t].data_ptr()
         if isinstance(n, SelNode):
             xs, o = bufs[n.src], bufs[n.dst]
-            prog.add('vd_frame_slice', xs.data_ptr(), o.data_ptr(), B, n.K, n.k0, n.kc, xs[0].numel(), 0)
-            prog.add('vd_amax_merge', am(n.src), None, am(n.dst))
+            prog.add('vd_frame_slice', xs.data_ptr(), o.data_ptr(), B, n.K, n.k0, n.kc, xs[0].numel() // (2 if bf16 else 1), 0)
+            if not bf16:
+                prog.add('vd_amax_merge', am(n.src), None, am(n.dst))
         else:
             a, b_, o = bufs[n.a], bufs[n.b], bufs[n.dst]
-            prog.add('vd_add', a.data_ptr(), b_.data_ptr(), o.data_ptr(), o.numel())
-            prog.add('vd_amax', o.data_ptr(), o.numel(), am(n.dst))
+            prog.add('vd_add_bf16' if bf16 else 'vd_add', a.data_ptr(), b_.data_ptr(), o.data_ptr(), o.numel())
+            if not bf16:
+                prog.add('vd_amax', o.data_ptr(), o.numel(), am(n.dst))
 
     # ------------------------------------------------------------------ bidirectional ConvGRU (GruNode)
     def _gru_conv_desc(self, cn, x, out, N, H, W, sidx, amax_in=None):
@@ -1824,13 +1830,11 @@ class YOLOV3(object):
                  meta=dict(kind='tdw_fwd', node=n.name, flops=6.0 * B * n.K * hw * n.C,
                            bytes=4.0 * B * n.K * hw * n.C * (3 if n.residual else 2)))
 
-    def _add_amax_reset(self, prog, bufs):
-        prog.add('vd_fill', bufs['amax'].data_ptr(), 0.0, bufs['amax'].numel())
-
     def _add_input_stage(self, prog, bufs, B, H, W):
-        """Layout change of the network inputs: none for the frame batch (the stem kernel reads NCHW directly); the
-        three cached feature maps of the no-backbone variant go NCHW -> NHWC."""
-        self._add_amax_reset(prog, bufs)
+        """The first records of every fp32 program: the max-abs slots are zeroed; then the layout change of the network
+        inputs - none for the frame batch (the stem kernel reads NCHW directly); the three cached feature maps of the
+        no-backbone variant go NCHW -> NHWC."""
+        prog.add('vd_fill', bufs['amax'].data_ptr(), 0.0, bufs['amax'].numel())
         if self.noback:
             for nm, c_, d_ in ROUTE_TENSORS:
                 prog.add('vd_nchw_to_nhwc', bufs['in:' + nm].data_ptr(), bufs[nm].data_ptr(), B, c_, H // d_, W // d_)
@@ -1916,128 +1920,8 @@ class YOLOV3(object):
                 'vd_resize_nv12_nchw')
 
     def _build_infer(self, B, H, W):
-        bufs = self._buffers('infer', B, H, W, False)
-        prog = Program()
-        self._add_input_stage(prog, bufs, B, H, W)
-        self._add_infer_nodes(prog, self.nodes, bufs, B, H, W)
-        o = self._add_detect_tail(prog, bufs, B, H, W)
-        autotune_program(prog)
-        return prog, bufs, o
-
-    def _add_infer_nodes(self, prog, nodes, bufs, B, H, W, ring=None):
-        """The fp32 inference records of `nodes` on B samples.  ring = (slot table [B][K] int32, S): the joins read their
-        K frames from the ring of cached per-frame features `bufs['ring:' + source]` (detect_video, vd_stream.hip)."""
-        am = lambda t: bufs['amax:' + t].data_ptr()
-        for n in nodes:
-            if isinstance(n, UpcatNode):
-                o = bufs[n.dst]
-                prog.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
-                         o.shape[1], o.shape[2], n.cu, n.cr)
-                prog.add('vd_amax_merge', am(n.up), am(n.route), am(n.dst))       # a concatenation: max of the two
-                continue
-            if isinstance(n, PoolNode) and ring is not None:
-                o, xs = bufs[n.dst], bufs['ring:' + n.src]
-                if n.type == 2:
-                    prog.add('vd_temporal_cat_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
-                             xs.shape[1] * xs.shape[2], xs.shape[3])
-                else:
-                    prog.add('vd_temporal_pool_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K, o[0].numel(),
-                             n.type, meta=dict(kind='pool_idx', bytes=4.0 * o.numel() * (n.K + 1)))
-                # the ring's frames went through the prefix in other launches: the operand scale is the join's own max-abs
-                prog.add('vd_amax', o.data_ptr(), o.numel(), am(n.dst))
-                continue
-            if isinstance(n, PoolNode):
-                o, xs = bufs[n.dst], bufs[n.src]
-                if n.type == 2:
-                    prog.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3], 0)
-                else:
-                    prog.add('vd_temporal_pool', xs.data_ptr(), o.data_ptr(), None, B, n.K, o[0].numel(), n.type)
-                prog.add('vd_amax_merge', am(n.src), None, am(n.dst))             # max / mean / stacking: bounded by the source's
-                continue
-            if isinstance(n, CorrNode):                 # its readers are range-exact (_build): no max-abs slots needed
-                xs = bufs[n.src]
-                prog.add('vd_corr_fwd', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d, n.ldy,
-                         meta=self._corr_meta(n, B, xs, 'fwd'))
-                continue
-            if isinstance(n, (SelNode, AddNode)):
-                self._add_sel_add_fwd(prog, n, bufs, B)
-                continue
-            if isinstance(n, GruNode):
-                self._add_gru_fwd(prog, n, bufs, B, H, W, False)
-                continue
-            if isinstance(n, TdwNode):
-                self._add_tdw_fwd(prog, n, bufs, B, H, W)
-                continue
-            if n.stem:
-                self._add_stem(prog, n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, leaky=True)
-                prog.add('vd_amax', bufs[n.dst].data_ptr(), bufs[n.dst].numel(), am(n.dst))
-                continue
-            if getattr(n, 'tvalid', False):
-                # (3,1,1) conv without temporal padding = frames [1, K-1) of the 'same'-padded one; BatchNorm sees those only
-                zf, zs, o = bufs['zf:' + n.dst], bufs['zs:' + n.dst], bufs[n.dst]
-                d = self._conv_desc(n, bufs, B, H, W, zf)
-                prog.hold(d)
-                prog.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
-                prog.add('vd_frame_slice', zf.data_ptr(), zs.data_ptr(), B, n.fr, 1, n.fr - 2, zf[0].numel(), 0)
-                prog.add('vd_bn_apply_leaky', zs.data_ptr(), n.fold_scale.data_ptr(), n.fold_shift.data_ptr(), None,
-                         o.data_ptr(), o.numel() // n.cout, n.cout, LEAKY_SLOPE, am(n.dst))
-                continue
-            if n.head:
-                d = self._conv_desc(n, bufs, B, H, W, bufs[n.dst], shift=n.bias)
-            else:
-                res = bufs[n.residual] if n.residual else None
-                d = self._conv_desc(n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, residual=res,
-                                    leaky=True, amax_out=True)
-            prog.hold(d)
-            prog.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
-
-    def _add_detect_tail(self, prog, bufs, B, H, W):
-        """decode + NMS of an inference plan over the (fp32) heads in `bufs`; returns the output tensors"""
-        grids = self._grid(H, W)
-        Bh = B * self._head_frames           # images the decode / NMS see (B*t with per-frame predictions)
-        hd = ops.make_head_desc([bufs[h] for h in self.head_names], grids, round_up(3 * (5 + self.num_class), 32),
-                                STRIDES[::-1], ANCHORS[::-1], Bh, self.num_class)
-        P = 3 * sum(g * g for g in grids)
-        if self.agnostic:
-            return self._add_agnostic_tail(prog, hd, P, Bh)
-        # one candidate slot per row of the reference's (B, C*P, 6) tensor: box_nms (yolo3.py:1197-1202) has no cap, and an
-        # untrained net (validation after epoch 0) passes valid_thresh on every row.  8 bytes x C*P per image (14.6 MB at
-        # 608x608 / 80 classes) is address space, not traffic: only the rows that pass are ever written or read.
-        cap = self.num_class * P
-        o = dict(cand_score=torch.empty(Bh, cap, device=self.device),
-                 cand_row=torch.empty(Bh, cap, dtype=torch.int32, device=self.device),
-                 counts=torch.zeros(Bh, dtype=torch.int32, device=self.device),
-                 ids=torch.empty(Bh, self.post_nms, 1, device=self.device),
-                 scores=torch.empty(Bh, self.post_nms, 1, device=self.device),
-                 bboxes=torch.empty(Bh, self.post_nms, 4, device=self.device),
-                 rows=torch.empty(Bh, self.post_nms, dtype=torch.int32, device=self.device),
-                 overflow=torch.zeros(Bh, dtype=torch.int32, device=self.device))
-        prog.hold(hd, o)
-        prog.add('vd_yolo_decode_filter', C.byref(hd), 0.01, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), cap,
-                 o['counts'].data_ptr())
-        prog.add('vd_nms_topk', C.byref(hd), o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), cap,
-                 o['counts'].data_ptr(), float(self.nms_thresh), int(self.nms_topk), int(self.post_nms),
-                 o['ids'].data_ptr(), o['scores'].data_ptr(), o['bboxes'].data_ptr(), o['rows'].data_ptr(),
-                 o['overflow'].data_ptr(), 4 * Bh)
-        return o
-
-    def _add_agnostic_tail(self, prog, hd, P, Bh):
-        """The class-agnostic decode + NMS of an inference plan (fp32 and bf16 plans: the heads are fp32 in both).  One
-        candidate per anchor at the most, so the lists hold P entries per image and cannot overflow."""
-        dev = self.device
-        o = dict(cand_score=torch.empty(Bh, P, device=dev), cand_row=torch.empty(Bh, P, dtype=torch.int32, device=dev),
-                 counts=torch.zeros(Bh, dtype=torch.int32, device=dev), ids=torch.empty(Bh, self.post_nms, 1, device=dev),
-                 scores=torch.empty(Bh, self.post_nms, 1, device=dev), bboxes=torch.empty(Bh, self.post_nms, 4, device=dev),
-                 rows=torch.empty(Bh, self.post_nms, dtype=torch.int32, device=dev),
-                 overflow=torch.zeros(Bh, dtype=torch.int32, device=dev))
-        prog.hold(hd, o)
-        prog.add('vd_yolo_decode_filter_agnostic', C.byref(hd), 0, 0.01, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), P,
-                 o['counts'].data_ptr())
-        prog.add('vd_nms_agnostic', C.byref(hd), 0, o['cand_score'].data_ptr(), o['cand_row'].data_ptr(), P,
-                 o['counts'].data_ptr(), float(self.nms_thresh), int(self.nms_topk), int(self.post_nms),
-                 o['ids'].data_ptr(), o['scores'].data_ptr(), o['bboxes'].data_ptr(), o['rows'].data_ptr(),
-                 o['overflow'].data_ptr(), 4 * Bh)
-        return o
+        """the fp32 inference plan (infer_plan.InferPlan) -> (prog, bufs, outputs)"""
+        return infer_plan.InferPlan(self, H, W, False).build(B)
 
     def _refresh_fold(self):
         if not self._fold_dirty:
@@ -2064,149 +1948,8 @@ class YOLOV3(object):
         """bf16 inference plan of every network variant: the plain net (BASELINE configs[1]), k > 1 windows (TimeDistributed
         backbone = frames folded into the batch, temporal pooling / stacking, 3-D and 2+1-D neck convs through Kfr), the
         no-backbone net (its three fp32 feature maps converted on the way in) and YOLOV3Temporal (frame selections, sums,
-        valid-frame convs, per-frame heads)."""
-        dev = self.device
-        lib = L.load()
-        BFT = torch.bfloat16
-        # channel runs of 64 (one 128-byte K-step); a 32-channel map stays unpadded (two taps per K-step, vd_conv_bf16.hip)
-        cp = lambda c: 32 if c == 32 else round_up(c, 64)
-        bufs = {}
-        for name, (c, div, ld, fr) in self.tensors.items():
-            if name == 'in':
-                bufs['in'] = torch.empty(B * fr, 3, H, W, device=dev)
-            elif name in self.head_names:
-                bufs[name] = torch.empty(B * fr, H // div, W // div, ld, device=dev)
-            else:
-                # zeros: padded channels are never written
-                bufs[name] = torch.zeros(B * fr, H // div, W // div, cp(c), dtype=BFT, device=dev)
-        prog = Program()
-        packs = []
-        if self.noback:
-            # the three cached feature maps arrive as fp32 NCHW: NHWC, then one conversion each
-            for nm, c_, d_ in ROUTE_TENSORS:
-                bufs['in:' + nm] = torch.empty(B, c_, H // d_, W // d_, device=dev)
-                bufs['f32:' + nm] = torch.empty(B, H // d_, W // d_, c_, device=dev)
-                assert cp(c_) == c_
-                prog.add('vd_nchw_to_nhwc', bufs['in:' + nm].data_ptr(), bufs['f32:' + nm].data_ptr(), B, c_, H // d_, W // d_)
-                n_el = bufs[nm].numel()
-                prog.add('vd_pack_weight_bf16', bufs['f32:' + nm].data_ptr(), bufs[nm].data_ptr(), 1, 1, n_el, n_el, 1)
-        self._add_infer_nodes_bf16(prog, self.nodes, bufs, B, H, W, packs)
-        return prog, bufs, self._add_detect_tail(prog, bufs, B, H, W), packs
-
-    def _add_infer_nodes_bf16(self, prog, nodes, bufs, B, H, W, packs, ring=None):
-        """The bf16 inference records of `nodes` on B samples; the bf16 weight images they read are appended to `packs`.
-        ring: as in _add_infer_nodes."""
-        dev = self.device
-        BFT = torch.bfloat16
-        cp = lambda c: 32 if c == 32 else round_up(c, 64)
-        fuse_stem = None
-        for n in nodes:
-            if isinstance(n, UpcatNode):
-                o = bufs[n.dst]
-                # 16-byte-unit copy kernel: pass channel counts as if fp32 (bf16 count / 2)
-                prog.add('vd_upsample2x_concat', bufs[n.up].data_ptr(), bufs[n.route].data_ptr(), o.data_ptr(), B * n.fr,
-                         o.shape[1], o.shape[2], cp(n.cu) // 2, cp(n.cr) // 2)
-                continue
-            if isinstance(n, PoolNode) and ring is not None:
-                o, xs = bufs[n.dst], bufs['ring:' + n.src]
-                assert xs.shape[3] % 8 == 0
-                if n.type == 2:
-                    prog.add('vd_temporal_cat_idx', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
-                             xs.shape[1] * xs.shape[2], xs.shape[3] // 2)
-                else:
-                    prog.add('vd_temporal_pool_idx_bf16', xs.data_ptr(), ring[0].data_ptr(), o.data_ptr(), ring[1], B, n.K,
-                             o[0].numel(), n.type, meta=dict(kind='pool_idx', bytes=2.0 * o.numel() * (n.K + 1)))
-                continue
-            if isinstance(n, PoolNode):
-                o, xs = bufs[n.dst], bufs[n.src]
-                if n.type == 2:          # stacking the K frames' channels: a copy (bf16 channel count / 2)
-                    assert xs.shape[3] % 8 == 0
-                    prog.add('vd_temporal_cat', xs.data_ptr(), o.data_ptr(), B, n.K, xs.shape[1] * xs.shape[2], xs.shape[3] // 2, 0)
-                else:
-                    prog.add('vd_temporal_pool_bf16', xs.data_ptr(), o.data_ptr(), B, n.K, o[0].numel(), n.type)
-                continue
-            if isinstance(n, CorrNode):
-                xs = bufs[n.src]
-                assert xs.shape[3] == n.C and bufs[n.dst].shape[3] == n.ldy
-                prog.add('vd_corr_fwd_bf16', xs.data_ptr(), bufs[n.dst].data_ptr(), B, n.K, xs.shape[1], xs.shape[2], n.C, n.d,
-                         n.ldy, meta=self._corr_meta(n, B, xs, 'fwd'))
-                continue
-            if isinstance(n, SelNode):
-                xs, o = bufs[n.src], bufs[n.dst]
-                prog.add('vd_frame_slice', xs.data_ptr(), o.data_ptr(), B, n.K, n.k0, n.kc, xs[0].numel() // 2, 0)
-                continue
-            if isinstance(n, AddNode):
-                a_, b_, o = bufs[n.a], bufs[n.b], bufs[n.dst]
-                prog.add('vd_add_bf16', a_.data_ptr(), b_.data_ptr(), o.data_ptr(), o.numel())
-                continue
-            if n.stem:
-                # the stem and the stride-2 conv behind it as ONE launch (vd_stem_conv_c32_bf16: the stem's 32-channel map is
-                # computed inside the first-stage patch kernel and never stored; same bits) where that conv is the stem's only
-                # reader; VD_STEM_FUSED=0: two launches
-                users = [m for m in nodes if n.dst in node_inputs(m)]
-                import os
-                fuse_stem = None
-                if (os.environ.get("VD_STEM_FUSED", "1") != "0" and len(users) == 1 and isinstance(users[0], ConvNode)
-                        and users[0].src == n.dst and users[0].k == 3 and users[0].kd == 1 and users[0].stride == 2
-                        and users[0].cin == 32 and users[0].cout == 64 and users[0].bn and not users[0].residual
-                        and not getattr(users[0], 'tvalid', False)):
-                    fuse_stem = (n, users[0])
-                    continue
-                # fp32 master weights and BN fold on the fp32 VALU, bf16 output (vd_stem.hip)
-                self._add_stem(prog, n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, leaky=True,
-                               bf16=True)
-                continue
-            tvalid = getattr(n, 'tvalid', False)
-            ci_p = cp(n.cin)
-            co_p = n.co_pad if n.head else cp(n.cout)
-            wb = torch.empty(co_p * n.T * ci_p, dtype=BFT, device=dev)
-            packs.append((n, wb, co_p, ci_p))
-            d = ConvDesc()
-            self._set_streamk(d, 0)
-            x = bufs[n.src]
-            Hi, Wi = H // n.div_in, W // n.div_in
-            Ho, Wo = H // n.div_out, W // n.div_out
-            out = bufs[n.dst]
-            if tvalid:
-                # (3,1,1) conv without temporal padding = frames [1, K-1) of the 'same'-padded one: all frames go through
-                # the conv and its (per-channel, batch-independent) BN-fold epilogue, the valid ones are sliced out
-                if ('zf:' + n.dst) not in bufs:
-                    bufs['zf:' + n.dst] = torch.zeros(B * n.fr, Ho, Wo, co_p, dtype=BFT, device=dev)
-                out = bufs['zf:' + n.dst]
-            d.in_, d.wp, d.out = x.data_ptr(), wb.data_ptr(), out.data_ptr()
-            d.N, d.Hi, d.Wi, d.Ci = B * n.fr, Hi, Wi, ci_p
-            d.Hg, d.Wg, d.in_stride = Ho, Wo, n.stride
-            ops._set_taps(d, n.taps())
-            d.Kfr = n.fr if n.kd > 1 else 1
-            d.Ho, d.Wo, d.Co = Ho, Wo, co_p
-            d.out_stride, d.out_oy, d.out_ox = 1, 0, 0
-            d.ldo = d.ldr = out.shape[-1]
-            if n.head:
-                d.flags, d.shift = EPI_AFFINE, n.bias.data_ptr()
-            else:
-                # padded fp32 fold vectors: one pair per NODE, shared by the plans of every input shape (a per-plan pair
-                # would go stale in all plans but the one that last refreshed it)
-                if getattr(n, 'bf_scale', None) is None or n.bf_scale.numel() != co_p:
-                    n.bf_scale, n.bf_shift = torch.zeros(co_p, device=dev), torch.zeros(co_p, device=dev)
-                sc, sh = n.bf_scale, n.bf_shift
-                d.flags = EPI_AFFINE | EPI_LEAKY | (EPI_RESIDUAL if n.residual else 0)
-                d.scale, d.shift = sc.data_ptr(), sh.data_ptr()
-                if n.residual:
-                    d.residual = bufs[n.residual].data_ptr()
-            d.slope = LEAKY_SLOPE
-            prog.hold(d, wb)
-            if fuse_stem is not None and fuse_stem[1] is n:
-                st = fuse_stem[0]
-                meta = self._flops(n, B, H, W, 'fwd')
-                meta['flops'] += self._flops(st, B, H, W, 'fwd')['flops']
-                meta['fused_stem'] = True
-                d.tile = 16
-                prog.add('vd_stem_conv_c32_bf16', bufs['in'].data_ptr(), st.wp.data_ptr(), st.fold_scale.data_ptr(),
-                         st.fold_shift.data_ptr(), LEAKY_SLOPE, C.byref(d), meta=meta)
-                continue
-            prog.add('vd_conv_igemm_bf16', C.byref(d), 1 if n.head else 0, meta=self._flops(n, B, H, W, 'fwd'))
-            if tvalid:
-                prog.add('vd_frame_slice', out.data_ptr(), bufs[n.dst].data_ptr(), B, n.fr, 1, n.fr - 2, out[0].numel() // 2, 0)
+        valid-frame convs, per-frame heads) -> (prog, bufs, outputs, packs)."""
+        return infer_plan.InferPlan(self, H, W, True).build(B)
 
     def _refresh_bf16(self, packs):
         """Re-derive the bf16 weight images and the padded fp32 scale/shift vectors after a parameter change."""
@@ -2221,7 +1964,6 @@ class YOLOV3(object):
                 n.bf_shift[:n.cout].copy_(n.fold_shift)
 
     def _tune_bf16(self, prog):
-        import os
         if os.environ.get("VD_AUTOTUNE", "1") == "0":
             return
         for (fname, fn, args) in prog.recs:
@@ -2230,18 +1972,21 @@ class YOLOV3(object):
             d, of32 = args[0]._obj, args[1]
             base = d.flags & ~(L.MATH_NOHALO | L.CONV_STREAMK | L.CONV_SPLITK)
             key = ('bf16', d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride, d.T, d.Co, base, of32, d.Kfr)
-            one = d.T == 1           # 14 / 15: small four-wave tiles for the HBM-bound 1x1 layers
-            # (16: the first-stage patch kernel of vd_conv_c32_bf16.hip - 3x3, 32 -> 64 channels; the library falls back to the
-            # default tile where it does not apply)
-            tiles = ((10, 11, 13) + ((14,) if one else ()) + ((16,) if (d.T == 9 and d.Co == 64 and not of32) else ()) if d.Ci == 32
-                     else (12, 10, 11, 13) + ((15,) if one else ()) if d.Co <= 32
-                     else (10, 11, 13, 2, 3, 4, 5) + ((14,) if one else ()) if d.Co <= 64
-                     else (1, 2, 3, 4, 5, 6, 7) + ((8, 9) if d.Co > 128 else ()) + ((14,) if one else ()))
-            # 3x3 stride-1 'same' geometry: the halo-staged loop (8-wave tiles; the library falls back by itself where it
-            # does not apply) is timed against the generic one
-            halo_geo = d.T == 9 and d.in_stride == 1 and d.Hg == d.Hi and d.Ci % 64 == 0
-            _tune_bf16_record(d, of32, key, tiles, halo_geo, splitk=True)
+            _tune_bf16_record(d, of32, key, *_bf16_tile_candidates(d, of32, patch_kernel=True, tall_tiles=True, halo=True),
+                              splitk=True)
         _TUNE_CACHE.save()
+
+    def _bf16_current(self, state, packs, progs):
+        """The bf16 weight images of ONE plan, current: every plan owns its images, re-packed when the weights / running
+        statistics moved since THIS plan last packed them (a net-wide flag would leave the other shapes' plans stale);
+        the plan's records are tuned once, after the first pack.  `state` (a dict of the plan) remembers the version."""
+        version = (self._weights_version, self._stats_version)
+        if state.get('packs_version') != version:
+            self._refresh_bf16(packs)
+            if 'packs_version' not in state:
+                for prog in progs:
+                    self._tune_bf16(prog)
+            state['packs_version'] = version
 
     # ------------------------------------------------------------------ inference
     def _in_shape(self, x):
@@ -2334,17 +2079,9 @@ class YOLOV3(object):
         if self.precision == 'bf16':
             key = ('infer_bf16', B, H, W)
             if key not in self._programs:
-                built = self._build_or_evict(lambda: self._build_infer_bf16(B, H, W))
-                self._refresh_bf16(built[3])
-                built[1]['packs_version'] = (self._weights_version, self._stats_version)
-                self._tune_bf16(built[0])
-                self._programs[key] = built
+                self._programs[key] = self._build_or_evict(lambda: self._build_infer_bf16(B, H, W))
             prog, bufs, o, packs = self._programs[key]
-            # every plan owns its bf16 weight images: refreshed when the weights / running statistics moved since THIS
-            # plan last packed them (a net-wide flag would leave the other shapes' plans stale)
-            if bufs.get('packs_version') != (self._weights_version, self._stats_version):
-                self._refresh_bf16(packs)
-                bufs['packs_version'] = (self._weights_version, self._stats_version)
+            self._bf16_current(bufs, packs, [prog])
         else:
             key = ('infer', B, H, W)
             if key not in self._programs:
@@ -2429,54 +2166,9 @@ class YOLOV3(object):
                     "%s behind the joins reads a per-frame tensor" % n.name
         return prefix, suffix
 
-    def _stream_bufs(self, names, rows, H, W, bf16):
-        """activation tensors `names` of a streaming plan on `rows` frames (layouts of _buffers / _build_infer_bf16)"""
-        dev, bufs = self.device, {}
-        cp = lambda c: 32 if c == 32 else round_up(c, 64)
-        for name in names:
-            c, div, ld, _ = self.tensors[name]
-            if name == 'in':
-                bufs['in'] = torch.zeros(rows, 3, H, W, device=dev)
-            elif bf16 and name not in self.head_names:
-                bufs[name] = torch.zeros(rows, H // div, W // div, cp(c), dtype=torch.bfloat16, device=dev)    # pad channels stay 0
-            else:
-                bufs[name] = torch.empty(rows, H // div, W // div, ld, device=dev)
-                if not bf16:
-                    bufs[name].normal_()                           # the autotuner times on these: noise, not zero pages (_buffers)
-        if not bf16:
-            act = [nm for nm in names if nm != 'in']
-            bufs['amax'] = torch.zeros(max(1, len(act)) * L.AMAX_FLOATS, device=dev)
-            for i, nm in enumerate(act):
-                bufs['amax:' + nm] = bufs['amax'][i * L.AMAX_FLOATS:(i + 1) * L.AMAX_FLOATS]
-        return bufs
-
     def _build_stream(self, Bc, H, W, S):
-        """The two programs of detect_video: the per-frame prefix on Bc frames, and the joins off the ring + the suffix +
-        decode / NMS on Bc windows."""
-        bf16 = self.precision == 'bf16'
-        prefix, suffix = self._stream_split()
-        srcs = [n.src for n in suffix if isinstance(n, PoolNode)]
-        pnames = ['in'] + [n.dst for n in prefix]
-        snames = [n.dst for n in suffix]
-        pb = self._stream_bufs(pnames, Bc, H, W, bf16)
-        sb = self._stream_bufs(snames, Bc, H, W, bf16)
-        for t in srcs:                                           # slot = frame index mod S
-            sb['ring:' + t] = torch.zeros((S,) + tuple(pb[t].shape[1:]), dtype=pb[t].dtype, device=self.device)
-        slots = torch.zeros(Bc, self._k, dtype=torch.int32, device=self.device)
-        pre, suf, packs = Program(), Program(), []
-        if bf16:
-            self._add_infer_nodes_bf16(pre, prefix, pb, Bc, H, W, packs)
-            self._add_infer_nodes_bf16(suf, suffix, sb, Bc, H, W, packs, ring=(slots, S))
-        else:
-            self._add_amax_reset(pre, pb)
-            self._add_infer_nodes(pre, prefix, pb, Bc, H, W)
-            self._add_amax_reset(suf, sb)
-            self._add_infer_nodes(suf, suffix, sb, Bc, H, W, ring=(slots, S))
-        o = self._add_detect_tail(suf, sb, Bc, H, W)
-        if not bf16:                                             # (the bf16 plans are tuned once their weight images exist)
-            autotune_program(pre)
-            autotune_program(suf)
-        return dict(pre=pre, suf=suf, pb=pb, sb=sb, o=o, packs=packs, slots=slots, srcs=srcs, S=S)
+        """The two programs of detect_video (infer_plan.InferPlan.build_stream), in the precision set on the net."""
+        return infer_plan.InferPlan(self, H, W, self.precision == 'bf16').build_stream(Bc, S)
 
     def _stage_frames(self, dst, frames, a, b):
         """frames [a, b) of the clip -> the first rows of the NCHW input tensor `dst`, normalised as net(x) does; the rows
@@ -2585,13 +2277,7 @@ class YOLOV3(object):
                 self._programs[key] = self._build_or_evict(lambda: self._build_stream(chunk, H, W, S))
             sp = self._programs[key]
             if bf16:
-                # every plan owns its bf16 weight images (see _forward_infer)
-                if sp.get('packs_version') != (self._weights_version, self._stats_version):
-                    self._refresh_bf16(sp['packs'])
-                    if 'packs_version' not in sp:
-                        self._tune_bf16(sp['pre'])
-                        self._tune_bf16(sp['suf'])
-                    sp['packs_version'] = (self._weights_version, self._stats_version)
+                self._bf16_current(sp, sp['packs'], [sp['pre'], sp['suf']])
             else:
                 self._refresh_fold()
             self._refresh_wamax()
@@ -2645,22 +2331,7 @@ class YOLOV3(object):
         B, H, W = self._in_shape(x)
         key = ('features', B, H, W)
         if key not in self._programs:
-            bufs = self._buffers('infer', B, H, W, False)
-            prog = Program()
-            self._add_input_stage(prog, bufs, B, H, W)
-            last = max(i for i, n in enumerate(self.nodes) if isinstance(n, ConvNode) and n.dst == ROUTE_TENSORS[-1][0])
-            for n in self.nodes[:last + 1]:
-                if n.stem:
-                    self._add_stem(prog, n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, leaky=True)
-                    prog.add('vd_amax', bufs[n.dst].data_ptr(), bufs[n.dst].numel(), bufs['amax:' + n.dst].data_ptr())
-                    continue
-                res = bufs[n.residual] if n.residual else None
-                d = self._conv_desc(n, bufs, B, H, W, bufs[n.dst], scale=n.fold_scale, shift=n.fold_shift, residual=res,
-                                    leaky=True, amax_out=True)
-                prog.hold(d)
-                prog.add('vd_conv_igemm', C.byref(d), meta=self._flops(n, B, H, W, 'fwd'))
-            autotune_program(prog)
-            self._programs[key] = (prog, bufs)
+            self._programs[key] = infer_plan.InferPlan(self, H, W, False).build_features(B)
         prog, bufs = self._programs[key]
         self._refresh_fold()
         self._refresh_wamax()
@@ -2673,7 +2344,7 @@ class YOLOV3(object):
         if not self.syncbn_scope or not torch.distributed.is_available() or not torch.distributed.is_initialized():
             return False
         # (VD_FORCE_DIST=1, bench.py / tests: the exchange runs on a single rank too - the RCCL call pattern of an N-rank job)
-        if torch.distributed.get_world_size(self.process_group) < 2 and __import__('os').environ.get("VD_FORCE_DIST", "0") != "1":
+        if torch.distributed.get_world_size(self.process_group) < 2 and os.environ.get("VD_FORCE_DIST", "0") != "1":
             return False
         if self.syncbn_scope == 'all':
             return True
@@ -2709,21 +2380,15 @@ class YOLOV3(object):
 
     def _tune_bf16_desc(self, d, of32):
         """Tile (and halo / generic loop) of one vd_conv_igemm_bf16 launch record, timed in place; persisted like the others."""
-        import os
         if os.environ.get("VD_AUTOTUNE", "1") == "0":
             return
         base = d.flags & ~(L.MATH_NOHALO | L.CONV_STREAMK)
         key = ('bf16', d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride, d.T, d.Co, base, of32, d.out_stride, bool(d.stats_part),
                bool(d.bs_part)) + ((d.Kfr,) if d.Kfr > 1 else ())      # (frame taps: the 3-D / 2+1-D neck convs of a window)
-        # 14 / 15: the small four-wave tiles (64x64 / 128x32, four or five workgroups per CU) for the HBM-bound 1x1 layers
-        one = d.T == 1
-        # (16: the first-stage patch kernel, forward with fused statistics; falls back to the default tile where it does not apply)
-        tiles = ((10, 11, 13) + ((14,) if one else ()) + ((16,) if (d.T == 9 and d.Co == 64 and d.stats_part and not d.bs_part and not of32) else ())
-                 if d.Ci == 32 else (12, 10, 11, 13) + ((15,) if one else ()) if d.Co <= 32
-                 else (10, 11, 13, 2, 3, 4, 5) + ((14,) if one else ()) if d.Co <= 64
-                 else (1, 2, 3, 4, 5, 6, 7) + ((8, 9) if (d.Co > 128 and not d.bs_part) else ()) + ((14,) if one else ()))
-        halo_geo = d.T == 9 and d.in_stride == 1 and d.Hg == d.Hi and d.Ci % 64 == 0 and d.out_stride == 1
-        _tune_bf16_record(d, of32, key, tiles, halo_geo)
+        # training: the patch kernel is the forward with fused statistics; no 256-row tiles under the fused BatchNorm-
+        # backward reductions; the halo loop only for an unstrided output (a parity launch of a stride-2 data gradient has none)
+        _tune_bf16_record(d, of32, key, *_bf16_tile_candidates(d, of32, patch_kernel=bool(d.stats_part and not d.bs_part),
+                                                               tall_tiles=not d.bs_part, halo=d.out_stride == 1))
 
     @staticmethod
     def _flops(n, B, H, W, kind, esz=4):
@@ -2923,7 +2588,6 @@ class YOLOV3(object):
 
     # ------------------------------------------------------------------ optimiser / DP hooks
     def _dp_active(self):
-        import os
         return torch.distributed.is_available() and torch.distributed.is_initialized() and \
             (torch.distributed.get_world_size(self.process_group) > 1 or os.environ.get("VD_FORCE_DIST") == "1")
 
@@ -3154,4 +2818,4 @@ def yolo3_no_backbone(classes, norm_layer=None, norm_kwargs=None, **kwargs):
     return YOLOV3(classes, syncbn_scope=scope, noback=True, **kwargs)
 
 
-from . import train_plan  # noqa: E402  (last: train_plan imports the node classes, Program and the tuners from this module)
+from . import infer_plan, train_plan  # noqa: E402  (last: they import the node classes, Program and the tuners from this module)

@@ -268,6 +268,14 @@ int vd_stem_conv(const float* x_nchw, const float* wp, void* out, int ldo, int N
 int64_t vd_stem_wgrad_ws_bytes(int N, int H, int W);
 int vd_stem_wgrad(const float* x_nchw, const float* dz, int ldd, float* dwp, int N, int H, int W, void* ws,
                   int64_t ws_bytes, void* stream);
+/* The same weight gradient without a stored dz: every element of dz is computed where vd_stem_wgrad loads it, from the
+ * stem's conv output z [N*H*W][ldz >= 32], the gradient dy [N*H*W][ldy >= 32] of its cell's output and the per-channel
+ * operands of vd_bn_bwd_apply (scale, shift, save_mean, save_invstd [32], sums2 fp64 [64], count, slope), in that
+ * kernel's arithmetic.  dwp is bit-identical to vd_bn_bwd_apply into a buffer followed by vd_stem_wgrad on it; same
+ * workspace (vd_stem_wgrad_ws_bytes). */
+int vd_stem_wgrad_bn(const float* x_nchw, const float* z, int ldz, const float* dy, int ldy, const float* scale,
+                     const float* shift, const float* save_mean, const float* save_invstd, const double* sums2, double count,
+                     float slope, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes, void* stream);
 /* Stem conv 3->32 3x3 s1 p1 (three_darknet.py:163-164): Ci=3 is too thin for the GEMM path, so
  * the stem is lowered to an explicit 32-wide im2col ( col[n,y,x,(ky*3+kx)*3+c], entries 27..31
  * zero ) followed by vd_conv_igemm / vd_conv_wgrad with T=1, Ci=32.  `in` is [N,H,W,3] (nchw=0)
@@ -565,6 +573,10 @@ int vd_temporal_pool_bwd_bf16(const void* dy, const uint8_t* argmax_u8, void* dx
 int vd_corr_bwd_bf16(const void* dy, const void* x, void* dx, int B, int K, int H, int W, int C, int d, int ldy, void* stream);
 int vd_stem_wgrad_bf16(const float* x_nchw, const void* dz, int ldd, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes,
                        void* stream);
+/* vd_stem_wgrad_bn on bf16 z and dy: each dz element is rounded to bf16 before use, as vd_bn_bwd_apply_bf16 stores it */
+int vd_stem_wgrad_bn_bf16(const float* x_nchw, const void* z, int ldz, const void* dy, int ldy, const float* scale,
+                          const float* shift, const float* save_mean, const float* save_invstd, const double* sums2, double count,
+                          float slope, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes, void* stream);
 int vd_yolo_loss_fwd_bwd_bf16(const vd_head_desc* h, const float* gt, int M, const float* obj_t, const float* center_t,
                               const float* scale_t, const float* weight_t, const float* class_t, float ignore_thresh,
                               int label_smooth, float* losses, void* const dhead[3], float* box_out, void* ws, int64_t ws_bytes,

@@ -214,8 +214,9 @@ def main():
             if fname is None:
                 recs.append(py(fn, "collective" if (meta or {}).get("kind") == "collective" else "py"))
             else:
+                fname = fn.__name__          # the entry point (a record may be listed under a family label: Program.add)
                 sig = L.SIGNATURES[fname][1]
-                recs.append({"fn": fname, "args": [val(v, t) for v, t in zip(args, sig)], "meta": meta, "stream": role(st)})
+                recs.append({"fn": fname,"args": [val(v, t) for v, t in zip(args, sig)], "meta": meta, "stream": role(st)})
         nrec += len(recs)
         doc.append({"phase": phase, "records": recs})
     with open(a.out, "w") as f:

@@ -8,6 +8,7 @@
 // fp32 per-thread partials over short runs -> LDS -> per-block rows in a workspace -> fp64 finalize.
 // The fp64 [2C] sums are the SyncBN exchange unit (one all-reduce per layer per direction).
 #include "vd_common.h"
+#include "vd_bn_math.h"
 #include <stdlib.h>
 
 namespace {
@@ -376,12 +377,7 @@ __global__ void k_bn_bwd_apply_v0(const T* __restrict__ x, const T* __restrict__
         const f32x4 d = vd_ld4(dy, i);
         f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float u = v[e] * sc[e] + sh[e];
-            const float g = u > 0.f ? d[e] : d[e] * slope;
-            const float xh = (v[e] - mu[e]) * is[e];
-            o[e] = sc[e] * (g - mg[e] - xh * mgx[e]);
-        }
+        for (int e = 0; e < 4; ++e) o[e] = vd_bn_bwd_dz(v[e], d[e], sc[e], sh[e], mu[e], is[e], mg[e], mgx[e], slope);
         vd_st4(dx, i, o);
         amx = fmaxf(amx, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
     }
@@ -509,12 +505,8 @@ __device__ __forceinline__ void bn_bwd_trip(const T* __restrict__ x, const T* __
         if (!ok[j]) continue;
         VEC o;
 #pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const float u = v[j][e] * k.sc[e] + k.sh[e];
-            const float g = u > 0.f ? d[j][e] : d[j][e] * slope;
-            const float xh = (v[j][e] - k.mu[e]) * k.is[e];
-            o[e] = k.sc[e] * (g - k.mg[e] - xh * k.mgx[e]);
-        }
+        for (int e = 0; e < V; ++e)
+            o[e] = vd_bn_bwd_dz(v[j][e], d[j][e], k.sc[e], k.sh[e], k.mu[e], k.is[e], k.mg[e], k.mgx[e], slope);
         bn_io<V, false>::st(dx, i + j * stride, o);
         amx = bn_vec_amax<V>(amx, o);
     }

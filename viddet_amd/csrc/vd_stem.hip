@@ -15,6 +15,7 @@
 //               straight from global memory - lane (co, pixel parity) reads dz coalesced, lane (k, pixel parity)
 //               gathers its frame value - no LDS, no im2col; per-block partial tiles + a fixed-order reduction.
 #include "vd_common.h"
+#include "vd_bn_math.h"
 #include <stdlib.h>
 
 namespace {
@@ -191,12 +192,48 @@ __global__ __launch_bounds__(SPX) void k_stem_fwd(const float* __restrict__ x, c
     }
 }
 
+// The fused forms of the two weight-gradient kernels (BN = true, vd_stem_wgrad_bn): the stem's dz has this one consumer,
+// so it is never stored.  The kernels' `dz` operand is then the conv output z, and the lane of output channel co computes
+// its dz element from z[p][co], dy[p][co] and the six constants of channel co - the arithmetic of vd_bn_bwd_apply
+// (vd_bn_math.h), rounded to the storage type as the stored dz was - where the plain forms load it.  Everything behind
+// that value (pixel order, MFMA sequence, partial tiles, reduction) is shared, so the weight gradient has the same bits.
+template <typename T>
+struct stem_bn_args {
+    const T* dy;                   // gradient of the cell's output [N*H*W][ldy]
+    int ldy;
+    const float *scale, *shift, *mean, *invstd;
+    const double* sums2;           // fp64 [2 * 32]: sum g, sum g * xhat
+    double count;
+    float slope;
+};
+
+// the constants of one lane's channel
+struct stem_bn_lane {
+    float sc, sh, mu, is, mg, mgx, slope;
+    template <typename T> __device__ __forceinline__ void load(const stem_bn_args<T>& bn, int co) {
+        const float inv_count = (float)(1.0 / bn.count);
+        sc = bn.scale[co];
+        sh = bn.shift[co];
+        mu = bn.mean[co];
+        is = bn.invstd[co];
+        mg = (float)bn.sums2[co] * inv_count;
+        mgx = (float)bn.sums2[SC + co] * inv_count;
+        slope = bn.slope;
+    }
+    template <typename T> __device__ __forceinline__ float dz(float z, float dy) const {
+        const float v = vd_bn_bwd_dz(z, dy, sc, sh, mu, is, mg, mgx, slope);
+        if constexpr (sizeof(T) == 2) return (float)(__bf16)v;       // the bf16 rounding of the stored dz
+        else return v;
+    }
+};
+
 // Weight gradient.  One wave owns a run of pixels; per MFMA (K = 2 pixels): A[co = lane&31][px = lane>>5] = dz, coalesced
 // 128-B rows; B[px][k = lane&31] = x[n][c(k)][y + dy(k)][x + dx(k)] (zero outside the frame and for k >= 27).
 // part: [gridDim.x * 4 waves][32 co][32 k] partial tiles, summed in wave order by k_stem_wgrad_reduce.
-template <typename T>      // storage type of dz (float, or __bf16 in bf16-storage training)
+template <typename T, bool BN>      // T: storage type of dz (float, or __bf16 in bf16-storage training)
 __global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ x, const T* __restrict__ dz, int ldd,
-                                                    float* __restrict__ part, int N, int H, int W, int64_t px_per_wave) {
+                                                    const stem_bn_args<T> bn, float* __restrict__ part, int N, int H, int W,
+                                                    int64_t px_per_wave) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t HW = (int64_t)H * W, P = (int64_t)N * HW;
     const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
@@ -222,19 +259,26 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ x,
     // batches of UNR steps: all 2*UNR loads of a batch are issued before its MFMAs (one step at a time left a single
     // pair of loads in flight per wave: latency bound at 1.4 TB/s)
     constexpr int UNR = 8;
+    stem_bn_lane kc;
+    if constexpr (BN) kc.load(bn, k);
     for (; p - par < p_end; p += 2 * UNR) {           // wave-uniform trip count (p - par is the batch's first pixel)
-        float a[UNR], b[UNR];
+        float a[UNR], b[UNR], g[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const int64_t pu = p + 2 * u;
             const bool in_run = pu < p_end;
             a[u] = in_run ? (float)dz[pu * ldd + k] : 0.f;                   // k doubles as co for the A operand
+            if constexpr (BN) g[u] = in_run ? (float)bn.dy[pu * bn.ldy + k] : 0.f;
             const int iy = y + dy, ix = xx + dx;
             const bool ok = in_run && k_ok && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
             b[u] = ok ? x[((int64_t)n * 3 + c) * HW + (int64_t)iy * W + ix] : 0.f;
             xx += 2;
             while (xx >= W) { xx -= W; ++y; }
             if (y >= H) { y -= H; ++n; }
+        }
+        if constexpr (BN) {                            // dz of the loaded pixels; exact zeros past the run, as above
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) a[u] = p + 2 * u < p_end ? kc.dz<T>(a[u], g[u]) : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
@@ -255,10 +299,26 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const float* __restrict__ x,
 // banks), the dz rows stream as before, and the four waves' tiles are summed in LDS (wave order) into ONE partial tile per
 // workgroup.  part: [N * ceil(H / 4)][32 co][32 k].
 constexpr int SROWS = 4;
-template <typename T>
+constexpr int SPATCH = 16 * SC;            // elements of one wave's dz patch of the VEC form: one batch of 16 pixels
+
+// lanes of one wave exchange data through LDS: the wave's LDS instructions execute in order, the fences keep the compiler
+// from moving the reads above the writes (and the next batch's writes above the reads)
+__device__ __forceinline__ void stem_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// VEC (with BN): z and dy are loaded as 16-byte vectors - lane = (pixel of the batch, 4 fp32 / 8 bf16 channels) - instead of
+// one element per lane (2-byte loads of bf16 tensors ran at 1.2 TB/s), dz is computed on that layout, each element by the same
+// function from the same operands, and handed to the operand layout through a 16-pixel x 32-channel patch per wave in LDS
+// behind the window: every operand lane receives the same value in the same step.  Needs 16-byte aligned rows.
+template <typename T, bool BN, bool VEC = false>
 __global__ __launch_bounds__(256) void k_stem_wgrad_rows(const float* __restrict__ x, const T* __restrict__ dz, int ldd,
-                                                         float* __restrict__ part, int N, int H, int W, int P) {
-    extern __shared__ float win[];                    // [3][SROWS + 2][P]; afterwards [4][32 * 32] for the wave tiles
+                                                         const stem_bn_args<T> bn, float* __restrict__ part, int N, int H,
+                                                         int W, int P) {
+    // [3][SROWS + 2][P]; afterwards [4][32 * 32] for the wave tiles; VEC: behind the larger of the two, [4 waves][SPATCH] of T
+    extern __shared__ __attribute__((aligned(16))) float win[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int groups = (H + SROWS - 1) / SROWS;
     const int n = blockIdx.x / groups, y0 = (blockIdx.x % groups) * SROWS;
@@ -283,13 +343,73 @@ __global__ __launch_bounds__(256) void k_stem_wgrad_rows(const float* __restrict
         const float* b0 = win + (c * (SROWS + 2) + wave + tap / 3) * P + (tap % 3) + par;
         const T* a0 = dz + ((int64_t)n * HW + (int64_t)y * W + par) * ldd + k;          // k doubles as co for the A operand
         constexpr int UNR = 8;
+        stem_bn_lane kc;
+        const T* g0 = nullptr;
+        if constexpr (BN && !VEC) {
+            kc.load(bn, k);
+            g0 = bn.dy + ((int64_t)n * HW + (int64_t)y * W + par) * bn.ldy + k;
+        }
+        if constexpr (BN && VEC) {
+            constexpr int VC = 16 / (int)sizeof(T);           // channels per vector: 4 (fp32) or 8 (bf16)
+            constexpr int LPP = SC / VC, PPL = 64 / LPP;      // lanes per pixel, pixels per wave-wide load
+            constexpr int NL = 2 * UNR / PPL;                 // loads per tensor and batch: 2 (fp32) or 1 (bf16)
+            typedef typename vd_select<sizeof(T) == 2, vd_bf16x8, f32x4>::type vec_t;
+            const int tile_floats = 4 * SC * 32, win_floats = 3 * (SROWS + 2) * P;
+            T* patch = reinterpret_cast<T*>(win + (win_floats > tile_floats ? win_floats : tile_floats)) + wave * SPATCH;
+            const int vp = lane / LPP, vc = (lane % LPP) * VC;
+            stem_bn_lane kv[VC];
+#pragma unroll
+            for (int e = 0; e < VC; ++e) kv[e].load(bn, vc + e);
+            const T* zr = dz + ((int64_t)n * HW + (int64_t)y * W) * ldd + vc;
+            const T* gr = bn.dy + ((int64_t)n * HW + (int64_t)y * W) * bn.ldy + vc;
+            vec_t zv[NL], gv[NL];
+            auto load = [&](int x0) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) {
+                    const int px = x0 + j * PPL + vp;
+                    if (px < W) {
+                        zv[j] = *reinterpret_cast<const vec_t*>(zr + (int64_t)px * ldd);
+                        gv[j] = *reinterpret_cast<const vec_t*>(gr + (int64_t)px * bn.ldy);
+                    }
+                }
+            };
+            load(0);
+            for (int x0 = 0; x0 < W; x0 += 2 * UNR) {
+#pragma unroll
+                for (int j = 0; j < NL; ++j) {
+                    if (x0 + j * PPL + vp < W) {               // pixels past the row: not loaded, not computed, not read below
+                        vec_t o;
+#pragma unroll
+                        for (int e = 0; e < VC; ++e) o[e] = (T)kv[e].template dz<T>((float)zv[j][e], (float)gv[j][e]);
+                        *reinterpret_cast<vec_t*>(patch + (j * PPL + vp) * SC + vc) = o;
+                    }
+                }
+                if (x0 + 2 * UNR < W) load(x0 + 2 * UNR);      // the next batch's vectors fly during this batch's MFMAs
+                stem_wave_sync();
+                float a[UNR], b[UNR];
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) {
+                    const bool in = x0 + 2 * u + par < W;
+                    a[u] = in ? (float)patch[(2 * u + par) * SC + k] : 0.f;
+                    b[u] = (in && k_ok) ? b0[x0 + 2 * u] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+                stem_wave_sync();                              // the patch is read: the next batch may overwrite it
+            }
+        } else
         for (int x0 = 0; x0 < W; x0 += 2 * UNR) {
-            float a[UNR], b[UNR];
+            float a[UNR], b[UNR], g[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const bool in = x0 + 2 * u + par < W;
                 a[u] = in ? (float)a0[(int64_t)(x0 + 2 * u) * ldd] : 0.f;
+                if constexpr (BN) g[u] = in ? (float)g0[(int64_t)(x0 + 2 * u) * bn.ldy] : 0.f;
                 b[u] = (in && k_ok) ? b0[x0 + 2 * u] : 0.f;
+            }
+            if constexpr (BN) {                        // dz of the loaded pixels; exact zeros past the row, as above
+#pragma unroll
+                for (int u = 0; u < UNR; ++u) a[u] = x0 + 2 * u + par < W ? kc.dz<T>(a[u], g[u]) : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
@@ -372,6 +492,12 @@ static bool stem_rows_ok(int W) {
     static const int on = getenv("VD_STEM_WGRAD_ROWS") ? atoi(getenv("VD_STEM_WGRAD_ROWS")) : 1;
     return on && stem_rows_lds(W) <= 64 * 1024;
 }
+// the fused row form loads z and dy as 16-byte vectors through an LDS patch (k_stem_wgrad_rows VEC) or one element per lane;
+// VD_STEM_BN_VEC=0 / 1: developer A/B, read at every launch (a test runs both forms in one process).  Default: DESIGN.md 8.3
+static bool stem_bn_vec(bool bf16) {
+    const char* e = getenv("VD_STEM_BN_VEC");
+    return e ? atoi(e) != 0 : bf16;
+}
 static int64_t stem_run_waves(int N, int H, int W) {
     const int64_t P = (int64_t)N * H * W;
     int64_t waves = vd_cdiv(P, 256);                 // >= 128 MFMA steps per wave
@@ -385,8 +511,46 @@ int64_t vd_stem_wgrad_ws_bytes(int N, int H, int W) {
     return (tiles + STEM_RED_CHUNKS) * SC * 32 * (int64_t)sizeof(float);
 }
 
-static int stem_wgrad_any(const float* x_nchw, const void* dz, int dz_bf16, int ldd, float* dwp, int N, int H, int W, void* ws,
-                         int64_t ws_bytes, void* stream) {
+// the BatchNorm operands of the fused entry points as the caller passes them; dy == NULL: the plain forms on a stored dz
+struct stem_bn_host {
+    const void* dy;
+    int ldy;
+    const float *scale, *shift, *mean, *invstd;
+    const double* sums2;
+    double count;
+    float slope;
+};
+
+extern "C++" {
+template <typename T, bool BN>
+static void stem_wgrad_launch(const float* x_nchw, const void* dz, int ldd, const stem_bn_host& h, float* part, int N, int H, int W,
+                              int64_t* tiles, hipStream_t s) {
+    const stem_bn_args<T> bn = {(const T*)h.dy, h.ldy, h.scale, h.shift, h.mean, h.invstd, h.sums2, h.count, h.slope};
+    if (stem_rows_ok(W)) {
+        *tiles = (int64_t)N * vd_cdiv(H, SROWS);
+        const int P = stem_rows_pitch(W), lds = (int)stem_rows_lds(W), lds_vec = lds + 4 * SPATCH * (int)sizeof(T);
+        // the fused form's 16-byte loads (VEC): rows of z and dy 16-byte aligned, the patch fits beside the window
+        const bool vec = BN && stem_bn_vec(sizeof(T) == 2) && lds_vec <= 64 * 1024 &&
+                         (((uintptr_t)dz | (uintptr_t)h.dy | (uintptr_t)(ldd * sizeof(T)) | (uintptr_t)(h.ldy * sizeof(T))) & 15) == 0;
+        if (vec)
+            hipLaunchKernelGGL((k_stem_wgrad_rows<T, BN, BN>), dim3((unsigned)*tiles), dim3(256), lds_vec, s, x_nchw, (const T*)dz, ldd,
+                               bn, part, N, H, W, P);
+        else
+            hipLaunchKernelGGL((k_stem_wgrad_rows<T, BN>), dim3((unsigned)*tiles), dim3(256), lds, s, x_nchw, (const T*)dz, ldd, bn, part,
+                               N, H, W, P);
+    } else {
+        const int64_t P = (int64_t)N * H * W;
+        *tiles = stem_run_waves(N, H, W);
+        int64_t ppw = vd_cdiv(P, *tiles);
+        ppw = vd_cdiv(ppw, 2) * 2;                       // even: a step is two pixels
+        hipLaunchKernelGGL((k_stem_wgrad<T, BN>), dim3((unsigned)(*tiles / 4)), dim3(256), 0, s, x_nchw, (const T*)dz, ldd, bn, part,
+                           N, H, W, ppw);
+    }
+}
+}  // extern "C++"
+
+static int stem_wgrad_any(const float* x_nchw, const void* dz, int dz_bf16, int ldd, const stem_bn_host& bn, float* dwp, int N,
+                          int H, int W, void* ws, int64_t ws_bytes, void* stream) {
     VD_REQUIRE(x_nchw && dz && dwp && N > 0 && H > 0 && W > 0 && ldd >= SC, "vd_stem_wgrad: bad args");
     const int64_t need = vd_stem_wgrad_ws_bytes(N, H, W);
     if (!ws || ws_bytes < need) {
@@ -394,27 +558,13 @@ static int stem_wgrad_any(const float* x_nchw, const void* dz, int dz_bf16, int 
         return VD_EWORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    int64_t tiles;
-    if (stem_rows_ok(W)) {
-        tiles = (int64_t)N * vd_cdiv(H, SROWS);
-        const int P = stem_rows_pitch(W), lds = (int)stem_rows_lds(W);
-        if (dz_bf16)
-            hipLaunchKernelGGL(k_stem_wgrad_rows<__bf16>, dim3((unsigned)tiles), dim3(256), lds, s, x_nchw, (const __bf16*)dz, ldd,
-                               (float*)ws, N, H, W, P);
-        else
-            hipLaunchKernelGGL(k_stem_wgrad_rows<float>, dim3((unsigned)tiles), dim3(256), lds, s, x_nchw, (const float*)dz, ldd,
-                               (float*)ws, N, H, W, P);
+    int64_t tiles = 0;
+    if (bn.dy) {
+        if (dz_bf16) stem_wgrad_launch<__bf16, true>(x_nchw, dz, ldd, bn, (float*)ws, N, H, W, &tiles, s);
+        else stem_wgrad_launch<float, true>(x_nchw, dz, ldd, bn, (float*)ws, N, H, W, &tiles, s);
     } else {
-        const int64_t P = (int64_t)N * H * W;
-        tiles = stem_run_waves(N, H, W);
-        int64_t ppw = vd_cdiv(P, tiles);
-        ppw = vd_cdiv(ppw, 2) * 2;                       // even: a step is two pixels
-        if (dz_bf16)
-            hipLaunchKernelGGL(k_stem_wgrad<__bf16>, dim3((unsigned)(tiles / 4)), dim3(256), 0, s, x_nchw, (const __bf16*)dz, ldd, (float*)ws,
-                               N, H, W, ppw);
-        else
-            hipLaunchKernelGGL(k_stem_wgrad<float>, dim3((unsigned)(tiles / 4)), dim3(256), 0, s, x_nchw, (const float*)dz, ldd, (float*)ws,
-                               N, H, W, ppw);
+        if (dz_bf16) stem_wgrad_launch<__bf16, false>(x_nchw, dz, ldd, bn, (float*)ws, N, H, W, &tiles, s);
+        else stem_wgrad_launch<float, false>(x_nchw, dz, ldd, bn, (float*)ws, N, H, W, &tiles, s);
     }
     VD_CHECK_LAUNCH("vd_stem_wgrad");
     float* lvl1 = (float*)ws + tiles * (SC * 32);
@@ -427,13 +577,30 @@ static int stem_wgrad_any(const float* x_nchw, const void* dz, int dz_bf16, int 
 
 int vd_stem_wgrad(const float* x_nchw, const float* dz, int ldd, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes,
                   void* stream) {
-    return stem_wgrad_any(x_nchw, dz, 0, ldd, dwp, N, H, W, ws, ws_bytes, stream);
+    return stem_wgrad_any(x_nchw, dz, 0, ldd, stem_bn_host{}, dwp, N, H, W, ws, ws_bytes, stream);
 }
 
 /* dz stored as bf16 (bf16-storage training); frames and the weight gradient stay fp32 */
 int vd_stem_wgrad_bf16(const float* x_nchw, const void* dz, int ldd, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes,
                        void* stream) {
-    return stem_wgrad_any(x_nchw, dz, 1, ldd, dwp, N, H, W, ws, ws_bytes, stream);
+    return stem_wgrad_any(x_nchw, dz, 1, ldd, stem_bn_host{}, dwp, N, H, W, ws, ws_bytes, stream);
+}
+
+/* the fused forms: dz = BatchNorm (+ LeakyReLU) backward of (z, dy), computed per element instead of loaded */
+int vd_stem_wgrad_bn(const float* x_nchw, const float* z, int ldz, const float* dy, int ldy, const float* scale, const float* shift,
+                     const float* save_mean, const float* save_invstd, const double* sums2, double count, float slope, float* dwp,
+                     int N, int H, int W, void* ws, int64_t ws_bytes, void* stream) {
+    VD_REQUIRE(dy && ldy >= SC && scale && shift && save_mean && save_invstd && sums2 && count > 0, "vd_stem_wgrad_bn: bad args");
+    const stem_bn_host bn = {dy, ldy, scale, shift, save_mean, save_invstd, sums2, count, slope};
+    return stem_wgrad_any(x_nchw, z, 0, ldz, bn, dwp, N, H, W, ws, ws_bytes, stream);
+}
+
+int vd_stem_wgrad_bn_bf16(const float* x_nchw, const void* z, int ldz, const void* dy, int ldy, const float* scale,
+                          const float* shift, const float* save_mean, const float* save_invstd, const double* sums2, double count,
+                          float slope, float* dwp, int N, int H, int W, void* ws, int64_t ws_bytes, void* stream) {
+    VD_REQUIRE(dy && ldy >= SC && scale && shift && save_mean && save_invstd && sums2 && count > 0, "vd_stem_wgrad_bn_bf16: bad args");
+    const stem_bn_host bn = {dy, ldy, scale, shift, save_mean, save_invstd, sums2, count, slope};
+    return stem_wgrad_any(x_nchw, z, 1, ldz, bn, dwp, N, H, W, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

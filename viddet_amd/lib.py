@@ -133,6 +133,7 @@ SIGNATURES = {
     "vd_stem_conv_c32_bf16": (_i, [_p, _p, _p, _p, C.c_float, C.POINTER(ConvDesc), _p]),
     "vd_stem_wgrad_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_stem_wgrad": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i64, _p]),
+    "vd_stem_wgrad_bn": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _d, _f, _p, _i, _i, _i, _p, _i64, _p]),
     "vd_preprocess_u8_nhwc": (_i, [_p, _p, _i64, _p]),
     "vd_preprocess_u8_nchw": (_i, [_p, _p, _i, _i, _i, _p]),
     "vd_temporal_pool": (_i, [_p, _p, _p, _i, _i, _i64, _i, _p]),
@@ -170,6 +171,7 @@ SIGNATURES = {
     "vd_pack_weight_dgrad_bf16": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _p]),
     "vd_upsample2x_concat_bwd_bf16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "vd_stem_wgrad_bf16": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i64, _p]),
+    "vd_stem_wgrad_bn_bf16": (_i, [_p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _d, _f, _p, _i, _i, _i, _p, _i64, _p]),
     "vd_yolo_loss_fwd_bwd_bf16": (_i, [C.POINTER(HeadDesc), _p, _i, _p, _p, _p, _p, _p, _f, _i, _p,
                                        C.POINTER(_fp * 3), _p, _p, _i64, _p]),
     # the joins of streaming video detection off a ring of cached per-frame features (vd_stream.hip)

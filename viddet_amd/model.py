@@ -52,9 +52,11 @@ class Program:
         self.keep = []          # descriptor structs / tensors the records point into
         self.streams = []       # per-record side stream (torch.cuda.Stream) or None = current stream
 
-    def add(self, fname, *args, meta=None, stream=None):
+    def add(self, fname, *args, meta=None, stream=None, label=None):
+        """`label`: the name the record is listed under where that is a kernel family, not the entry point (the fused stem
+        weight gradient vd_stem_wgrad_bn is a `vd_stem_wgrad` record to everything that counts or times records by name)"""
         fn = getattr(L.load(), fname)
-        self.recs.append((fname, fn, args))
+        self.recs.append((label or fname, fn, args))
         self.meta.append(meta)
         self.streams.append(stream)
 
@@ -1574,7 +1576,9 @@ class YOLOV3(object):
         """Activation (and in training gradient) tensors of one input shape.  bf16: the tensors of bf16-storage training -
         bf16 activations and gradients, no max-abs slots; the head logits stay fp32 and the heads take the bf16 pitch
         (_bf16_pitch), zero-filled so that the logits' pad columns stay 0."""
-        ck = ('buf', B, H, W, train) + (('bf16',) if bf16 else ())
+        # VD_STEM_FUSE_BWD (train_plan.stem_fuse_bwd, default on): no plan stores the stem's dz, which sizes the dz scratch
+        stem_dz = train and not train_plan.stem_fuse_bwd()
+        ck = ('buf', B, H, W, train) + (('bf16',) if bf16 else ()) + (('stem_dz',) if stem_dz else ())
         if ck in self._programs:
             return self._programs[ck]
         dev = self.device
@@ -1628,8 +1632,11 @@ class YOLOV3(object):
                 if name != 'in':
                     bufs['d:' + name] = (torch.zeros_like if 'd:' + name in zeroed else torch.empty_like)(bufs[name], dtype=dt)
             mx = max(bufs[n.dst].numel() for n in self.conv_nodes)
-            bufs['dz'] = torch.empty(mx, dtype=dt, device=dev)
-            bufs['dz2'] = torch.empty(mx, dtype=dt, device=dev)
+            # the two dz scratch buffers: the largest cell that stores a dz (the fused stem does not: TrainPlan.stem_fused)
+            mz = mx if stem_dz else max(bufs[n.dst].numel() for n in self.conv_nodes
+                                        if not (n.stem and n.bn and not getattr(n, 'tvalid', False)))
+            bufs['dz'] = torch.empty(mz, dtype=dt, device=dev)
+            bufs['dz2'] = torch.empty(mz, dtype=dt, device=dev)
             bufs['tmp'] = torch.empty(mx, dtype=dt, device=dev)
         # The plan-time autotuner times candidate kernels in place on these buffers.  Fresh allocations are zero pages, and on
         # all-zero operands the chip holds a ~20 % higher clock - for every candidate, but not equally: stand-alone the 256x128
@@ -1711,6 +1718,10 @@ class YOLOV3(object):
         for i, n in enumerate(bn):
             # (the operand tensor behind a _conv21d cell is its temporal conv's output: per-channel taps, same channel scales)
             for k, name in ((0, n.tdw.dst if getattr(n, 'tdw', None) is not None else n.dst), (1, 'dz:' + n.name)):
+                if k == 1 and n.stem:
+                    # no launch reads the stem's dz max-abs slot: no data gradient flows into the frames, its weight
+                    # gradient is an fp32 MFMA kernel (vd_stem.hip), and the fused one never stores a dz at all
+                    continue
                 if fl[2 * i + k] and name not in self._range_exact:
                     new[name] = float(ra[2 * i + k])
         if new:

@@ -325,6 +325,15 @@ def stem_wgrad(x_nchw, dz, dwp, ws):
     check(fn(ptr(x_nchw), ptr(dz), dz.shape[-1], ptr(dwp), N, H, W, ptr(ws), ws.numel() * ws.element_size(), _s()), "vd_stem_wgrad")
 
 
+def stem_wgrad_bn(x_nchw, z, dy, scale, shift, smean, sinv, sums2, count, dwp, ws, slope=0.1):
+    """The stem's weight gradient with dz = BatchNorm (+ LeakyReLU) backward of (z, dy) computed inside the kernel; z and dy
+    [N,H,W,ld] with their own row pitches (ld = shape[-1] of the tensor passed; channels 0..31 are read)."""
+    N, _, H, W = x_nchw.shape
+    fn = _lib().vd_stem_wgrad_bn_bf16 if z.dtype == torch.bfloat16 else _lib().vd_stem_wgrad_bn
+    check(fn(ptr(x_nchw), ptr(z), z.shape[-1], ptr(dy), dy.shape[-1], ptr(scale), ptr(shift), ptr(smean), ptr(sinv), ptr(sums2),
+             float(count), slope, ptr(dwp), N, H, W, ptr(ws), ws.numel() * ws.element_size(), _s()), "vd_stem_wgrad_bn")
+
+
 def bn_stats(x2d_rows, C_, x, sums, ws):
     fn = _lib().vd_bn_stats_bf16 if x.dtype == torch.bfloat16 else _lib().vd_bn_stats
     check(fn(ptr(x), x2d_rows, C_, ptr(sums), ptr(ws), ws.numel() * ws.element_size(), _s()), "vd_bn_stats")

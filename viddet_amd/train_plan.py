@@ -30,6 +30,13 @@ class Switches:
         self.parity_streams = env.get('VD_PARITY_STREAMS', '1') == '1'
         self.fuse_bwd_s2 = env.get('VD_FUSE_BWD_S2', '1') == '1'             # fused BN-backward reductions in stride-2 data gradients
         self.autotune = env.get('VD_AUTOTUNE', '1') != '0'                   # (fused_s2: 'auto' arithmetic needs the autotuner)
+        self.stem_fuse_bwd = stem_fuse_bwd(env)                              # stem dz computed inside its weight gradient
+
+
+def stem_fuse_bwd(env=os.environ):
+    """VD_STEM_FUSE_BWD (default 1): the stem's BatchNorm-backward apply pass runs inside its weight-gradient kernel
+    (vd_stem_wgrad_bn) and its dz is never stored; also sizes the dz scratch (YOLOV3._buffers)"""
+    return env.get('VD_STEM_FUSE_BWD', '1') == '1'
 
 
 class TrainPlan:
@@ -376,18 +383,18 @@ class TrainPlan:
             if not self.net.alias_skip_grad:
                 self.materialize(n.residual)
 
-    def side_launch(self, *wargs, meta):
+    def side_launch(self, *wargs, meta, label=None):
         """A weight-gradient launch (`wargs`: entry point and arguments up to the workspace) on the side stream, between
         an event pair: main records `ready`, the side stream waits for it, runs the launch on its own workspace and records
         `done`.  Returns `done` (None without a side stream: the launch is on the main stream)."""
         seg, side = self.seg, self.side
         if side is None:
-            seg.add(*wargs, self.ws.data_ptr(), self.ws_bytes, meta=meta)
+            seg.add(*wargs, self.ws.data_ptr(), self.ws_bytes, meta=meta, label=label)
             return None
         e_ready, e_done = torch.cuda.Event(), torch.cuda.Event()
         seg.add_py(ev_record(e_ready))
         seg.add_py(ev_wait(e_ready, side))
-        seg.add(*wargs, self.ws_w.data_ptr(), self.ws_bytes, meta=meta, stream=side)
+        seg.add(*wargs, self.ws_w.data_ptr(), self.ws_bytes, meta=meta, stream=side, label=label)
         seg.add_py(ev_record(e_done, side))
         seg.hold(e_ready, e_done)
         self.last_side = e_done
@@ -651,14 +658,16 @@ class TrainPlan:
         self.seg.add('vd_bn_param_grads', sums.data_ptr(), n.co_pad, self.bufs['tmp'].data_ptr(), n.gbias.data_ptr())
         return dz
 
+    def stem_fused(self, n):
+        """the stem cell whose apply pass is left to its weight-gradient kernel (VD_STEM_FUSE_BWD; a `tvalid` stem keeps
+        the stored dz: its frame slice reads it)"""
+        return self.sw.stem_fuse_bwd and n.stem and n.bn and not getattr(n, 'tvalid', False)
+
     def bn_backward(self, n, dy):
         """BatchNorm (+ LeakyReLU) backward of conv cell n: reduce, SyncBN exchange, apply into one of the two dz scratch
-        buffers, frame slice.  Returns (dz, its scratch slot)."""
+        buffers, frame slice.  Returns (dz, its scratch slot); (None, None) for the fused stem."""
         seg, bufs, sfx, M = self.seg, self.bufs, self.sfx, self.out_rows(n)
         z = bufs['z:' + n.dst]
-        slot = self.n_dz % 2
-        self.n_dz += 1
-        dz = self.dz_bufs[slot][:M * n.cout].view(-1, self.H // n.div_out, self.W // n.div_out, n.cout)
         bn = (n.b_scale.data_ptr(), n.b_shift.data_ptr(), n.b_mean.data_ptr(), n.b_invstd.data_ptr())
         if n.name not in self.fused_bwd:      # (fused: sums and gamma / beta gradients came with the table reduction)
             seg.add('vd_bn_bwd_reduce' + sfx, z.data_ptr(), dy.data_ptr(), *bn, M, n.cout, LEAKY_SLOPE, n.sums2.data_ptr(),
@@ -668,6 +677,15 @@ class TrainPlan:
         if self.net._syncbn(n):          # [sum g, sum g xhat] over the ranks (the local gamma / beta gradients came first)
             seg.add_coll(self.net._syncbn_exchange(n.sums2))
             count = float(M * self.world)
+        if self.stem_fused(n):
+            # dz has one consumer, the stem's weight gradient (no gradient flows into the frames), which computes it from z
+            # and dy itself (conv_wgrad): no apply pass, no dz, no scratch slot.  With the stem weight frozen nothing reads it.
+            self.stem_bn = (z, dy, bn, count)
+            return None, None
+        slot = self.n_dz % 2
+        self.n_dz += 1
+        assert M * n.cout <= self.dz_bufs[slot].numel(), "dz scratch too small for " + n.name
+        dz = self.dz_bufs[slot][:M * n.cout].view(-1, self.H // n.div_out, self.W // n.div_out, n.cout)
         if self.side is not None and self.dz_free[slot] is not None:
             seg.add_py(ev_wait(self.dz_free[slot]))           # the wgrad that read this scratch has finished
         seg.add('vd_bn_bwd_apply' + sfx, z.data_ptr(), dy.data_ptr(), *bn, n.sums2.data_ptr(), count, M, n.cout, LEAKY_SLOPE,
@@ -684,7 +702,16 @@ class TrainPlan:
         """weight gradient straight into the gradient arena (same fwd-packed layout as the weights)"""
         net, bufs, B, H, W = self.net, self.bufs, self.B, self.H, self.W
         Hi, Wi = H // n.div_in, W // n.div_in
-        if n.stem:
+        label = None
+        if n.stem and dz is None:
+            # the fused stem (bn_backward): dz computed per element from z and dy inside the kernel; the `ready` event of
+            # side_launch follows the reductions and the SyncBN exchange of sums2 on the main stream.  Listed under the
+            # family name of the weight gradient it replaces.
+            z, dy, bn, count = self.stem_bn
+            label = 'vd_stem_wgrad' + self.sfx
+            wargs = ('vd_stem_wgrad_bn' + self.sfx, bufs['in'].data_ptr(), z.data_ptr(), z.shape[-1], dy.data_ptr(), dy.shape[-1],
+                     *bn, n.sums2.data_ptr(), count, LEAKY_SLOPE, n.gwp.data_ptr(), B * n.fr, Hi, Wi)
+        elif n.stem:
             # both operands straight from global memory: the NCHW batch and dz (vd_stem.hip)
             wargs = ('vd_stem_wgrad' + self.sfx, bufs['in'].data_ptr(), dz.data_ptr(), n.co_pad, n.gwp.data_ptr(),
                      B * n.fr, Hi, Wi)
@@ -704,8 +731,11 @@ class TrainPlan:
                 autotune_wgrad(wd_, self.ws.data_ptr(), self.ws_bytes)
             self.seg.hold(wd_)
             wargs = ('vd_conv_wgrad', C.byref(wd_))
-        e_done = self.side_launch(*wargs, meta=net._flops(n, B, H, W, 'wgrad', self.esz))
-        if e_done is not None and not n.head:
+        meta = net._flops(n, B, H, W, 'wgrad', self.esz)
+        if label is not None:
+            meta['bytes'] += float(self.esz) * self.stem_bn[0].numel()       # the fused stem reads z and dy where it read dz
+        e_done = self.side_launch(*wargs, meta=meta, label=label)
+        if e_done is not None and slot is not None:
             self.dz_free[slot] = e_done
         self.close_bucket(n, n is self.first_wtrain or n.stem)
 

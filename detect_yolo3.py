@@ -19,7 +19,9 @@ reference counterpart) runs sequence NMS over the detections of every clip on th
 predictions and results are written as without it, the rescored ones beside them under pred_seq and *_seq.  `--track` (no
 reference counterpart) links the detections of every clip into tracks on the device (vd_track): every prediction
 set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
-clip; everything else is written as without the flag.  Visualisation and the worst-video tool are out of scope.
+clip; everything else is written as without the flag.  `--live` (with --stream; no reference counterpart) sends every clip
+through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
+the files and results are those of --stream byte for byte.  Visualisation and the worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -124,6 +126,12 @@ def parse_flags(argv=None):
            "(--stream or --synthetic_videos).  Every prediction set gets a twin (pred_trk, pred_seq_trk) whose lines end in the "
            "row's track id (-1: none), and tracks.txt / tracks_seq.txt hold `clip tracks rows mean_len` per clip; everything "
            "else is written as without the flag (DESIGN.md 28)")
+    A("--live", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --stream: every clip goes through a live session (net.open_video) in pushes of "
+           "--live_push frames and a flush, as a camera or a decoder would hand it over; the prediction files and results are "
+           "those of --stream byte for byte, --track included (its online ids are decided at the clip's end).  Not with "
+           "--seq_nms, which has no online form")
+    A("--live_push", type=int, default=1, help="--live: frames per push (default 1)")
     A("--track_iou", type=float, default=0.5, help="--track: a box joins a track where its IoU to the track's last box is at least this")
     A("--track_low", type=float, default=0.0, help="--track: detections scored below this take no part")
     A("--track_high", type=float, default=0.5, help="--track: a track is kept where its best score is at least this")
@@ -235,14 +243,35 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
     return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
 
+def live_clip(net, frames, step, chunk, push, track=None):
+    """--live: detect_video(frames, step, chunk, track) by way of a live session - pushes of `push` frames, then a flush ->
+    (ids, scores, bboxes, the (track, tlen, tscore) of detect_video's last_tracks or None).  The session's online tracker
+    decides nothing; finalize_tracks decides at the clip's end, from the rows the session gave out."""
+    session = net.open_video(step=step, chunk=chunk, track=track)
+    outs, trks = [], []
+    for a in range(0, frames.shape[0], push):
+        outs.append(session.push(frames[a:a + push])[1:])
+        trks.append(session.last_tracks)
+    outs.append(session.flush()[1:])
+    trks.append(session.last_tracks)
+    ids, scores, bboxes = (torch.cat(t) for t in zip(*outs))
+    assert ids.shape[0] == frames.shape[0], "the session gave out %d of %d frames" % (ids.shape[0], frames.shape[0])
+    if track is None:
+        return ids, scores, bboxes, None
+    from viddet_amd.track import finalize_tracks
+    online = [torch.cat(t).cpu().numpy() for t in zip(*trks)]
+    final = finalize_tracks(*online, **session.track_decide)
+    return ids, scores, bboxes, tuple(torch.from_numpy(a) for a in final)
+
+
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None):
+                  seq_nms=None, input_nms=0.45, track=None, live=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
     ones detect_video keeps in net.last_plain.  track (a dict): handed to detect_video too, which links the rows it returns;
     the plain rows ahead of Seq-NMS are linked by a call of their own; returns (boxes, rescored or None, tracks, tracks of the
-    rescored or None)."""
+    rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
@@ -256,7 +285,11 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         sidxs = [dataset.sample_index(v, t) for t in range(x.shape[0])]
         W = data_shape if device_resize else x.shape[-2]
         trk_kw = {} if track is None else dict(track=dict(track, clip=W))  # the tracker sees the boxes as they are saved too
-        if seq_nms is None:
+        if live is not None:
+            ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, trk_kw.get("track"))
+            if track is not None:
+                _collect_tracks(tracks, dataset, ids, last[0], sidxs)
+        elif seq_nms is None:
             ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, **trk_kw)
             if track is not None:
                 _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
@@ -311,6 +344,16 @@ def check_flags(FLAGS):
             raise NotImplementedError("--seq_nms_rescore must be avg or max, got %r" % (FLAGS.seq_nms_rescore,))
         if not 0 < getattr(FLAGS, "seq_nms_input_nms", 0.45) < 1:
             raise NotImplementedError("--seq_nms_input_nms must lie inside (0, 1), got %r" % (FLAGS.seq_nms_input_nms,))
+    if getattr(FLAGS, "live", False):
+        # a live session is detect_video on a clip that arrives in pieces
+        if not getattr(FLAGS, "stream", False):
+            raise NotImplementedError("--live needs --stream: a live session is the streaming path (net.detect_video) on a clip "
+                                      "that arrives in pieces; the windowed path has no clips to push")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--live does not combine with --seq_nms: Seq-NMS revisits every frame of a clip until no "
+                                      "row is alive, so no frame is final before the clip ends - it has no online form")
+        if isinstance(getattr(FLAGS, "live_push", 1), bool) or int(getattr(FLAGS, "live_push", 1)) < 1:
+            raise NotImplementedError("--live_push must be at least 1 (the frames per push), got %r" % (FLAGS.live_push,))
     if getattr(FLAGS, "track", False):
         # the tracker links the frames of a clip: refused where --seq_nms is, for its reasons
         if len(FLAGS.dataset) > 1:
@@ -533,7 +576,7 @@ def main(argv=None):
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
-                              **seq_kw)
+                              live=FLAGS.live_push if FLAGS.live else None, **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = None

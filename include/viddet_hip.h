@@ -768,6 +768,25 @@ int vd_track(const float* ids, const float* scores, const float* bboxes, const i
              int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
              int32_t* out_len, float* out_score, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The same tracker in resumable form, for a stream of frames that never says where it ends (vd_track_live.hip, DESIGN.md
+ * 31): what viddet_amd.track.track_online_host computes, bit for bit.  One launch runs the extend and start steps above, with the
+ * same arithmetic and tie rules, on the F frames of V streams - ids, scores [V][F][N], bboxes [V][F][N][4] - starting from each
+ * stream's state and leaving the new state behind; nothing is decided on the device, so sigma_h and t_min are no arguments
+ * (track.finalize_tracks decides on the host, once a clip has ended).  state: V blocks of VD_TRACK_STATE_BYTES, each
+ *   int32 n_active, int32 next_id, 8 bytes unused, then float4 box[1024], int32 class[1024], id[1024], misses[1024],
+ *   length[1024], float maximum[1024] - the active tracks in order of creation, the first n_active entries live.
+ * A block of all zero bytes is a fresh stream; n_active is clamped into [0, 1024] before it indexes anything; the live entries
+ * and the header are written back with ordinary stores.  Outputs, written in full, [V][F][N]: out_track int32 (the row's track
+ * id, a creation number counted over the whole stream from 0, one counter for all classes; -1 for a row that is no candidate),
+ * out_len int32 (the rows of its track so far, this one included; 0 beside -1), out_score (the track's maximum score so far; -1
+ * beside -1).  A stream hands out at most N ids per frame: the caller keeps frames * N below 2^31.  One workgroup per stream, no
+ * workspace, no atomics, bit-reproducible; the inputs are never written.  1 <= N <= 128, F >= 1, V >= 1, num_class >= 1,
+ * 0 <= max_age <= 7, no threshold NaN; bboxes and state 16-byte, every other pointer 4-byte aligned. */
+#define VD_TRACK_STATE_BYTES 36880
+int vd_track_push(const float* ids, const float* scores, const float* bboxes, int V, int F, int N, int num_class, float sigma_l,
+                  float sigma_iou, int max_age, void* state, int64_t state_bytes, int32_t* out_track, int32_t* out_len,
+                  float* out_score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

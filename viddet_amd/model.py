@@ -1274,6 +1274,7 @@ class YOLOV3(object):
         self._pack_stream = None         # weight layouts and remembers the version they were packed from
         self._pack_event = None
         self._graph_cache = {}
+        self._live = None                # the VideoSession with frames in flight, if any (open_video)
         self.use_graphs = False
         self.overlap_wgrad = os.environ.get('VD_OVERLAP', '1') != '0'   # wgrad GEMMs on a side stream (_build_train)
         self.fuse_bn_stats = os.environ.get('VD_FUSE_STATS', '1') != '0'  # BN statistics in the conv epilogue
@@ -2217,6 +2218,9 @@ class YOLOV3(object):
         why = self._stream_refusal()
         if why is not None:
             raise NotImplementedError("detect_video with " + why)
+        if self._live is not None:
+            raise RuntimeError("detect_video: %r has frames in flight on this net (they share the feature ring): flush() it first"
+                               % (self._live,))
         seq_kw = None
         if seq_nms is not None and seq_nms is not False:
             seq_kw = {} if seq_nms is True else dict(seq_nms)
@@ -2332,6 +2336,16 @@ class YOLOV3(object):
             boxes = res[2] if trk_clip is None else res[2].clamp(0, float(trk_clip))
             self.last_tracks = ops.track(res[0], res[1], boxes, num_class=1 if self.agnostic else self.num_class, **trk_kw)
         return res
+
+    def open_video(self, step=1, chunk=8, track=None):
+        """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and
+        whose length nobody knows - session.push(frames) returns the detections that are final by now, session.flush() ends
+        the clip.  Refused where detect_video is, in the same words, and while another session of this net has
+        frames in flight.  Seq-NMS has no online form and is no option here."""
+        if self._live is not None:
+            raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))
+        from .live import VideoSession
+        return VideoSession(self, step, chunk, track)
 
     def extract_features(self, x):
         """extract_base_features.py:127-130: f1 = features[:15](x), f2 = features[15:24](f1), f3 = features[24:](f2) in

@@ -659,6 +659,57 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
     return out_track, out_len, out_score
 
 
+class TrackState:
+    """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
+    device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -
+    and the fixed parameters.  push(ids, scores, bboxes) runs the next F frames of every stream: ids (V,F,N[,1]), scores
+    (V,F,N[,1]) and bboxes (V,F,N,4), contiguous fp32 device tensors (V == 1: the leading axis may be left out), ->
+    (track, tlen, tscore), new device tensors of the leading shape: the row's track id counted over the whole stream (-1: no
+    candidate), its track's length so far and maximum so far.  Launches on the current stream; nothing is downloaded and
+    nothing waits.  A stream hands out at most N ids per frame, so a push that could take frames * N past 2**31 - 1 is
+    refused (counted on the host).  reset() starts every stream afresh."""
+
+    def __init__(self, V=1, N=100, num_class=1, sigma_l=0.0, sigma_iou=0.5, max_age=0, device="cuda"):
+        from .track import check_params
+        self.sigma_l, _, self.sigma_iou, _, self.max_age = check_params(sigma_l, 0.5, sigma_iou, 1, max_age, "TrackState")
+        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
+                raise ValueError("TrackState: %s must be an integer in [1, %d], got %r" % (name, hi, v))
+        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
+        self.state = torch.zeros(self.V, L.TRACK_STATE_BYTES, dtype=torch.uint8, device=device)
+        self.frames = 0                               # pushed to every stream since the last reset
+
+    def reset(self):
+        self.state.zero_()
+        self.frames = 0
+
+    def push(self, ids, scores, bboxes):
+        V, N = self.V, self.N
+        lead = tuple(bboxes.shape[:-2])
+        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
+            raise ValueError("TrackState.push: bboxes must be (%d,F,%d,4)%s, got %r"
+                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
+        F = int(lead[-1])
+        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
+            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("TrackState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                                 % (name, n, t.dtype, tuple(t.shape)))
+        if (self.frames + F) * N > 2 ** 31 - 1:
+            raise ValueError("TrackState.push: %d + %d frames of %d rows could hand out more than 2**31 - 1 track ids; reset() "
+                             "the state (a new clip) first" % (self.frames, F, N))
+        dev = bboxes.device
+        out_track = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+        out_len = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+        out_score = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+        if F == 0:
+            return out_track, out_len, out_score
+        check(_lib().vd_track_push(ptr(ids), ptr(scores), ptr(bboxes), V, F, N, self.num_class, float(self.sigma_l),
+                                   float(self.sigma_iou), self.max_age, ptr(self.state), int(self.state.numel()), ptr(out_track),
+                                   ptr(out_len), ptr(out_score), _s()), "vd_track_push")
+        self.frames += F
+        return out_track, out_len, out_score
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

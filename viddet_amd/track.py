@@ -18,6 +18,9 @@ given) and score >= sigma_l.  Per clip, frames in order:
      renumbered.
 At most N * (max_age + 1) tracks are active at once: an active track has taken a row of one of the last max_age + 1 frames, and
 a row belongs to one track.
+
+`track_online_host` is steps 1 and 2 on a stream that never says where it ends, a state carried from call to call (DESIGN.md 31;
+vd_track_push, `ops.TrackState`, equals it bit for bit); `finalize_tracks` is step 3 on its rows, once a clip has ended.
 """
 import numpy as np
 
@@ -116,6 +119,88 @@ def track_host(ids, scores, bboxes, clip_start=None, num_class=None, sigma_l=0.0
     if stats is not None:
         stats["active"], stats["closed"], stats["tracks"] = n_active, n_closed, kept_per_clip
     return track, tlen, tscore
+
+
+def track_online_host(state, ids, scores, bboxes, num_class=None, sigma_l=0.0, sigma_iou=0.5, max_age=0):
+    """The tracker on a stream that never says where it ends (vd_track_push, `ops.TrackState`, equals it bit for
+    bit): track_host's extend and start steps on the given frames, starting from `state` (None: a fresh stream) ->
+    (the new state, track, tlen, tscore).  Per row, (F,N): `track` int32, the id of the row's track - a creation number counted
+    over the whole stream - or -1 for a row that is no candidate; `tlen` int32, the rows of its track so far, this one included
+    (0 beside -1); `tscore` float32, the track's maximum score so far (-1 beside -1).  Nothing is decided here, so sigma_h and
+    t_min are no arguments: finalize_tracks makes track_host's arrays of a finished clip's rows.  A state is a dict of 'next_id'
+    and 'active', the active tracks [id, class, last box, misses, length, maximum] in order of creation; the one given is not
+    changed.  Pushing a clip in pieces gives what one call on all of it gives."""
+    sl, _, si, _, max_age = check_params(sigma_l, 0.5, sigma_iou, 1, max_age, "track_online_host")
+    ids = np.asarray(ids, dtype=_F)
+    scores = np.asarray(scores, dtype=_F)
+    bboxes = np.asarray(bboxes, dtype=_F)
+    if bboxes.ndim != 3 or bboxes.shape[2] != 4 or ids.size != bboxes.shape[0] * bboxes.shape[1] or scores.size != ids.size:
+        raise ValueError("expected ids (F,N,1), scores (F,N,1), bboxes (F,N,4), got %r %r %r" % (ids.shape, scores.shape, bboxes.shape))
+    F, N = bboxes.shape[0], bboxes.shape[1]
+    sc = scores.reshape(F, N)
+    cls = row_classes(ids.reshape(F, N), sc, num_class)
+    with np.errstate(invalid="ignore"):
+        cls = np.where(sc >= sl, cls, -1)
+    track = np.full((F, N), -1, dtype=np.int32)
+    tlen = np.zeros((F, N), dtype=np.int32)
+    tscore = np.full((F, N), -1, dtype=_F)
+    next_id = 0 if state is None else int(state["next_id"])
+    active = [] if state is None else [[a[0], a[1], np.array(a[2], dtype=_F), a[3], a[4], _F(a[5])] for a in state["active"]]
+    for t in range(F):
+        free = cls[t] >= 0
+        if active and free.any():
+            iou = iou_matrix(np.stack([a[2] for a in active]), bboxes[t])              # (active, N), once per frame
+        survivors = []
+        for k, a in enumerate(active):
+            rows = np.nonzero(free & (cls[t] == a[1]))[0]
+            hit = False
+            if len(rows):
+                j = int(rows[np.argmax(iou[k, rows])])             # the first maximum: the lowest row of a tie
+                hit = bool(iou[k, j] >= si)
+            if hit:
+                free[j] = False
+                a[2], a[3] = bboxes[t, j].copy(), 0
+                a[4] += 1
+                if sc[t, j] > a[5]:
+                    a[5] = sc[t, j]
+                track[t, j], tlen[t, j], tscore[t, j] = a[0], a[4], a[5]
+            else:
+                a[3] += 1
+            if a[3] <= max_age:
+                survivors.append(a)
+        active = survivors
+        for j in np.nonzero(free)[0]:
+            active.append([next_id, int(cls[t, j]), bboxes[t, j].copy(), 0, 1, sc[t, j]])
+            track[t, j], tlen[t, j], tscore[t, j] = next_id, 1, sc[t, j]
+            next_id += 1
+    return dict(next_id=next_id, active=active), track, tlen, tscore
+
+
+def finalize_tracks(track, tlen, tscore, sigma_h=0.5, t_min=2):
+    """track_online_host's three outputs over ALL frames of one finished clip, (F,N) each -> track_host's three arrays: a
+    track's length and maximum are the largest `tlen` and `tscore` among its rows (both only grow, and its last row carries
+    them); it is kept iff its maximum >= sigma_h and it holds at least t_min rows; the rows of a dropped track become
+    -1 / 0 / -1.  Ids are not renumbered."""
+    _, sh, _, t_min, _ = check_params(0.0, sigma_h, 0.5, t_min, 0, "finalize_tracks")
+    track = np.asarray(track, dtype=np.int32)
+    tlen = np.asarray(tlen, dtype=np.int32)
+    tscore = np.asarray(tscore, dtype=_F)
+    if track.ndim != 2 or tlen.shape != track.shape or tscore.shape != track.shape:
+        raise ValueError("expected track, tlen and tscore (F,N), got %r %r %r" % (track.shape, tlen.shape, tscore.shape))
+    on = track >= 0
+    if not on.any():
+        return np.full(track.shape, -1, np.int32), np.zeros(track.shape, np.int32), np.full(track.shape, -1, _F)
+    # (ids are creation numbers: a clip of a session starts at 0; a clip cut out of a longer stream starts higher)
+    lo = int(track[on].min())
+    idx = np.where(on, track - lo, 0)
+    n = int(idx.max()) + 1
+    length = np.zeros(n, dtype=np.int32)
+    best = np.full(n, -np.inf, dtype=_F)
+    np.maximum.at(length, idx[on], tlen[on])
+    np.maximum.at(best, idx[on], tscore[on])
+    kept = on & ((best >= sh) & (length >= t_min))[idx]
+    return (np.where(kept, track, -1).astype(np.int32), np.where(kept, length[idx], 0).astype(np.int32),
+            np.where(kept, best[idx], _F(-1)).astype(_F))
 
 
 def clip_summary(track, tlen, clip_start=None):

@@ -21,7 +21,10 @@ reference counterpart) links the detections of every clip into tracks on the dev
 set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
 clip; everything else is written as without the flag.  `--live` (with --stream; no reference counterpart) sends every clip
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
-the files and results are those of --stream byte for byte.  Visualisation and the worst-video tool are out of scope.
+the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
+pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
+an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.  Visualisation
+and the worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -138,6 +141,16 @@ def parse_flags(argv=None):
     A("--track_min_len", type=int, default=2, help="--track: a track is kept where it holds at least this many boxes")
     A("--track_max_age", type=int, default=0,
       help="--track: the frames in a row a track may go without a box before it is closed, 0 (the paper) to 7")
+    A("--tubelet", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --track: a tubelet pass over every tracked clip on the device (vd_tubelet): the rows "
+           "of a track take the track's score, the frames a track skipped get a linearly interpolated box, every frame is "
+           "re-sorted.  Everything a run without the flag writes is written unchanged; the rows after the pass go to pred_tub, "
+           "their twin with track ids to pred_tub_trk, tracks_tub.txt and the --metrics files *_tub.txt (DESIGN.md 32).  Not with "
+           "--live (a hole is known only after its frame was given out) and not with --seq_nms")
+    A("--tubelet_rescore", default="avg", choices=["avg", "max", "none"], help="--tubelet: the score a track gives its rows (none: they keep theirs)")
+    A("--tubelet_max_gap", type=int, default=7, help="--tubelet: holes of up to this many frames are filled, 0 (none) to 7")
+    A("--tubelet_drop_untracked", type=_bool, nargs="?", const=True, default=False,
+      help="--tubelet: the rows that no kept track holds are dropped")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -171,6 +184,14 @@ def track_args(FLAGS):
                 max_age=FLAGS.track_max_age)
 
 
+def tubelet_args(FLAGS):
+    """the dict net.detect_video and ops.tubelet take, None without --tubelet"""
+    if not getattr(FLAGS, "tubelet", False):
+        return None
+    return dict(rescore=None if FLAGS.tubelet_rescore == "none" else FLAGS.tubelet_rescore, max_gap=FLAGS.tubelet_max_gap,
+                drop_untracked=FLAGS.tubelet_drop_untracked)
+
+
 def _collect_tracks(tracks, dataset, ids, track, sidxs):
     """the track id of every row _collect files, in its order, under the same image path"""
     ids, track = ids.cpu().numpy(), track.cpu().numpy()
@@ -189,12 +210,14 @@ def clip_offsets(sidxs, frames_per_video):
     return cs + [len(sidxs)]
 
 
-def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None):
+def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None, tubelet=None):
     """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
     (--device_resize: raw frames, resized on the device).  seq_nms (a dict of link_thresh / nms_thresh / rescore): every
     batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored).
     track (a dict of ops.track's parameters): the outputs stay on the device likewise and ONE ops.track call per prediction set
-    follows; returns (boxes, rescored or None, tracks, tracks of the rescored or None)."""
+    follows; returns (boxes, rescored or None, tracks, tracks of the rescored or None).  tubelet (a dict of ops.tubelet's
+    parameters, with track and without seq_nms): ONE ops.tubelet call over all tracked clips follows; the rows after the pass
+    and their track ids are returned as a fifth and a sixth element."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     boxes = dict()
     if max_do < 0:
@@ -216,6 +239,7 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
     from viddet_amd import ops
     boxes_seq = dict()
     tracks, tracks_seq = dict(), dict()
+    boxes_tub, tracks_tub = dict(), dict()
     if kept:
         sidxs = [i for k in kept for i in k[3]]
         order = sorted(range(len(sidxs)), key=lambda n: sidxs[n])          # clip order: sample = video * frames + frame
@@ -231,7 +255,12 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
         C = 1 if net.agnostic else net.num_class
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         if track is not None:
-            _collect_tracks(tracks, dataset, ids, ops.track(ids, scores, bboxes, clip_start=cs, num_class=C, **track)[0], sidxs)
+            linked = ops.track(ids, scores, bboxes, clip_start=cs, num_class=C, **track)[0]
+            _collect_tracks(tracks, dataset, ids, linked, sidxs)
+            if tubelet is not None:
+                out = ops.tubelet(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **tubelet)
+                _collect(boxes_tub, dataset, out[0], out[1], out[2], sidxs, W)
+                _collect_tracks(tracks_tub, dataset, out[0], out[4], sidxs)
         if seq_nms is not None:
             out = ops.seq_nms(ids, scores, bboxes, clip_start=cs, num_class=C, **seq_nms)
             _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
@@ -240,6 +269,8 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
                                 sidxs)
     if track is None:
         return boxes, boxes_seq
+    if tubelet is not None:
+        return boxes, None, tracks, None, boxes_tub, tracks_tub
     return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
 
@@ -265,18 +296,21 @@ def live_clip(net, frames, step, chunk, push, track=None):
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None, live=None):
+                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
     ones detect_video keeps in net.last_plain.  track (a dict): handed to detect_video too, which links the rows it returns;
     the plain rows ahead of Seq-NMS are linked by a call of their own; returns (boxes, rescored or None, tracks, tracks of the
-    rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead."""
+    rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead.  tubelet (a dict,
+    with track, without seq_nms and live): handed to detect_video as well; the plain rows are the ones it keeps in
+    net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
     boxes, boxes_seq = dict(), dict()
     tracks, tracks_seq = dict(), dict()
+    boxes_tub, tracks_tub = dict(), dict()
     if max_do < 0:
         max_do = len(dataset)
     c = 0
@@ -289,6 +323,12 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, trk_kw.get("track"))
             if track is not None:
                 _collect_tracks(tracks, dataset, ids, last[0], sidxs)
+        elif tubelet is not None:
+            out = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, tubelet=tubelet, **trk_kw)
+            _collect(boxes_tub, dataset, out[0], out[1], out[2], sidxs, W)
+            _collect_tracks(tracks_tub, dataset, out[0], net.last_tubelet[1], sidxs)
+            ids, scores, bboxes = net.last_pre_tubelet                     # the plain rows, clipped as _collect clips them
+            _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
         elif seq_nms is None:
             ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, **trk_kw)
             if track is not None:
@@ -307,22 +347,26 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         c += x.shape[0]
         if c > max_do:
             break
+    if tubelet is not None:
+        return boxes, None, tracks, None, boxes_tub, tracks_tub
     if track is not None:
         return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
     return boxes if seq_nms is None else (boxes, boxes_seq)
 
 
-def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False):
+def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False, tub=False):
     """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag;
     seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq; trk: the twin of either whose lines end in the
-    track id of --track, `_trk` last"""
-    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + ("_trk" if trk else ""))
+    track id of --track, `_trk` last; tub: the rows after the pass of --tubelet, under pred_tub / pred_ag_tub"""
+    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + ("_tub" if tub else "")
+                        + ("_trk" if trk else ""))
 
 
-def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=False):
+def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=False, tub=False):
     """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798; `_met` marks a class-agnostic metric over a
-    per-class model, which only the vid metric has); seq: the metric of the predictions rescored by --seq_nms, `_seq` last"""
-    tail = "_seq" if seq else ""
+    per-class model, which only the vid metric has); seq: the metric of the predictions rescored by --seq_nms, `_seq` last; tub:
+    the metric of the rows after the pass of --tubelet, `_tub` last"""
+    tail = ("_seq" if seq else "") + ("_tub" if tub else "")
     if model_agnostic:
         return metric_name + "_ag" + tail
     return (metric_name + "_ag_met" if metric_agnostic else metric_name) + tail
@@ -372,6 +416,26 @@ def check_flags(FLAGS):
             msg = str(e)
             for k, flag in names.items():
                 msg = msg.replace("--track: " + k, flag)
+            raise NotImplementedError(msg)
+    if getattr(FLAGS, "tubelet", False):
+        # the tubelet pass runs over the tracks of a finished clip
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--tubelet needs --track: the pass runs over the tracks of a clip")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--tubelet does not combine with --live: a hole is known only once its track resumes, after "
+                                      "the frame has been given out - the pass has no online form")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--tubelet does not combine with --seq_nms: net.detect_video composes the two, the script "
+                                      "would need a fourth family of prediction sets")
+        if getattr(FLAGS, "tubelet_rescore", "avg") not in ("avg", "max", "none"):
+            raise NotImplementedError("--tubelet_rescore must be avg, max or none, got %r" % (FLAGS.tubelet_rescore,))
+        from viddet_amd.tubelet import check_params as check_tubelet
+        try:
+            check_tubelet(who="--tubelet", **tubelet_args(FLAGS))
+        except ValueError as e:
+            msg = str(e)
+            for k, flag in (("max_gap", "--tubelet_max_gap"), ("drop_untracked", "--tubelet_drop_untracked"), ("rescore", "--tubelet_rescore")):
+                msg = msg.replace("--tubelet: " + k, flag)
             raise NotImplementedError(msg)
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
@@ -573,14 +637,19 @@ def main(argv=None):
         if not FLAGS.stream and world > 1:
             raise NotImplementedError("--track without --stream runs on one GPU: the windowed path shards the frames of a clip "
                                       "over the ranks")
+    tub = tubelet_args(FLAGS)
+    if tub is not None:
+        seq_kw = dict(seq_kw, tubelet=tub)
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
                               live=FLAGS.live_push if FLAGS.live else None, **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
-    boxes_seq = tracks = tracks_seq = None
-    if trk is not None:
+    boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None
+    if tub is not None:
+        boxes, boxes_seq, tracks, tracks_seq, boxes_tub, tracks_tub = boxes
+    elif trk is not None:
         boxes, boxes_seq, tracks, tracks_seq = boxes
     elif seq is not None:
         boxes, boxes_seq = boxes
@@ -599,14 +668,14 @@ def main(argv=None):
             boxes_seq = merged
         if trk is not None:
             gathered = []
-            for part_of in (tracks, tracks_seq):
+            for part_of in (tracks, tracks_seq, boxes_tub, tracks_tub):
                 merged = None
                 if part_of is not None:
                     merged = dict()
                     for part in vdist.all_gather_objects(part_of):
                         merged.update(part)
                 gathered.append(merged)
-            tracks, tracks_seq = gathered
+            tracks, tracks_seq, boxes_tub, tracks_tub = gathered
         if rank != 0:
             return None
     result = save_and_evaluate(FLAGS, dataset, boxes, save_dir)
@@ -619,13 +688,18 @@ def main(argv=None):
         for bx, tr, is_seq in ((boxes, tracks, False), (boxes_seq, tracks_seq, True)):
             if bx is not None:
                 save_tracks(FLAGS, dataset, bx, tr, is_seq)
+    if boxes_tub is not None:
+        # the rows after the tubelet pass, last: pred_tub, vid_tub.txt, coco_tub.txt, ..., pred_tub_trk, tracks_tub.txt
+        save_and_evaluate(FLAGS, dataset, boxes_tub, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, tub=True),
+                          tub=True)
+        save_tracks(FLAGS, dataset, boxes_tub, tracks_tub, tub=True)
     return result
 
 
-def save_tracks(FLAGS, dataset, boxes, tracks, seq=False):
+def save_tracks(FLAGS, dataset, boxes, tracks, seq=False, tub=False):
     """--track: the twin of a prediction set - its files' lines with `,track` appended (every row, -1 too) - and one line
-    `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt"""
-    save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=seq, trk=True)
+    `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt (tub: pred_tub_trk, tracks_tub.txt)"""
+    save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=seq, trk=True, tub=tub)
     os.makedirs(save_dir, exist_ok=True)
     n = len(dataset) if FLAGS.max_do < 0 else min(FLAGS.max_do, len(dataset))
     per_clip = [[set(), 0] for _ in range(dataset.num_videos)]
@@ -640,15 +714,15 @@ def save_tracks(FLAGS, dataset, boxes, tracks, seq=False):
                 if tid >= 0:
                     per_clip[idx // dataset.frames_per_video][0].add(tid)
                     per_clip[idx // dataset.frames_per_video][1] += 1
-    out = os.path.join(FLAGS.save_dir, FLAGS.save_prefix, result_name("tracks", FLAGS.model_agnostic, seq=seq) + ".txt")
+    out = os.path.join(FLAGS.save_dir, FLAGS.save_prefix, result_name("tracks", FLAGS.model_agnostic, seq=seq, tub=tub) + ".txt")
     with open(out, "w") as f:
         for v, (ids, rows) in enumerate(per_clip):
             f.write("{} {} {} {:.4f}\n".format(v, len(ids), rows, rows / len(ids) if ids else 0.0))
 
 
-def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):
+def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False, tub=False):
     """The tail of main(): the prediction files under save_dir, then --metrics on what was saved; seq names the result files
-    of the predictions rescored by --seq_nms."""
+    of the predictions rescored by --seq_nms, tub those of the rows after the pass of --tubelet."""
     save_predictions(save_dir, dataset, boxes, max_do=FLAGS.max_do)
     metrics = [m.lower() for m in FLAGS.metrics]
     out_dir = os.path.join(FLAGS.save_dir, FLAGS.save_prefix)
@@ -661,7 +735,7 @@ def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):
             vid_class = VIDDetectionMetric
         vid_result = evaluate_by_sample_id(vid_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset, preds)
         # vid.txt / vid_ag.txt / vid_ag_met.txt
-        write_results(os.path.join(out_dir, result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq) + ".txt"),
+        write_results(os.path.join(out_dir, result_name("vid", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"),
                       *vid_result)
     if len(FLAGS.dataset) > 1 and {"voc", "coco"} & set(metrics):              # detect_yolo3.py:898-899 (class-tree sets), ahead of
         preds = hierarchical_nms(preds, dataset, level_thresh=FLAGS.hier_level)  # the metrics (vid is refused on such a set)
@@ -672,7 +746,7 @@ def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):
         if FLAGS.model_agnostic:
             # the per-class and the mean AP in <metric>_ag.txt beside pred_ag.  The metric is handed the rows as they are (ids
             # all 0): the reference's voc / coco metrics take no agnostic argument
-            write_results(os.path.join(out_dir, result_name("voc", True, seq=seq) + ".txt"), names, values, echo=False)
+            write_results(os.path.join(out_dir, result_name("voc", True, seq=seq, tub=tub) + ".txt"), names, values, echo=False)
         voc_result = names, values
     if "coco" in metrics:
         if FLAGS.device_metric:
@@ -680,9 +754,9 @@ def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False):
         else:
             coco_class = COCODetectionMetric
         # get_metric :186: the detections' JSON beside pred/, removed again (cleanup); no time stamp in its name
-        metric = coco_class(dataset, os.path.join(out_dir, "coco_results_seq" if seq else "coco_results"), use_time=False, cleanup=True, data_shape=None)
+        metric = coco_class(dataset, os.path.join(out_dir, "coco_results" + ("_seq" if seq else "") + ("_tub" if tub else "")), use_time=False, cleanup=True, data_shape=None)
         coco_result = evaluate_by_sample_id(metric, dataset, preds)
-        write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq) + ".txt"),
+        write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"),
                       *coco_result)
     # what main() hands back is what it handed back before coco was built: voc's where asked for, else vid's; coco's alone
     if voc_result is not None:

@@ -787,6 +787,42 @@ int vd_track_push(const float* ids, const float* scores, const float* bboxes, in
                   float sigma_iou, int max_age, void* state, int64_t state_bytes, int32_t* out_track, int32_t* out_len,
                   float* out_score, void* stream);
 
+/* ---- Tubelet rescoring and gap filling over the tracks of video clips (vd_tubelet.hip): what
+ * viddet_amd.tubelet.tubelet_host computes, bit for bit, on all six outputs.  ids, scores, bboxes, clip_start, V, F, N,
+ * num_class: as vd_seq_nms takes them; track [F][N] int32: vd_track's out_track (any table is safe).  Per clip [t0, t1):
+ *   1. a row is present iff it is a candidate of vd_seq_nms (id >= 0, a finite score, a class below num_class); a present row is
+ *      a member of track u = track[t][i] iff 0 <= u < (t1 - t0) * N and no lower row of its frame is a member of u already; a
+ *      track's members are ordered by frame.
+ *   2. rescore 1 (avg): s_u = the fp32 sum of the members' scores in frame order, from 0, one rounding per add, divided by
+ *      (float)len, correctly rounded; 2 (max): the first member's score, replaced by a later one's where that is greater; every
+ *      member's new score is s_u; 0: the scores stay.  A row that is no member keeps its score.
+ *   3. consecutive members at frames f0 < f1, g = f1 - f0, 1 < g <= max_gap + 1, give every frame f0 + j, 0 < j < g, a candidate
+ *      fill row: the id of the member at f0, track u, w = (float)j / (float)g, every coordinate a + (b - a) * w (a at f0, b at
+ *      f1; every operation rounded, no FMA), score s_u, with rescore 0 the same formula on the two scores.
+ *   4. per frame: the kept rows - the present rows in row order, with drop_untracked only the members - then the fills in
+ *      ascending track id while kept + admitted < N (dropped[t] counts the others), sorted by new score descending, stably, by
+ *      float comparison (-0.0 and 0.0 tie; no score is a NaN: the members' scores are finite); rows of -1 follow.
+ * Outputs, written in full: out_ids, out_scores [F][N], out_bboxes [F][N][4]; perm [F][N] int32 (the old row of an output row,
+ * -2 a filled row, -1 an empty one); track_out [F][N] int32 (the output row's track, -1 where it has none or the row is empty);
+ * dropped [F] int32.  A frame that no clip covers comes out empty.  A track id is checked against [0, (t1 - t0) * N) before it
+ * indexes the per-track tables (sum, count, maximum, last member), which live in ws, VD_TUBELET_WS_PER_ROW bytes per (frame,
+ * row), at the clip's first row + the id.  Four launches (one fewer without clip_start): clear, members per (clip, frame), ONE
+ * workgroup per clip accumulating in frame order, assembly per (clip, frame).  1 <= N <= 128, F >= 1, F * N < 2^31, V >= 1,
+ * num_class >= 1, 0 <= max_gap <= 7; bboxes and out_bboxes 16-byte, every other pointer 4-byte aligned.  The inputs are never
+ * written.  No atomics, bit-reproducible.  vd_tubelet_ws_bytes: the bytes ws must hold, -1 for sizes that are not taken. */
+#define VD_TUBELET_WS_PER_ROW 24
+int64_t vd_tubelet_ws_bytes(int F, int N);
+int vd_tubelet(const float* ids, const float* scores, const float* bboxes, const int32_t* track, const int32_t* clip_start, int V,
+               int F, int N, int num_class, int rescore, int max_gap, int drop_untracked, float* out_ids, float* out_scores,
+               float* out_bboxes, int32_t* perm, int32_t* track_out, int32_t* dropped, void* ws, int64_t ws_bytes, void* stream);
+/* the same, for timing the launches one by one (tools/tubelet_probe.py): stages is a mask of 1 (clear), 2 (members), 4 (chain),
+ * 8 (frames); vd_tubelet is stages 15.  With fewer the outputs may stay unwritten; an id read back from the workspace is checked
+ * against the clip's range again, so a launch that meets a workspace no earlier launch filled stays inside it. */
+int vd_tubelet_stages(const float* ids, const float* scores, const float* bboxes, const int32_t* track, const int32_t* clip_start,
+                      int V, int F, int N, int num_class, int rescore, int max_gap, int drop_untracked, float* out_ids,
+                      float* out_scores, float* out_bboxes, int32_t* perm, int32_t* track_out, int32_t* dropped, void* ws,
+                      int64_t ws_bytes, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

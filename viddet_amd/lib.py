@@ -19,6 +19,8 @@ SEQ_NMS_WS_PER_ROW = 48                             # vd_seq_nms: workspace byte
 TRACK_MAX_ROWS, TRACK_MAX_ACTIVE = 128, 1024        # vd_track: rows per frame, active tracks = rows * (max_age + 1) (vd_track.hip)
 TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes per (frame, row) (VD_TRACK_WS_PER_ROW)
 TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of one stream's state (VD_TRACK_STATE_BYTES)
+TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
+TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -201,6 +203,10 @@ SIGNATURES = {
     "vd_track": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _i64, _p]),
     # the same tracker resumable: the active tracks carried from launch to launch in a state block (vd_track_live.hip)
     "vd_track_push": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _i64, _p, _p, _p, _p]),
+    # tubelet rescoring and gap filling over the tracks of video clips (vd_tubelet.hip)
+    "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
+    "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "vd_tubelet_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
 }
 
 _lib = None

@@ -2193,7 +2193,7 @@ class YOLOV3(object):
         if n < dst.shape[0]:
             dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
 
-    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None):
+    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None):
         """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
         (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
         (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
@@ -2214,7 +2214,15 @@ class YOLOV3(object):
         track: None (the default), True, or a dict of sigma_l / sigma_h / sigma_iou / t_min / max_age (and `clip`, as above) -
         the rows the call returns are linked into tracks on the device (ops.track; with seq_nms: the rescored,
         re-sorted rows).  The returned tensors are what the call returns without it; last_tracks = (track, tlen, tscore),
-        each (T,post_nms), holds the result and is None after a call without `track`."""
+        each (T,post_nms), holds the result and is None after a call without `track`.
+
+        tubelet: None (the default), True, or a dict of rescore / max_gap / drop_untracked; needs `track` - the rows the tracker
+        saw (those of Seq-NMS where that is on, clipped where track's `clip` is given) go through the tubelet pass on the device
+        (ops.tubelet): the rows of a track take its score, the frames it skipped get an interpolated box, every
+        frame is re-sorted, and those three tensors are returned.  last_pre_tubelet holds the three tensors ahead of the pass,
+        last_tracks stays ops.track's result on them, last_tubelet = (perm, track_out, dropped), last_rows follows perm (-1 on
+        filled and empty rows).  A call without it sets last_tubelet to None.  open_video takes no such argument: a hole is
+        known only once its track resumes, after the frame has been given out."""
         why = self._stream_refusal()
         if why is not None:
             raise NotImplementedError("detect_video with " + why)
@@ -2243,7 +2251,18 @@ class YOLOV3(object):
             if self.post_nms > L.TRACK_MAX_ROWS:
                 raise ValueError("detect_video with track: post_nms=%d rows per frame, the tracker takes at most %d"
                                  % (self.post_nms, L.TRACK_MAX_ROWS))
+        tub_kw = None
+        if tubelet is not None and tubelet is not False:
+            from .tubelet import DEFAULTS as TUB_DEFAULTS, check_params as check_tubelet
+            tub_kw = {} if tubelet is True else dict(tubelet)
+            unknown = sorted(set(tub_kw) - set(TUB_DEFAULTS))
+            if unknown:
+                raise ValueError("detect_video: tubelet takes rescore, max_gap and drop_untracked, got %s" % ", ".join(unknown))
+            check_tubelet(who="detect_video with tubelet", **tub_kw)
+            if trk_kw is None:
+                raise ValueError("detect_video: tubelet needs track: the pass runs over the tracks of the clip")
         self.last_tracks = None
+        self.last_tubelet = self.last_pre_tubelet = None
         if self._k > 1:
             self._stream_split()                                  # the graph's own word, before anything touches the GPU
         from .stream import stream_window_slots, ring_size, chunk_slots
@@ -2335,13 +2354,23 @@ class YOLOV3(object):
         if trk_kw is not None:
             boxes = res[2] if trk_clip is None else res[2].clamp(0, float(trk_clip))
             self.last_tracks = ops.track(res[0], res[1], boxes, num_class=1 if self.agnostic else self.num_class, **trk_kw)
+            if tub_kw is not None:
+                self.last_pre_tubelet = res[0], res[1], boxes             # the rows the tracker saw
+                out_t = ops.tubelet(res[0], res[1], boxes, self.last_tracks[0], num_class=1 if self.agnostic else self.num_class,
+                                    **tub_kw)
+                perm = out_t[3]
+                rows = torch.gather(self.last_rows, 1, perm.clamp(min=0).long())
+                self.last_rows = torch.where(perm >= 0, rows, torch.full_like(rows, -1))
+                self.last_tubelet = out_t[3], out_t[4], out_t[5]
+                res = out_t[0], out_t[1], out_t[2]
         return res
 
     def open_video(self, step=1, chunk=8, track=None):
         """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and
         whose length nobody knows - session.push(frames) returns the detections that are final by now, session.flush() ends
         the clip.  Refused where detect_video is, in the same words, and while another session of this net has
-        frames in flight.  Seq-NMS has no online form and is no option here."""
+        frames in flight.  Seq-NMS has no online form and is no option here; nor is the tubelet pass: a hole is
+        known only once its track resumes, after the frame has been given out."""
         if self._live is not None:
             raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))
         from .live import VideoSession

@@ -659,6 +659,65 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
     return out_track, out_len, out_score
 
 
+def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="avg", max_gap=7, drop_untracked=False, ws=None,
+            stages=None):
+    """vd_tubelet (viddet_amd/tubelet.py::tubelet_host on the device, bit for bit, DESIGN.md 32): ids (F,N[,1]), scores (F,N[,1])
+    and bboxes (F,N,4) are contiguous fp32 device tensors, N <= 128; track (F,N) a contiguous int32 device tensor, ops.track's
+    first result; clip_start as ops.seq_nms takes it.  Returns (ids, scores, bboxes, perm, track_out, dropped), new device
+    tensors: the first three of the inputs' shapes, perm and track_out (F,N) int32, dropped (F,) int32.  Launches on the current
+    stream; nothing is downloaded and nothing waits.  ws: a uint8 device tensor of >= 24*F*N bytes to reuse, else one is
+    allocated.  stages (a mask of 1, 2, 4, 8; tools/tubelet_probe.py): only those of the four launches are made
+    (vd_tubelet_stages) and the outputs may stay unwritten."""
+    from .tubelet import RESCORE, check_params
+    rescore, max_gap, drop_untracked = check_params(rescore, max_gap, drop_untracked, "tubelet")
+    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("tubelet: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TUBELET_MAX_ROWS:
+        raise ValueError("tubelet: N=%d rows per frame, vd_tubelet takes at most %d" % (N, L.TUBELET_MAX_ROWS))
+    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
+        raise ValueError("tubelet: num_class must be an integer >= 1, got %r" % (num_class,))
+    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
+                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("tubelet: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(track.shape) != (F, N):
+        raise ValueError("tubelet: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("tubelet: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("tubelet: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TUBELET_WS_PER_ROW * F * N
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("tubelet: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    dev = bboxes.device
+    out_ids, out_scores, out_bboxes = torch.empty_like(ids), torch.empty_like(scores), torch.empty_like(bboxes)
+    perm = torch.empty(F, N, dtype=torch.int32, device=dev)
+    track_out = torch.empty(F, N, dtype=torch.int32, device=dev)
+    dropped = torch.empty(F, dtype=torch.int32, device=dev)
+    if F == 0 or N == 0:
+        return out_ids, out_scores, out_bboxes, perm, track_out, dropped
+    args = (ptr(ids), ptr(scores), ptr(bboxes), ptr(track), ptr(clip_start), V, F, N, int(num_class), RESCORE[rescore], max_gap,
+            int(drop_untracked), ptr(out_ids), ptr(out_scores), ptr(out_bboxes), ptr(perm), ptr(track_out), ptr(dropped), ptr(ws),
+            int(ws.numel()))
+    if stages is None:
+        check(_lib().vd_tubelet(*args, _s()), "vd_tubelet")
+    else:
+        check(_lib().vd_tubelet_stages(*args, int(stages), _s()), "vd_tubelet_stages")
+    return out_ids, out_scores, out_bboxes, perm, track_out, dropped
+
+
 class TrackState:
     """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
     device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -

@@ -23,8 +23,11 @@ clip; everything else is written as without the flag.  `--live` (with --stream; 
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
 the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
 pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
-an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.  Visualisation
-and the worst-video tool are out of scope.
+an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.  `--metrics mot`
+(with --track; no reference counterpart) scores every tracked twin with the MOT tracking metric (viddet_amd/mot_metric.py: MOTA,
+MOTP, id switches, fragmentations, IDF1, ... against the track ids of SyntheticTracks) on the rows read back from the
+twin's files, and writes mot.txt / mot_seq.txt / mot_tub.txt; `--device_metric` with the per-frame matching on the device
+(vd_mot_match).  Visualisation and the worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -43,6 +46,7 @@ from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticTrac
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.vid_metric import VIDDetectionMetric
 from viddet_amd.coco_metric import COCODetectionMetric
+from viddet_amd.mot_metric import MOTMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
 from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
 from train_yolov3 import _list, _bool
@@ -112,7 +116,8 @@ def parse_flags(argv=None):
     A("--device_metric", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) --metrics vid and --metrics coco match detections and ground truth on the GPU (vd_vid_match, "
            "vd_coco_match: one workgroup per image; DeviceVIDDetectionMetric, DeviceCOCODetectionMetric): the same vid.txt / "
-           "coco.txt as the host metrics write (DESIGN.md 25, 26)")
+           "coco.txt as the host metrics write (DESIGN.md 25, 26).  --metrics mot likewise (vd_mot_match: one workgroup per clip; "
+           "DeviceMOTMetric): the same mot.txt (DESIGN.md 33)")
     A("--seq_nms", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) sequence NMS (Han et al. 2016) over the detections of every clip, on the device "
            "(vd_seq_nms): boxes of adjacent frames are linked, the best sequence's rows take its score, what overlaps them is "
@@ -375,6 +380,16 @@ def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=Fa
 def check_flags(FLAGS):
     """What the parsed flags ask for that is not built is refused here, before anything touches the GPU; returns the checked
     conv_types (None: the plain 2-D backbone)."""
+    mot = "mot" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
+    if mot:
+        # the MOT metric scores tracks against the ground-truth tracks of a clip
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--metrics mot needs --track: it scores the tracks of the tracked prediction sets (pred_trk, ...)")
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--metrics mot does not combine with several --dataset names: the combined set has no "
+                                      "clips and no ground-truth tracks")
+        if getattr(FLAGS, "mult_out", False):
+            raise NotImplementedError("--metrics mot does not combine with --mult_out: its rows are not the detections of one frame")
     if getattr(FLAGS, "seq_nms", False):
         # Seq-NMS links the frames of a clip: a set without clips has nothing to link
         if len(FLAGS.dataset) > 1:
@@ -448,15 +463,16 @@ def check_flags(FLAGS):
     coco = "coco" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
     if FLAGS.model_agnostic:
         FLAGS.metric_agnostic = True                      # detect_yolo3.py:797-798
-    elif FLAGS.metric_agnostic and not vid:
-        raise NotImplementedError("--metric_agnostic without --model_agnostic only acts inside VIDDetectionMetric "
-                                  "(detect_yolo3.py:189-190): it needs --metrics vid, the voc metric takes no agnostic argument")
+    elif FLAGS.metric_agnostic and not (vid or mot):
+        raise NotImplementedError("--metric_agnostic without --model_agnostic only acts inside VIDDetectionMetric and MOTMetric "
+                                  "(detect_yolo3.py:189-190): it needs --metrics vid or --metrics mot, the voc metric takes no "
+                                  "agnostic argument")
     if vid and len(FLAGS.dataset) > 1:
         raise NotImplementedError("--metrics vid does not combine with several --dataset names: the combined set has no "
                                   "tracks, so no motion IoUs")
-    if getattr(FLAGS, "device_metric", False) and not (vid or coco):
-        raise NotImplementedError("--device_metric acts on --metrics vid and --metrics coco only (train_yolov3.py has the voc "
-                                  "metric's)")
+    if getattr(FLAGS, "device_metric", False) and not (vid or coco or mot):
+        raise NotImplementedError("--device_metric acts on --metrics vid, --metrics coco and --metrics mot only (train_yolov3.py "
+                                  "has the voc metric's)")
     # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
     ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
     if ct is not None:
@@ -590,8 +606,8 @@ def main(argv=None):
     fmt = dict(frame_format="nv12", yuv_matrix=FLAGS.yuv_matrix, yuv_range=FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else {}
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
-    elif "vid" in [m.lower() for m in FLAGS.metrics]:
-        # the vid metric needs tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
+    elif {"vid", "mot"} & {m.lower() for m in FLAGS.metrics}:
+        # the vid and mot metrics need tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
         dataset = SyntheticTracks(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
                                   frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
                                   step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1, **fmt)
@@ -685,9 +701,12 @@ def main(argv=None):
                           seq=True)
     if trk is not None:
         # the tracked twins, after everything a run without --track writes: pred_trk / tracks.txt, pred_seq_trk / tracks_seq.txt
+        # (and with --metrics mot their mot.txt / mot_seq.txt; the plain twin's is what main() returns where no other metric ran)
         for bx, tr, is_seq in ((boxes, tracks, False), (boxes_seq, tracks_seq, True)):
             if bx is not None:
-                save_tracks(FLAGS, dataset, bx, tr, is_seq)
+                mot_result = save_tracks(FLAGS, dataset, bx, tr, is_seq)
+                if result is None and not is_seq:
+                    result = mot_result
     if boxes_tub is not None:
         # the rows after the tubelet pass, last: pred_tub, vid_tub.txt, coco_tub.txt, ..., pred_tub_trk, tracks_tub.txt
         save_and_evaluate(FLAGS, dataset, boxes_tub, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, tub=True),
@@ -718,6 +737,49 @@ def save_tracks(FLAGS, dataset, boxes, tracks, seq=False, tub=False):
     with open(out, "w") as f:
         for v, (ids, rows) in enumerate(per_clip):
             f.write("{} {} {} {:.4f}\n".format(v, len(ids), rows, rows / len(ids) if ids else 0.0))
+    if "mot" not in [m.lower() for m in FLAGS.metrics]:
+        return None
+    # --metrics mot: what is scored is what is on disk - the rows read back from the twin's files
+    if FLAGS.device_metric:
+        from viddet_amd.device_mot_metric import DeviceMOTMetric as mot_class
+    else:
+        mot_class = MOTMetric
+    result = evaluate_tracks(mot_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset,
+                             load_tracked_predictions(save_dir, dataset, FLAGS.max_do))
+    # mot.txt / mot_seq.txt / mot_tub.txt, mot_ag*.txt under --model_agnostic, mot_ag_met*.txt under --metric_agnostic alone
+    write_results(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
+                               result_name("mot", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"), *result)
+    return result
+
+
+def load_tracked_predictions(save_dir, dataset, max_do=-1):
+    """load_predictions for a tracked twin: {image path: [[id, score, x1, y1, x2, y2, track]]}"""
+    boxes = dict()
+    n = len(dataset) if max_do < 0 else min(max_do, len(dataset))
+    for idx in range(n):
+        img_path = dataset.sample_path(idx)
+        p = os.path.join(save_dir, os.path.split(img_path)[1].split(".")[0] + ".txt")
+        if not os.path.exists(p):
+            continue
+        with open(p) as f:
+            for line in f:
+                v = line.rstrip().split(",")
+                boxes.setdefault(v[0], []).append([int(v[1])] + [float(t) for t in v[2:7]] + [int(v[7])])
+    return boxes
+
+
+def evaluate_tracks(metric, dataset, predictions):
+    """evaluate_by_sample_id for the MOT metric: the saved rows of a tracked twin, un-normalised to the source frame in the same
+    way, with their track ids; an image without a saved row is not fed - the metric takes it as a frame without predictions"""
+    for idx, sid in enumerate(dataset.sample_ids):
+        img_path = dataset.sample_path(idx)
+        if img_path in predictions:
+            w, h = dataset.image_size(sid)
+            pred = predictions[img_path]
+            det_bboxes = [[[[b[2] * w, b[3] * h, b[4] * w, b[5] * h] for b in pred]]]          # [1][image][row][4]
+            metric.update(det_bboxes, [[[b[0] for b in pred]]], [[[b[1] for b in pred]]], None, None, None, sid=sid,
+                          tracks=[[[b[6] for b in pred]]])
+    return metric.get()
 
 
 def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False, tub=False):

@@ -823,6 +823,36 @@ int vd_tubelet_stages(const float* ids, const float* scores, const float* bboxes
                       float* out_scores, float* out_bboxes, int32_t* perm, int32_t* track_out, int32_t* dropped, void* ws,
                       int64_t ws_bytes, int stages, void* stream);
 
+/* ---- The per-frame matching of the MOT tracking metric (vd_mot_eval.hip): what
+ * viddet_amd.mot_metric.mot_match_host computes, bit for bit, on all four outputs.  gt_boxes [F][G][4] fp32, gt_cls, gt_id
+ * [F][G] int32: the label rows (corner boxes, class, ground-truth track id); ids, scores, bboxes, clip_start, V, F, N, num_class: as
+ * vd_seq_nms takes them; track [F][N] int32: vd_track's out_track / vd_tubelet's track_out (any table is safe).  Per clip
+ * [t0, t1), frames in order, last[a] (0 <= a < 1024) = the prediction id ground-truth id a was matched to last, none at t0:
+ *   1. a prediction row is eligible iff it is a candidate of vd_seq_nms and track >= 0, a ground-truth row iff gt_cls >= 0 and
+ *      0 <= gt_id < 1024; an eligible row is a candidate iff no lower eligible row of its frame carries its id;
+ *   2. (g, j) is admissible iff both are candidates, iou >= iou_thresh (vd_seq_nms's fp32 IoU) and (agnostic or the classes are
+ *      equal): bit j % 32 of adm[t][g][j / 32];
+ *   3. carry-over, ground-truth candidates in row order: where last[gt_id] = p, the candidate row j carrying p is free and (g, j)
+ *      is admissible, g is matched to j;
+ *   4. the rest: the minimum-cost assignment over admissible pairs at cost 2^20 - int(iou * 2^20), a dummy column per row at
+ *      2^27 - successive shortest augmenting paths with int64 potentials, rows in row order, among columns of equal least slack
+ *      the lowest (prediction rows in row order, then the dummies); entered only when both pools hold a row;
+ *   5. match [F][G] int32: the prediction row, -1 an unmatched candidate, -2 no candidate; miou [F][G]: the pair's IoU, else 0;
+ *      flags [F][G] int32: bit 0 an id switch (last[a] set and different from the matched id), bit 1 a carry-over match; then
+ *      last[a] = the matched id.
+ * All four outputs are written in full; the rows of a frame that no clip covers get -2 / 0 / 0 / 0.  ws carries the candidate
+ * tables between the launches, VD_MOT_WS_PER_ROW bytes per (frame, row) of either side.  Three launches (one fewer without
+ * clip_start): clear, pairs per (clip, frame), ONE workgroup per clip for steps 3 to 5.  1 <= G, N <= 128, F >= 1, V >= 1,
+ * num_class >= 1, 0 < iou_thresh <= 1, agnostic 0 or 1; gt_boxes, bboxes and adm 16-byte, every other pointer 4-byte aligned.
+ * The inputs are never written.  No atomics, bit-reproducible.  vd_mot_match_ws_bytes: the bytes ws must hold, -1 for sizes
+ * that are not taken. */
+#define VD_MOT_WS_PER_ROW 4
+int64_t vd_mot_match_ws_bytes(int F, int G, int N);
+int vd_mot_match(const float* gt_boxes, const int32_t* gt_cls, const int32_t* gt_id, const float* ids, const float* scores,
+                 const float* bboxes, const int32_t* track, const int32_t* clip_start, int V, int F, int G, int N, int num_class,
+                 float iou_thresh, int agnostic, int32_t* match, float* miou, int32_t* flags, uint32_t* adm, void* ws,
+                 int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

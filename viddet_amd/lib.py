@@ -21,6 +21,8 @@ TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes 
 TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of one stream's state (VD_TRACK_STATE_BYTES)
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
+MOT_MAX_ROWS = 128                                  # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
+MOT_WS_PER_ROW = 4                                  # vd_mot_match: workspace bytes per (frame, row) of either side (VD_MOT_WS_PER_ROW)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -207,6 +209,9 @@ SIGNATURES = {
     "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
     "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "vd_tubelet_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
+    # the per-frame matching of the MOT tracking metric on the device (vd_mot_eval.hip)
+    "vd_mot_match_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_mot_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -718,6 +718,70 @@ def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="a
     return out_ids, out_scores, out_bboxes, perm, track_out, dropped
 
 
+def mot_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, clip_start=None, num_class=1, iou_thresh=0.5, agnostic=False,
+              ws=None):
+    """vd_mot_match (viddet_amd/mot_metric.py::mot_match_host on the device, bit for bit, DESIGN.md 33): gt_boxes (F,G,4) fp32,
+    gt_cls and gt_id (F,G) int32 - the label rows -, ids (F,N[,1]), scores (F,N[,1]) and bboxes (F,N,4) fp32, track (F,N) int32
+    (ops.track's first result, ops.tubelet's fifth), all contiguous device tensors, G and N <= 128; clip_start as ops.seq_nms
+    takes it.  Returns (match (F,G) int32, miou (F,G) fp32, flags (F,G) int32, adm (F,G,4) int32 - the bits of the definition's
+    uint32 words), new device tensors.  Launches on the current stream; nothing is downloaded and nothing waits.  ws: a uint8
+    device tensor of >= 4*F*(G+N) bytes to reuse, else one is allocated."""
+    from .mot_metric import check_iou_thresh
+    thr = check_iou_thresh(iou_thresh, "mot_match")
+    if type(agnostic).__name__ not in ("bool", "bool_"):
+        raise ValueError("mot_match: agnostic must be a bool, got %r" % (agnostic,))
+    for name, t in (("gt_boxes", gt_boxes), ("bboxes", bboxes)):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[-1] != 4:
+            raise ValueError("mot_match: %s must be (F,%s,4), got %r" % (name, "G" if name == "gt_boxes" else "N", tuple(getattr(t, "shape", ()))))
+    F, G, N = int(gt_boxes.shape[0]), int(gt_boxes.shape[1]), int(bboxes.shape[1])
+    if int(bboxes.shape[0]) != F:
+        raise ValueError("mot_match: gt_boxes holds %d frames, bboxes %d" % (F, int(bboxes.shape[0])))
+    if not 1 <= G <= L.MOT_MAX_ROWS:
+        raise ValueError("mot_match: gt_boxes holds G=%d label rows per frame, vd_mot_match takes 1 to %d" % (G, L.MOT_MAX_ROWS))
+    if not 1 <= N <= L.MOT_MAX_ROWS:
+        raise ValueError("mot_match: bboxes holds N=%d prediction rows per frame, vd_mot_match takes 1 to %d" % (N, L.MOT_MAX_ROWS))
+    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
+        raise ValueError("mot_match: num_class must be an integer >= 1, got %r" % (num_class,))
+    f32, i32 = torch.float32, torch.int32
+    for name, t, n, dt in (("gt_boxes", gt_boxes, F * G * 4, f32), ("gt_cls", gt_cls, F * G, i32), ("gt_id", gt_id, F * G, i32),
+                           ("ids", ids, F * N, f32), ("scores", scores, F * N, f32), ("bboxes", bboxes, F * N * 4, f32),
+                           ("track", track, F * N, i32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("mot_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    for name, t, shape in (("gt_cls", gt_cls, (F, G)), ("gt_id", gt_id, (F, G)), ("track", track, (F, N))):
+        if tuple(t.shape) != shape:
+            raise ValueError("mot_match: %s must be %r, got %r" % (name, shape, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("mot_match: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("mot_match: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.MOT_WS_PER_ROW * F * (G + N)
+    if ws is None:
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=bboxes.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("mot_match: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    dev = bboxes.device
+    match = torch.empty(F, G, dtype=i32, device=dev)
+    miou = torch.empty(F, G, dtype=f32, device=dev)
+    flags = torch.empty(F, G, dtype=i32, device=dev)
+    adm = torch.empty(F, G, 4, dtype=i32, device=dev)
+    if F == 0:
+        return match, miou, flags, adm
+    check(_lib().vd_mot_match(ptr(gt_boxes), ptr(gt_cls), ptr(gt_id), ptr(ids), ptr(scores), ptr(bboxes), ptr(track), ptr(clip_start),
+                              V, F, G, N, int(num_class), float(thr), int(bool(agnostic)), ptr(match), ptr(miou), ptr(flags), ptr(adm),
+                              ptr(ws), int(ws.numel()), _s()), "vd_mot_match")
+    return match, miou, flags, adm
+
+
 class TrackState:
     """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
     device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -

@@ -1,7 +1,7 @@
 """CPU: the host half of live video sessions, none of which touches a GPU.
 
 Planner: stream.StreamPlanner, fed a clip in any partition and then flushed, returns the launch groups of detect_video on the
-whole clip - the two loops of YOLOV3.detect_video (viddet_amd/model.py) are written out below as `detect_video_actions` - and
+whole clip - the two loops detect_video ran before it was put on the planner are written out below as `detect_video_actions` - and
 the slot table of every suffix chunk is chunk_slots of stream_window_slots(T, ...).
 Tracker: track.track_online_host over any partition equals one call on all frames; its ids are track_host's with nothing
 dropped; finalize_tracks of it is track_host at the real sigma_h and t_min, on all three arrays.
@@ -16,8 +16,8 @@ from viddet_amd.track import finalize_tracks, track_host, track_online_host
 
 # ------------------------------------------------------------------------------------------------ planner
 def detect_video_actions(T, K, step, chunk):
-    """The launches of detect_video(frames (T,...), step, chunk) in order, from model.py: ('prefix', a, b) for
-    _stage_frames(.., done, done + m) + pre.run(), ('suffix', t0, n) for suf.run() (K = 1: _forward_infer on the chunk) - and
+    """The launches of detect_video(frames (T,...), step, chunk) in order - the loops detect_video ran before it was put on the
+    planner: ('prefix', a, b) for _stage_frames(.., done, done + m) + pre.run(), ('suffix', t0, n) for suf.run() (K = 1: _forward_infer on the chunk) - and
     with each suffix the frames [first, last) its chunk_slots call is checked against."""
     acts, rings = [], []
     if K == 1:

@@ -276,6 +276,20 @@ def test_session_on_a_uint8_clip_from_the_host_with_set_nms():
     session.flush()
 
 
+@pytest.mark.parametrize("k1", [False, True], ids=["k3-max-early", "k1"])
+def test_detect_video_on_a_float_clip_in_host_memory(k1):
+    """the engine slices every group out of the clip where it lives: a float clip on the host gives the device clip's bits"""
+    net = _mk_k1() if k1 else _mk("max", "early")
+    frames = torch.from_numpy(SO.clip_frames())
+    assert frames.dtype == torch.float32 and not frames.is_cuda
+    want = [t.clone() for t in net.detect_video(frames.cuda(), chunk=CHUNK)] + [net.last_rows.clone(), net.last_overflow.clone()]
+    got = list(net.detect_video(frames.cpu(), chunk=CHUNK)) + [net.last_rows, net.last_overflow]
+    torch.cuda.synchronize()
+    assert bool((want[0] >= 0).any()), "fixture produced no detections"
+    for name, g, w in zip(("ids", "scores", "bboxes", "rows", "overflow"), got, want):
+        assert g.is_cuda and g.dtype == w.dtype and torch.equal(g, w), name
+
+
 def test_session_with_track():
     net = _mk("max", "early")
     frames = torch.from_numpy(SO.clip_frames()).cuda()

@@ -87,7 +87,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("tools/stream_bench.py needs an MI355X: a timing taken elsewhere says nothing")
     from viddet_amd.model import yolo3_darknet53
-    from viddet_amd.stream import stream_window_slots
+    from viddet_amd.stream import ring_size, stream_window_slots
     T, K, chunk = a.frames, a.window, a.chunk
     g = torch.Generator(device="cuda").manual_seed(3)
     frames = torch.randn(T, 3, a.size, a.size, device="cuda", generator=g)
@@ -112,7 +112,7 @@ def main(argv=None):
             for _ in range(a.blocks):                              # alternating blocks in one process
                 ts.append(_sync_time(stream))
                 tw.append(_sync_time(windowed))
-            sp = net._programs[('stream_bf16' if prec == 'bf16' else 'stream', chunk, a.size, a.size, chunk + 2 * (K // 2))]
+            sp = net._programs[('stream_bf16' if prec == 'bf16' else 'stream', chunk, a.size, a.size, ring_size(K, 1, chunk))]
             res = dict(variant="max %s %s" % (jp, prec), frames=T, size=a.size, classes=a.classes, K=K, chunk=chunk,
                        stream_fps=round(T / statistics.median(ts), 1), windowed_fps=round(T / statistics.median(tw), 1),
                        ratio=round(statistics.median(tw) / statistics.median(ts), 3),

@@ -29,9 +29,10 @@
 
 #pragma clang fp contract(off)
 
+#include "vd_track_math.h"
+
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kMaxRows = 128;                         // G and N
 constexpr int kThreads = 256;                         // both kernels: 4 wavefronts; the assignment's columns: G + N at most
 constexpr int kWaves = kThreads / kWave;
@@ -40,19 +41,6 @@ constexpr int kMaxY = 128;                            // workgroups of a clip in
 constexpr long long kInf = 1ll << 62;                 // a forbidden cell, a column that no path reaches
 constexpr long long kDummy = 1ll << 27;
 constexpr int kQOne = 1 << 20;
-
-// np.minimum / np.maximum of a pair: a NaN on either side gives NaN
-__device__ inline float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
-__device__ inline float np_min(float a, float b) { return (a <= b || a != a) ? a : b; }
-
-__device__ inline float iou(const float4 a, const float4 b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = iw * ih;
-    const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-    const float q = inter / ((aa + ab) - inter);
-    return (iw > 0.f && ih > 0.f) ? q : 0.f;
-}
 
 // the class of a prediction row, -1 where seq_nms.row_classes makes it no candidate
 __device__ inline int row_class(float id, float score, int num_class) {

@@ -2,11 +2,10 @@
 // of one push and carries the active tracks from launch to launch in a state block in HBM, so that a stream of frames that
 // never says where it ends keeps its tracks (viddet_amd/track.py::track_online_host is the definition).
 //
-// Arithmetic and tie rules are k_track's, restated here operation for operation (vd_track.hip is not touched): fp32, no product
-// and sum contracted into an FMA, `/` the correctly rounded division, choice_before's order (np.argmax's: a NaN first, the
-// larger value, the lower row).  Nothing is decided on the device: per row the track's id (a creation number counted over the
-// whole stream), its length so far and its maximum score so far come out; track.finalize_tracks makes track_host's arrays of
-// a finished clip from them.
+// Arithmetic and tie rules are k_track's, the same functions (vd_track_math.h): fp32, no product and sum contracted into an
+// FMA, `/` the correctly rounded division, choice_before's order (np.argmax's: a NaN first, the larger value, the lower row).
+// Nothing is decided on the device: per row the track's id (a creation number counted over the whole stream), its length so
+// far and its maximum score so far come out; track.finalize_tracks makes track_host's arrays of a finished clip from them.
 //
 // One launch, one workgroup of kWaves wavefronts per stream.  A stream's state - VD_TRACK_STATE_BYTES - is
 //   int32 n_active, int32 next_id, 8 bytes unused                                   16 bytes
@@ -18,82 +17,16 @@
 
 #pragma clang fp contract(off)
 
+#include "vd_track_math.h"
+
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kMaxN = 128;
-constexpr int kMaxAge = 7;
-constexpr int kMaxActive = kMaxN * (kMaxAge + 1);
 constexpr int kWaves = 8;                             // wavefronts of a stream's workgroup
 constexpr int kThreads = kWaves * kWave;
-constexpr int kFewHolders = 8;                        // up to this many lanes with a choice are read one by one
 constexpr int kHeaderBytes = 16;
 
 static_assert(VD_TRACK_STATE_BYTES == kHeaderBytes + kMaxActive * (16 + 5 * 4), "the state layout and the header disagree");
 static_assert(VD_TRACK_STATE_BYTES % 16 == 0, "every stream's box table must stay 16-byte aligned");
-
-// np.minimum / np.maximum of a pair: a NaN on either side gives NaN
-__device__ inline float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
-__device__ inline float np_min(float a, float b) { return (a <= b || a != a) ? a : b; }
-
-__device__ inline float iou(const float4 a, const float4 b) {
-    const float iw = np_min(a.z, b.z) - np_max(a.x, b.x);
-    const float ih = np_min(a.w, b.w) - np_max(a.y, b.y);
-    const float inter = iw * ih;
-    const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
-    const float q = inter / ((aa + ab) - inter);
-    return (iw > 0.f && ih > 0.f) ? q : 0.f;
-}
-
-// the class of a row, -1 where it is no candidate: id >= 0 (NaN is not), a finite score >= sigma_l, a class below num_class
-__device__ inline int row_class(float id, float score, int num_class, float sigma_l) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u || !(score >= sigma_l)) return -1;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class ? c : -1;
-}
-
-// (iou, row) of a choice; row < 0: none.  np.argmax's order: a NaN before every number, the larger value, then the lower row
-__device__ inline bool choice_before(float v, int r, float bv, int br) {
-    if (r < 0) return false;
-    if (br < 0) return true;
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;
-    return v > bv || ((vn || v == bv) && r < br);
-}
-
-// The choice of a track (last box tb, class tc) among the rows of the frame that are candidates of its class and whose bit in
-// the taken masks is clear; every lane of the wavefront ends with the same (bv, br).  br < 0: no such row.  (k_track's choose)
-__device__ inline void choose(const float4 tb, int tc, const int (&cls)[2], const float4 (&box)[2], unsigned long long tk_lo,
-                              unsigned long long tk_hi, int lane, float& bv, int& br) {
-    bv = 0.f, br = -1;
-    const bool on[2] = {cls[0] == tc && !((tk_lo >> lane) & 1ull), cls[1] == tc && !((tk_hi >> lane) & 1ull)};
-    if (on[0] || on[1]) {
-        const float v[2] = {iou(tb, box[0]), iou(tb, box[1])};
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (on[h] && choice_before(v[h], lane + h * kWave, bv, br)) bv = v[h], br = lane + h * kWave;
-    }
-    unsigned long long holders = __ballot(br >= 0);
-    if (__popcll(holders) <= kFewHolders) {
-        float cv = 0.f;
-        int cr = -1;
-        while (holders) {
-            const int l = __ffsll((long long)holders) - 1;
-            holders &= holders - 1;
-            const float ov = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv), l));
-            const int orow = __builtin_amdgcn_readlane(br, l);
-            if (choice_before(ov, orow, cv, cr)) cv = ov, cr = orow;
-        }
-        bv = cv, br = cr;
-    } else {
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off, kWave);
-            const int orow = __shfl_xor(br, off, kWave);
-            if (choice_before(ov, orow, bv, br)) bv = ov, br = orow;
-        }
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void k_track_push(const float* __restrict__ ids, const float* __restrict__ scores,
                                                          const float* __restrict__ bboxes, int F, int N, int num_class,

@@ -1,17 +1,169 @@
-"""Live video sessions: detect_video on a clip whose frames arrive a few at a time and whose length nobody knows.
+"""Streaming video detection on the host: the engine (StreamEngine), detect_video on a whole clip and live
+sessions, detect_video on a clip whose frames arrive a few at a time and whose length nobody knows.
 
 `net.open_video(step, chunk, track)` returns a VideoSession.  `push(frames)` takes the next frames and returns the detections
 that are final by now, `flush()` ends the clip.  Over any way of cutting a clip into pushes followed by one flush, the
-concatenated results are torch.equal to `net.detect_video(clip, step, chunk)`: the session runs detect_video's own two
-programs in exactly the launch groups detect_video forms (stream.StreamPlanner) - the fp32 operand scales are per tensor, so
-any other grouping would round differently.  With `track`, the emitted rows go through a resumable tracker on the device
+concatenated results are torch.equal to `net.detect_video(clip, step, chunk)`: both run the one engine, in exactly the
+launch groups stream.StreamPlanner forms - the fp32 operand scales are per tensor, so any other grouping would round
+differently.  With `track`, the emitted rows go through a resumable tracker on the device
 (ops.TrackState, vd_track_push) whose state survives from push to push.
 """
 import torch
 
-from . import lib as L
 from . import ops
+from .seq_nms import parse_option as parse_seq_nms
 from .stream import StreamPlanner
+from .track import parse_option as parse_track
+from .tubelet import parse_option as parse_tubelet
+
+
+def frame_shape(net, frames, nv12_name, name, d):
+    """The frames detect_video ("a clip (T,...") and VideoSession.push ("frames (n,...") accept -> net._in_shape's (n, H, W)"""
+    u8 = frames.dtype == torch.uint8
+    if net._dev_nv12 is not None and u8:                          # NV12 (n,H0*3/2,W0); _in_shape checks the rest
+        if frames.dim() != 3 or frames.shape[0] < 1:
+            raise ValueError("set_device_resize(source='nv12') is on: expected %s (%s,H0*3/2,W0) uint8, got %s"
+                             % (nv12_name, d, tuple(frames.shape)))
+    elif frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
+        raise ValueError("expected %s (%s,3,H,W), or (%s,H,W,3) uint8, got %s" % (name, d, d, tuple(frames.shape)))
+    return net._in_shape(frames)
+
+
+class StreamEngine:
+    """The device half of streaming detection, the one place where the feature ring is written and read:
+    detect_video and VideoSession both run their launch groups here.
+
+    run(acts, frames, base, T, hw) runs the actions of `plan` (a stream.StreamPlanner on the net's K, `step` and `chunk`) in
+    order.  frames: the clip's frames from frame `base` on, wherever they live - every group is sliced out of them and staged
+    from there (net._stage_frames), the clip is never moved to the device as a whole.  T: the clip's length, None while it is
+    open.  hw: (H, W) of the network's input.  ('prefix', a, b): frames [a, b) go through the prefix program, their rows
+    into the ring slots a % S ..; ('suffix', t0, n): the slot table of the windows of frames [t0, t0 + n) is uploaded and the
+    suffix program runs (K = 1: the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame).
+    Returns the dict of emitted tensors - ids, scores, bboxes, rows, overflow - as new tensors over the m >= 0 frames of the
+    suffix actions.  `stats` counts the frames through each part; with keep_heads, `heads` collects the three raw head
+    tensors of every K > 1 suffix launch."""
+
+    def __init__(self, net, step, chunk):
+        self.net, self.chunk = net, chunk
+        self.plan = StreamPlanner(net._k, step, chunk)
+        self.stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
+        self.heads = []
+
+    def _programs(self, H, W):
+        """the two programs at this clip's size, current (K > 1)"""
+        net, S = self.net, self.plan.S
+        bf16 = net.precision == 'bf16'
+        key = ('stream_bf16' if bf16 else 'stream', self.chunk, H, W, S)
+        if key not in net._programs:
+            net._programs[key] = net._build_or_evict(lambda: net._build_stream(self.chunk, H, W, S))
+        sp = net._programs[key]
+        if bf16:
+            net._bf16_current(sp, sp['packs'], [sp['pre'], sp['suf']])
+        else:
+            net._refresh_fold()
+        net._refresh_wamax()
+        return sp
+
+    def _prefix(self, sp, frames, base, a, b):
+        S, m = self.plan.S, b - a
+        self.net._stage_frames(sp['pb']['in'], frames, a - base, b - base)
+        sp['pre'].run()
+        for t in sp['srcs']:                                      # rows -> slots (a run of frames wraps at most once: m <= S)
+            ring, src = sp['sb']['ring:' + t], sp['pb'][t]
+            s0 = a % S
+            m0 = min(m, S - s0)
+            ring[s0:s0 + m0].copy_(src[:m0])
+            if m0 < m:
+                ring[:m - m0].copy_(src[m0:m])
+        self.stats['prefix_frames'] += m
+
+    def _suffix(self, sp, frames, base, t0, n, T, hw, keep_heads):
+        net = self.net
+        if net._k == 1:
+            # no join, no prefix: the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame
+            x = frames[t0 - base:t0 - base + n]
+            if n < self.chunk:
+                x = torch.cat([x, x[-1:].expand((self.chunk - n,) + tuple(x.shape[1:]))], dim=0)
+            net._forward_infer(x)
+            o = net._programs[('infer_bf16' if net.precision == 'bf16' else 'infer', self.chunk) + tuple(hw)][2]
+        else:
+            sp['slots'].copy_(torch.from_numpy(self.plan.slots(t0, n, T)))
+            sp['suf'].run()
+            o = sp['o']
+            if keep_heads:                                        # tests: the raw head tensors of every chunk
+                self.heads.append([sp['sb'][h][:n].clone() for h in net.head_names])
+        self.stats['suffix_frames'] += n
+        self.stats['chunks'] += 1
+        return {k: o[k][:n].clone() for k in ('ids', 'scores', 'bboxes', 'rows', 'overflow')}
+
+    def run(self, acts, frames, base, T, hw, keep_heads=False):
+        net = self.net
+        sp = self._programs(*hw) if net._k > 1 and acts else None
+        outs = []
+        for kind, a, b in acts:
+            if kind == 'prefix':
+                self._prefix(sp, frames, base, a, b)
+            else:
+                outs.append(self._suffix(sp, frames, base, a, b, T, hw, keep_heads))
+        if outs:
+            return {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
+        dev, P = net.device, net.post_nms
+        return dict(ids=torch.empty(0, P, 1, device=dev), scores=torch.empty(0, P, 1, device=dev),
+                    bboxes=torch.empty(0, P, 4, device=dev), rows=torch.empty(0, P, dtype=torch.int32, device=dev),
+                    overflow=torch.empty(0, dtype=torch.int32, device=dev))
+
+
+def _follow(rows, perm):
+    """last_rows behind a pass that permutes the rows of every frame: the old row of every output row, -1 where it has none"""
+    old = torch.gather(rows, 1, perm.clamp(min=0).long())
+    return torch.where(perm >= 0, old, torch.full_like(old, -1))
+
+
+def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None):
+    """YOLOV3.detect_video (its docstring is the description): a clip whose end is known is one push and one flush of the
+    planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> tubelet on the finished clip."""
+    why = net._stream_refusal()
+    if why is not None:
+        raise NotImplementedError("detect_video with " + why)
+    if net._live is not None:
+        raise RuntimeError("detect_video: %r has frames in flight on this net (they share the feature ring): flush() it first"
+                           % (net._live,))
+    seq = parse_seq_nms(seq_nms, net.post_nms, "detect_video")
+    trk = parse_track(track, net.post_nms, "detect_video")
+    tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
+    net.last_tracks = None
+    net.last_tubelet = net.last_pre_tubelet = None
+    if net._k > 1:
+        net._stream_split()                                       # the graph's own word, before anything touches the GPU
+    step, chunk = int(step), int(chunk)
+    if step < 1 or chunk < 1:
+        raise ValueError("detect_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
+    T, H, W = frame_shape(net, frames, "an NV12 clip", "a clip", "T")
+    assert 0 < net.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
+    eng = StreamEngine(net, step, chunk)
+    acts = eng.plan.push(T) + eng.plan.flush()
+    out = eng.run(acts, frames, 0, T, (H, W), keep_heads=getattr(net, 'stream_keep_heads', False))
+    net.stream_stats = eng.stats
+    net.stream_heads = [torch.cat(h) for h in zip(*eng.heads)] if eng.heads else None
+    net.last_rows, net.last_overflow = out['rows'], out['overflow']
+    res = out['ids'], out['scores'], out['bboxes']
+    num_class = 1 if net.agnostic else net.num_class
+    if seq is not None:
+        net.last_plain = res                                      # the rows ahead of Seq-NMS
+        boxes = res[2] if seq[1] is None else res[2].clamp(0, float(seq[1]))
+        ids, scores, bboxes, perm = ops.seq_nms(res[0], res[1], boxes, num_class=num_class, **seq[0])
+        net.last_rows = _follow(net.last_rows, perm)
+        res = ids, scores, bboxes
+    if trk is not None:
+        boxes = res[2] if trk[1] is None else res[2].clamp(0, float(trk[1]))
+        net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if tub_kw is not None:
+            net.last_pre_tubelet = res[0], res[1], boxes          # the rows the tracker saw
+            out_t = ops.tubelet(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **tub_kw)
+            net.last_rows = _follow(net.last_rows, out_t[3])
+            net.last_tubelet = out_t[3], out_t[4], out_t[5]
+            res = out_t[0], out_t[1], out_t[2]
+    return res
 
 
 class VideoSession:
@@ -53,30 +205,20 @@ class VideoSession:
             raise ValueError("open_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
         self.track_decide = None
         self._trk_kw = self._trk_clip = self._trk = None
-        if track is not None and track is not False:
-            from .track import DEFAULTS, check_params
-            kw = {} if track is True else dict(track)
-            self._trk_clip = kw.pop("clip", None)
-            unknown = sorted(set(kw) - set(DEFAULTS))
-            if unknown:
-                raise ValueError("open_video: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age, got %s" % ", ".join(unknown))
-            kw = dict(DEFAULTS, **kw)
-            check_params(who="open_video with track", **kw)
-            if net.post_nms > L.TRACK_MAX_ROWS:
-                raise ValueError("open_video with track: post_nms=%d rows per frame, the tracker takes at most %d"
-                                 % (net.post_nms, L.TRACK_MAX_ROWS))
-            self.track_decide = dict(sigma_h=kw.pop("sigma_h"), t_min=kw.pop("t_min"))
-            self._trk_kw = kw
+        trk = parse_track(track, net.post_nms, "open_video")
+        if trk is not None:
+            self._trk_kw, self._trk_clip = trk
+            self.track_decide = dict(sigma_h=self._trk_kw.pop("sigma_h"), t_min=self._trk_kw.pop("t_min"))
         if net._k > 1:
             net._stream_split()                                   # the graph's own word, before anything touches the GPU
         self.net, self.step, self.chunk = net, step, chunk
-        self._plan = StreamPlanner(net._k, step, chunk)
+        self._eng = StreamEngine(net, step, chunk)
+        self._plan = self._eng.plan
         self._buf = None                                          # the frames [_buf0, frames_in) that wait for their group
         self._buf0 = 0
         self._shape = None                                        # (shape of a frame, dtype), fixed by the clip's first push
         self._hw = None
         self.frames_out = 0
-        self.stream_stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
         self.last_rows = self.last_overflow = self.last_tracks = None
 
     def __repr__(self):
@@ -86,74 +228,18 @@ class VideoSession:
     def frames_in(self):
         return self._plan.frames_in
 
-    # ------------------------------------------------------------------ the two launch groups, as detect_video runs them
-    def _programs(self):
-        """detect_video's programs at this clip's size, current (K > 1)"""
-        net = self.net
-        H, W = self._hw
-        bf16 = net.precision == 'bf16'
-        key = ('stream_bf16' if bf16 else 'stream', self.chunk, H, W, self._plan.S)
-        if key not in net._programs:
-            net._programs[key] = net._build_or_evict(lambda: net._build_stream(self.chunk, H, W, self._plan.S))
-        sp = net._programs[key]
-        if bf16:
-            net._bf16_current(sp, sp['packs'], [sp['pre'], sp['suf']])
-        else:
-            net._refresh_fold()
-        net._refresh_wamax()
-        return sp
-
-    def _prefix(self, sp, frames, a, b):
-        net, S, m = self.net, self._plan.S, b - a
-        net._stage_frames(sp['pb']['in'], frames, a - self._buf0, b - self._buf0)
-        sp['pre'].run()
-        for t in sp['srcs']:                                      # rows -> slots (a run of frames wraps at most once: m <= S)
-            ring, src = sp['sb']['ring:' + t], sp['pb'][t]
-            s0 = a % S
-            m0 = min(m, S - s0)
-            ring[s0:s0 + m0].copy_(src[:m0])
-            if m0 < m:
-                ring[:m - m0].copy_(src[m0:m])
-        self.stream_stats['prefix_frames'] += m
-
-    def _suffix(self, sp, frames, t0, n, T):
-        net = self.net
-        if net._k == 1:
-            # the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame
-            x = frames[t0 - self._buf0:t0 - self._buf0 + n]
-            if n < self.chunk:
-                x = torch.cat([x, x[-1:].expand((self.chunk - n,) + tuple(x.shape[1:]))], dim=0)
-            net._forward_infer(x)
-            o = net._programs[('infer_bf16' if net.precision == 'bf16' else 'infer', self.chunk) + self._hw][2]
-        else:
-            sp['slots'].copy_(torch.from_numpy(self._plan.slots(t0, n, T)))
-            sp['suf'].run()
-            o = sp['o']
-        self.stream_stats['suffix_frames'] += n
-        self.stream_stats['chunks'] += 1
-        return {k: o[k][:n].clone() for k in ('ids', 'scores', 'bboxes', 'rows', 'overflow')}
+    @property
+    def stream_stats(self):
+        return self._eng.stats
 
     def _run(self, acts, frames, T):
         """the planner's actions on `frames` (the clip's frames from _buf0 on) -> (t0, ids, scores, bboxes) of the frames they emit"""
         net = self.net
-        sp = self._programs() if net._k > 1 and acts else None
-        outs = []
-        for kind, a, b in acts:
-            if kind == 'prefix':
-                self._prefix(sp, frames, a, b)
-            else:
-                outs.append(self._suffix(sp, frames, a, b, T))
-        dev, P = net.device, net.post_nms
-        if outs:
-            out = {k: torch.cat([o[k] for o in outs]) for k in outs[0]}
-        else:
-            out = dict(ids=torch.empty(0, P, 1, device=dev), scores=torch.empty(0, P, 1, device=dev),
-                       bboxes=torch.empty(0, P, 4, device=dev), rows=torch.empty(0, P, dtype=torch.int32, device=dev),
-                       overflow=torch.empty(0, dtype=torch.int32, device=dev))
+        out = self._eng.run(acts, frames, self._buf0, T, self._hw)
         self.last_rows, self.last_overflow = out['rows'], out['overflow']
         if self._trk_kw is not None:
             if self._trk is None:
-                self._trk = ops.TrackState(1, P, 1 if net.agnostic else net.num_class, device=dev, **self._trk_kw)
+                self._trk = ops.TrackState(1, net.post_nms, 1 if net.agnostic else net.num_class, device=net.device, **self._trk_kw)
             boxes = out['bboxes'] if self._trk_clip is None else out['bboxes'].clamp(0, float(self._trk_clip))
             self.last_tracks = self._trk.push(out['ids'], out['scores'], boxes)
         t0 = self.frames_out
@@ -165,19 +251,12 @@ class VideoSession:
         net = self.net
         if net._live is not None and net._live is not self:
             raise RuntimeError("push: the net has another video session with frames in flight (%r): flush() it first" % (net._live,))
-        u8 = frames.dtype == torch.uint8
-        if net._dev_nv12 is not None and u8:                      # NV12 frames (n,H0*3/2,W0); _in_shape checks the rest
-            if frames.dim() != 3 or frames.shape[0] < 1:
-                raise ValueError("set_device_resize(source='nv12') is on: expected NV12 frames (n,H0*3/2,W0) uint8, got %s"
-                                 % (tuple(frames.shape),))
-        elif frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
-            raise ValueError("expected frames (n,3,H,W), or (n,H,W,3) uint8, got %s" % (tuple(frames.shape),))
-        _, H, W = net._in_shape(frames)
+        _, H, W = frame_shape(net, frames, "NV12 frames", "frames", "n")
         shape = (tuple(frames.shape[1:]), frames.dtype)
         if self.frames_in == 0:
             assert 0 < net.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
             self._shape, self._hw = shape, (H, W)
-            self.stream_stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
+            self._eng.stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
         elif shape != self._shape:
             raise ValueError("push: this clip's frames are %s %s (its first push fixed that), got %s %s; flush() starts a new clip"
                              % (self._shape[0], str(self._shape[1]).replace("torch.", ""), shape[0], str(shape[1]).replace("torch.", "")))

@@ -2155,11 +2155,10 @@ class YOLOV3(object):
         import copy
         pools = [n for n in self.nodes if isinstance(n, PoolNode)]
         assert pools, "no join to split at"
-        ins = lambda n: [t for t in (getattr(n, a, None) for a in ('src', 'residual', 'up', 'route', 'a', 'b')) if t is not None]
         need = {p.src for p in pools}
         for n in reversed(self.nodes):
             if not isinstance(n, PoolNode) and n.dst in need:
-                need.update(ins(n))
+                need.update(node_inputs(n))
         prefix, suffix = [], []
         for n in self.nodes:
             if isinstance(n, PoolNode) or n.dst not in need:
@@ -2174,7 +2173,7 @@ class YOLOV3(object):
             if isinstance(n, PoolNode):
                 assert n.K == self._k and self.tensors[n.src][3] == self._k and self.tensors[n.dst][3] == 1, n.name
             else:
-                assert isinstance(n, (ConvNode, UpcatNode)) and n.fr == 1 and not (set(ins(n)) & need), \
+                assert isinstance(n, (ConvNode, UpcatNode)) and n.fr == 1 and not (set(node_inputs(n)) & need), \
                     "%s behind the joins reads a per-frame tensor" % n.name
         return prefix, suffix
 
@@ -2223,147 +2222,8 @@ class YOLOV3(object):
         last_tracks stays ops.track's result on them, last_tubelet = (perm, track_out, dropped), last_rows follows perm (-1 on
         filled and empty rows).  A call without it sets last_tubelet to None.  open_video takes no such argument: a hole is
         known only once its track resumes, after the frame has been given out."""
-        why = self._stream_refusal()
-        if why is not None:
-            raise NotImplementedError("detect_video with " + why)
-        if self._live is not None:
-            raise RuntimeError("detect_video: %r has frames in flight on this net (they share the feature ring): flush() it first"
-                               % (self._live,))
-        seq_kw = None
-        if seq_nms is not None and seq_nms is not False:
-            seq_kw = {} if seq_nms is True else dict(seq_nms)
-            seq_clip = seq_kw.pop("clip", None)
-            unknown = sorted(set(seq_kw) - {"link_thresh", "nms_thresh", "rescore"})
-            if unknown:
-                raise ValueError("detect_video: seq_nms takes link_thresh, nms_thresh and rescore, got %s" % ", ".join(unknown))
-            if self.post_nms > L.SEQ_NMS_MAX_ROWS:
-                raise ValueError("detect_video with seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most %d"
-                                 % (self.post_nms, L.SEQ_NMS_MAX_ROWS))
-        trk_kw = None
-        if track is not None and track is not False:
-            from .track import DEFAULTS, check_params
-            trk_kw = {} if track is True else dict(track)
-            trk_clip = trk_kw.pop("clip", None)
-            unknown = sorted(set(trk_kw) - set(DEFAULTS))
-            if unknown:
-                raise ValueError("detect_video: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age, got %s" % ", ".join(unknown))
-            check_params(who="detect_video with track", **trk_kw)
-            if self.post_nms > L.TRACK_MAX_ROWS:
-                raise ValueError("detect_video with track: post_nms=%d rows per frame, the tracker takes at most %d"
-                                 % (self.post_nms, L.TRACK_MAX_ROWS))
-        tub_kw = None
-        if tubelet is not None and tubelet is not False:
-            from .tubelet import DEFAULTS as TUB_DEFAULTS, check_params as check_tubelet
-            tub_kw = {} if tubelet is True else dict(tubelet)
-            unknown = sorted(set(tub_kw) - set(TUB_DEFAULTS))
-            if unknown:
-                raise ValueError("detect_video: tubelet takes rescore, max_gap and drop_untracked, got %s" % ", ".join(unknown))
-            check_tubelet(who="detect_video with tubelet", **tub_kw)
-            if trk_kw is None:
-                raise ValueError("detect_video: tubelet needs track: the pass runs over the tracks of the clip")
-        self.last_tracks = None
-        self.last_tubelet = self.last_pre_tubelet = None
-        if self._k > 1:
-            self._stream_split()                                  # the graph's own word, before anything touches the GPU
-        from .stream import stream_window_slots, ring_size, chunk_slots
-        step, chunk = int(step), int(chunk)
-        if step < 1 or chunk < 1:
-            raise ValueError("detect_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
-        u8 = frames.dtype == torch.uint8
-        if self._dev_nv12 is not None and u8:                     # an NV12 clip (T,H0*3/2,W0); _in_shape checks the rest
-            if frames.dim() != 3 or frames.shape[0] < 1:
-                raise ValueError("set_device_resize(source='nv12') is on: expected an NV12 clip (T,H0*3/2,W0) uint8, got %s"
-                                 % (tuple(frames.shape),))
-        elif frames.dim() != 4 or frames.shape[0] < 1 or (frames.shape[-1] if u8 else frames.shape[1]) != 3:
-            raise ValueError("expected a clip (T,3,H,W), or (T,H,W,3) uint8, got %s" % (tuple(frames.shape),))
-        T, H, W = self._in_shape(frames)
-        assert 0 < self.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
-        dev, K = self.device, self._k
-        out = dict(ids=torch.empty(T, self.post_nms, 1, device=dev), scores=torch.empty(T, self.post_nms, 1, device=dev),
-                   bboxes=torch.empty(T, self.post_nms, 4, device=dev),
-                   rows=torch.empty(T, self.post_nms, dtype=torch.int32, device=dev),
-                   overflow=torch.zeros(T, dtype=torch.int32, device=dev))
-        stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
-        heads = [] if getattr(self, 'stream_keep_heads', False) else None     # tests: the raw head tensors of every chunk
-
-        def keep(o, t0, n, bufs=None):
-            for k_ in out:
-                out[k_][t0:t0 + n].copy_(o[k_][:n])
-            if heads is not None and bufs is not None:
-                heads.append([bufs[h][:n].clone() for h in self.head_names])
-            stats['suffix_frames'] += n
-            stats['chunks'] += 1
-
-        if K == 1:
-            # no join, no prefix: the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame
-            for t0 in range(0, T, chunk):
-                n = min(chunk, T - t0)
-                x = frames[t0:t0 + n]
-                if n < chunk:
-                    x = torch.cat([x, x[-1:].expand((chunk - n,) + tuple(x.shape[1:]))], dim=0)
-                self._forward_infer(x)
-                keep(self._programs[('infer_bf16' if self.precision == 'bf16' else 'infer', chunk, H, W)][2], t0, n)
-        else:
-            S = ring_size(K, step, chunk)
-            bf16 = self.precision == 'bf16'
-            key = ('stream_bf16' if bf16 else 'stream', chunk, H, W, S)
-            if key not in self._programs:
-                self._programs[key] = self._build_or_evict(lambda: self._build_stream(chunk, H, W, S))
-            sp = self._programs[key]
-            if bf16:
-                self._bf16_current(sp, sp['packs'], [sp['pre'], sp['suf']])
-            else:
-                self._refresh_fold()
-            self._refresh_wamax()
-            windows = stream_window_slots(T, K, step)
-            reach = (K // 2) * step
-            done = 0                                             # frames [max(0, done - S), done) are in the ring
-            for t0 in range(0, T, chunk):
-                n = min(chunk, T - t0)
-                need = min(T, t0 + n + reach)
-                while done < need:                               # each frame goes through the prefix here, once
-                    m = min(chunk, need - done)
-                    self._stage_frames(sp['pb']['in'], frames, done, done + m)
-                    sp['pre'].run()
-                    for t in sp['srcs']:                         # rows -> slots (a run of frames wraps at most once: m <= S)
-                        ring, src = sp['sb']['ring:' + t], sp['pb'][t]
-                        s0 = done % S
-                        m0 = min(m, S - s0)
-                        ring[s0:s0 + m0].copy_(src[:m0])
-                        if m0 < m:
-                            ring[:m - m0].copy_(src[m0:m])
-                    done += m
-                    stats['prefix_frames'] += m
-                tab = chunk_slots(windows, t0, n, chunk, S, max(0, done - S), done)
-                sp['slots'].copy_(torch.from_numpy(tab))
-                sp['suf'].run()
-                keep(sp['o'], t0, n, sp['sb'])
-        self.stream_stats = stats
-        self.stream_heads = [torch.cat(h) for h in zip(*heads)] if heads else None
-        self.last_rows, self.last_overflow = out['rows'], out['overflow']
-        if seq_kw is not None:
-            self.last_plain = out['ids'], out['scores'], out['bboxes']        # the rows ahead of Seq-NMS
-            boxes = out['bboxes'] if seq_clip is None else out['bboxes'].clamp(0, float(seq_clip))
-            ids, scores, bboxes, perm = ops.seq_nms(out['ids'], out['scores'], boxes,
-                                                    num_class=1 if self.agnostic else self.num_class, **seq_kw)
-            rows = torch.gather(out['rows'], 1, perm.clamp(min=0).long())          # the old row of every output row
-            self.last_rows = torch.where(perm >= 0, rows, torch.full_like(rows, -1))
-            res = ids, scores, bboxes
-        else:
-            res = out['ids'], out['scores'], out['bboxes']
-        if trk_kw is not None:
-            boxes = res[2] if trk_clip is None else res[2].clamp(0, float(trk_clip))
-            self.last_tracks = ops.track(res[0], res[1], boxes, num_class=1 if self.agnostic else self.num_class, **trk_kw)
-            if tub_kw is not None:
-                self.last_pre_tubelet = res[0], res[1], boxes             # the rows the tracker saw
-                out_t = ops.tubelet(res[0], res[1], boxes, self.last_tracks[0], num_class=1 if self.agnostic else self.num_class,
-                                    **tub_kw)
-                perm = out_t[3]
-                rows = torch.gather(self.last_rows, 1, perm.clamp(min=0).long())
-                self.last_rows = torch.where(perm >= 0, rows, torch.full_like(rows, -1))
-                self.last_tubelet = out_t[3], out_t[4], out_t[5]
-                res = out_t[0], out_t[1], out_t[2]
-        return res
+        from .live import detect_video
+        return detect_video(self, frames, step, chunk, seq_nms, track, tubelet)
 
     def open_video(self, step=1, chunk=8, track=None):
         """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and

@@ -20,6 +20,21 @@ RESCORE = {"avg": 0, "max": 1}
 MAX_ROWS = 128          # rows per frame vd_seq_nms takes (a 128-bit mask per row)
 
 
+def parse_option(seq_nms, post_nms, who):
+    """The `seq_nms=` option of `who` (detect_video): None / False -> None; True or a dict of link_thresh / nms_thresh / rescore
+    and `clip` -> (the dict as given, `clip` or None).  A ValueError names what is not usable."""
+    if seq_nms is None or seq_nms is False:
+        return None
+    kw = {} if seq_nms is True else dict(seq_nms)
+    clip = kw.pop("clip", None)
+    unknown = sorted(set(kw) - {"link_thresh", "nms_thresh", "rescore"})
+    if unknown:
+        raise ValueError("%s: seq_nms takes link_thresh, nms_thresh and rescore, got %s" % (who, ", ".join(unknown)))
+    if post_nms > MAX_ROWS:
+        raise ValueError("%s with seq_nms: post_nms=%d rows per frame, Seq-NMS takes at most %d" % (who, post_nms, MAX_ROWS))
+    return kw, clip
+
+
 def row_classes(ids, scores, num_class=None):
     """(F,N) int64: the class of every candidate row, -1 for a row that is no candidate"""
     ids = np.asarray(ids, dtype=_F).reshape(ids.shape[0], ids.shape[1])

@@ -24,6 +24,7 @@ vd_track_push, `ops.TrackState`, equals it bit for bit); `finalize_tracks` is st
 """
 import numpy as np
 
+from .lib import TRACK_MAX_ROWS
 from .seq_nms import MAX_ROWS, _clips, iou_matrix, row_classes
 
 _F = np.float32
@@ -48,6 +49,23 @@ def check_params(sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0, wh
             raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
         out.append(int(v))
     return tuple(out)
+
+
+def parse_option(track, post_nms, who):
+    """The `track=` option of `who` (detect_video, open_video): None / False -> None; True or a dict of the five parameters
+    and `clip` -> (the five parameters, defaults filled in, `clip` or None).  A ValueError names what is not usable."""
+    if track is None or track is False:
+        return None
+    kw = {} if track is True else dict(track)
+    clip = kw.pop("clip", None)
+    unknown = sorted(set(kw) - set(DEFAULTS))
+    if unknown:
+        raise ValueError("%s: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age, got %s" % (who, ", ".join(unknown)))
+    kw = dict(DEFAULTS, **kw)
+    check_params(who=who + " with track", **kw)
+    if post_nms > TRACK_MAX_ROWS:
+        raise ValueError("%s with track: post_nms=%d rows per frame, the tracker takes at most %d" % (who, post_nms, TRACK_MAX_ROWS))
+    return kw, clip
 
 
 def track_host(ids, scores, bboxes, clip_start=None, num_class=None, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0,

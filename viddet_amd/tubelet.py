@@ -43,6 +43,21 @@ def check_params(rescore="avg", max_gap=MAX_AGE, drop_untracked=False, who="tube
     return rescore, int(max_gap), bool(drop_untracked)
 
 
+def parse_option(tubelet, tracked, who):
+    """The `tubelet=` option of `who` (detect_video): None / False -> None; True or a dict of the three parameters -> the dict
+    as given.  tracked: the call has `track` on - the pass runs over its tracks.  A ValueError names what is not usable."""
+    if tubelet is None or tubelet is False:
+        return None
+    kw = {} if tubelet is True else dict(tubelet)
+    unknown = sorted(set(kw) - set(DEFAULTS))
+    if unknown:
+        raise ValueError("%s: tubelet takes rescore, max_gap and drop_untracked, got %s" % (who, ", ".join(unknown)))
+    check_params(who=who + " with tubelet", **kw)
+    if not tracked:
+        raise ValueError("%s: tubelet needs track: the pass runs over the tracks of the clip" % who)
+    return kw
+
+
 def tubelet_host(ids, scores, bboxes, track, clip_start=None, num_class=None, rescore="avg", max_gap=MAX_AGE, drop_untracked=False,
                  stats=None):
     """ids (F,N[,1]), scores (F,N[,1]), bboxes (F,N,4), track (F,N) int32 -> (ids, scores, bboxes of the inputs' shapes; perm

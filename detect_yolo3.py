@@ -19,7 +19,8 @@ reference counterpart) runs sequence NMS over the detections of every clip on th
 predictions and results are written as without it, the rescored ones beside them under pred_seq and *_seq.  `--track` (no
 reference counterpart) links the detections of every clip into tracks on the device (vd_track): every prediction
 set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
-clip; everything else is written as without the flag.  `--live` (with --stream; no reference counterpart) sends every clip
+clip; everything else is written as without the flag; `--track_method sort` links them with SORT instead (vd_track_sort, DESIGN.md
+34; not with --live).  `--live` (with --stream; no reference counterpart) sends every clip
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
 the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
 pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
@@ -140,12 +141,20 @@ def parse_flags(argv=None):
            "those of --stream byte for byte, --track included (its online ids are decided at the clip's end).  Not with "
            "--seq_nms, which has no online form")
     A("--live_push", type=int, default=1, help="--live: frames per push (default 1)")
-    A("--track_iou", type=float, default=0.5, help="--track: a box joins a track where its IoU to the track's last box is at least this")
+    A("--track_method", default="iou", choices=["iou", "sort"],
+      help="--track: iou (the default, vd_track) or sort (vd_track_sort, DESIGN.md 34): SORT of Bewley et al. 2016 - every track is "
+           "predicted by a constant-velocity Kalman filter and the predictions are matched to the frame's boxes by an optimal "
+           "assignment, so a track survives missed frames of a moving object and crossing objects keep their ids.  The same files "
+           "are written.  Not with --live")
+    A("--track_iou", type=float, default=None,
+      help="--track: a box joins a track where its IoU to the track's last box (sort: its predicted box) is at least this "
+           "(default: iou 0.5, sort 0.3)")
     A("--track_low", type=float, default=0.0, help="--track: detections scored below this take no part")
     A("--track_high", type=float, default=0.5, help="--track: a track is kept where its best score is at least this")
     A("--track_min_len", type=int, default=2, help="--track: a track is kept where it holds at least this many boxes")
-    A("--track_max_age", type=int, default=0,
-      help="--track: the frames in a row a track may go without a box before it is closed, 0 (the paper) to 7")
+    A("--track_max_age", type=int, default=None,
+      help="--track: the frames in a row a track may go without a box before it is closed, 0 to 7 (default: iou 0, sort 1, "
+           "the papers' values)")
     A("--tubelet", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) with --track: a tubelet pass over every tracked clip on the device (vd_tubelet): the rows "
            "of a track take the track's score, the frames a track skipped get a linearly interpolated box, every frame is "
@@ -159,7 +168,17 @@ def parse_flags(argv=None):
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
-    return ap.parse_args(argv)
+    FLAGS = ap.parse_args(argv)
+    # --track_iou / --track_max_age left out: the linking method's own defaults (iou: 0.5 and 0, sort: 0.3 and 1)
+    if FLAGS.track_method == "sort":
+        from viddet_amd.sort import DEFAULTS as track_defaults
+    else:
+        from viddet_amd.track import DEFAULTS as track_defaults
+    if FLAGS.track_iou is None:
+        FLAGS.track_iou = track_defaults["sigma_iou"]
+    if FLAGS.track_max_age is None:
+        FLAGS.track_max_age = track_defaults["max_age"]
+    return FLAGS
 
 
 def _collect(boxes, dataset, ids, scores, bboxes, sidxs, W):
@@ -182,11 +201,27 @@ def seq_nms_args(FLAGS):
 
 
 def track_args(FLAGS):
-    """the dict net.detect_video and ops.track take, None without --track"""
+    """the dict net.detect_video and link_rows take, None without --track: ops.track's parameters and, with --track_method
+    sort, `method`; --track_iou and --track_max_age left out take the method's defaults (iou: 0.5 and 0, sort: 0.3 and 1)"""
     if not getattr(FLAGS, "track", False):
         return None
-    return dict(sigma_iou=FLAGS.track_iou, sigma_l=FLAGS.track_low, sigma_h=FLAGS.track_high, t_min=FLAGS.track_min_len,
-                max_age=FLAGS.track_max_age)
+    method = getattr(FLAGS, "track_method", "iou")
+    if method == "sort":
+        from viddet_amd.sort import DEFAULTS
+    else:
+        from viddet_amd.track import DEFAULTS
+    iou, age = getattr(FLAGS, "track_iou", None), getattr(FLAGS, "track_max_age", None)
+    args = dict(sigma_iou=DEFAULTS["sigma_iou"] if iou is None else iou, sigma_l=FLAGS.track_low, sigma_h=FLAGS.track_high,
+                t_min=FLAGS.track_min_len, max_age=DEFAULTS["max_age"] if age is None else age)
+    return dict(args, method=method) if method != "iou" else args
+
+
+def link_rows(ids, scores, bboxes, track, **kw):
+    """the track id of every row: ops.track, or with track_args' method 'sort' ops.track_sort, on the rows of whole clips"""
+    from viddet_amd import ops
+    track = dict(track)
+    link = ops.track_sort if track.pop("method", "iou") == "sort" else ops.track
+    return link(ids, scores, bboxes, **kw, **track)[0]
 
 
 def tubelet_args(FLAGS):
@@ -260,7 +295,7 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
         C = 1 if net.agnostic else net.num_class
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         if track is not None:
-            linked = ops.track(ids, scores, bboxes, clip_start=cs, num_class=C, **track)[0]
+            linked = link_rows(ids, scores, bboxes, track, clip_start=cs, num_class=C)
             _collect_tracks(tracks, dataset, ids, linked, sidxs)
             if tubelet is not None:
                 out = ops.tubelet(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **tubelet)
@@ -270,8 +305,7 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
             out = ops.seq_nms(ids, scores, bboxes, clip_start=cs, num_class=C, **seq_nms)
             _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
             if track is not None:
-                _collect_tracks(tracks_seq, dataset, out[0], ops.track(out[0], out[1], out[2], clip_start=cs, num_class=C, **track)[0],
-                                sidxs)
+                _collect_tracks(tracks_seq, dataset, out[0], link_rows(out[0], out[1], out[2], track, clip_start=cs, num_class=C), sidxs)
     if track is None:
         return boxes, boxes_seq
     if tubelet is not None:
@@ -346,8 +380,8 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             if track is not None:
                 from viddet_amd import ops
                 _collect_tracks(tracks_seq, dataset, out[0], net.last_tracks[0], sidxs)
-                plain = ops.track(ids, scores, bboxes.clamp(0, W), num_class=1 if net.agnostic else net.num_class, **track)
-                _collect_tracks(tracks, dataset, ids, plain[0], sidxs)
+                plain = link_rows(ids, scores, bboxes.clamp(0, W), track, num_class=1 if net.agnostic else net.num_class)
+                _collect_tracks(tracks, dataset, ids, plain, sidxs)
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
         c += x.shape[0]
         if c > max_do:
@@ -422,9 +456,14 @@ def check_flags(FLAGS):
         if not getattr(FLAGS, "stream", False) and getattr(FLAGS, "synthetic_videos", None) is None:
             raise NotImplementedError("--track needs clips: give --stream or --synthetic_videos (the plain synthetic set is "
                                       "unrelated still images)")
+        if getattr(FLAGS, "track_method", "iou") not in ("iou", "sort"):
+            raise NotImplementedError("--track_method must be iou or sort, got %r" % (FLAGS.track_method,))
+        if getattr(FLAGS, "track_method", "iou") != "iou" and getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_method %s does not combine with --live: it has no resumable form yet, a live "
+                                      "session carries the iou tracker only" % FLAGS.track_method)
         from viddet_amd.track import check_params
         try:
-            check_params(who="--track", **track_args(FLAGS))
+            check_params(who="--track", **{k: v for k, v in track_args(FLAGS).items() if k != "method"})
         except ValueError as e:
             names = dict(sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high", t_min="--track_min_len",
                          max_age="--track_max_age")

@@ -853,6 +853,44 @@ int vd_mot_match(const float* gt_boxes, const int32_t* gt_cls, const int32_t* gt
                  float iou_thresh, int agnostic, int32_t* match, float* miou, int32_t* flags, uint32_t* adm, void* ws,
                  int64_t ws_bytes, void* stream);
 
+/* ---- The detections of video clips linked into tracks by SORT (vd_track_sort.hip): what
+ * viddet_amd.sort.sort_host computes, bit for bit, on all four outputs - Bewley et al., "Simple Online and Realtime Tracking"
+ * (ICIP 2016).  ids, scores, bboxes, clip_start, V, F, N, num_class, sigma_l, sigma_h, t_min, max_age: as vd_track takes them,
+ * and a row is a candidate iff it is one there.  The filter of a track is 17 floats, (x, xd, p00, p01, p11) for the centre u,
+ * v and the area s and (r, p) for the aspect w / h; every operation is one fp32 operation, nothing is contracted into an FMA,
+ * `/` and sqrt are correctly rounded:
+ *   measurement of a box  w = x2 - x1, h = y2 - y1, z = (x1 + w/2, y1 + h/2, w*h, w/h)
+ *   start                 x = z, xd = 0, (p00, p01, p11) = (10, 0, 1e4); p = 10 for r
+ *   predict               first `if s + ds <= 0: ds = 0` (a NaN compares false); per pair, on the old values: x = x + xd,
+ *                         p00 = ((p00 + p01) + (p01 + p11)) + 1, p01 = p01 + p11, p11 = p11 + (.01, .01, 1e-4); p = p + 1
+ *   box of a state        w = sqrt(s*r), h = s / w, (u - w/2, v - h/2, u + w/2, v + h/2)
+ *   update with z         per pair: S = p00 + (1, 1, 10), k0 = p00 / S, k1 = p01 / S, y = z - x, x = x + k0*y, xd = xd + k1*y,
+ *                         p11 = p11 - k1*p01, p01 = p01 - k0*p01, p00 = p00 - k0*p00; S = p + 10, k = p / S,
+ *                         r = r + k*(z - r), p = p - k*p
+ * Per clip, frames in order.  Predict: every active track.  Associate: rows = the frame's candidates in row order, columns = the
+ * active tracks in order of creation, then a dummy per row; (row i, track k) is admissible iff the classes are equal and
+ * iou(predicted box of k, box of i) >= sigma_iou (vd_seq_nms's arithmetic, the track side first; a NaN is not admissible) and
+ * costs 2^20 - int(iou * 2^20); a row's own dummy costs 2^27; the minimum-cost assignment is vd_mot_match's - successive
+ * shortest augmenting paths with int64 potentials, rows in row order, among columns of equal least slack the lowest; entered
+ * only when the frame has a candidate and a track is active.  Update: a matched track is updated with its row, its miss count
+ * 0, its length one more, its maximum max(maximum, score); every other track's miss count grows by one and the track is closed
+ * once it exceeds max_age; the survivors keep their order.  Start: every candidate that took its dummy (every candidate where
+ * no assignment was made) starts a track, in row order; ids as vd_track's.  Decide, at the clip's end, as vd_track.  Outputs,
+ * written in full: out_track, out_len, out_score [F][N] as vd_track's; out_tbox [F][N][4]: the posterior box of the row's
+ * track after this row's update (the box of the start state for a track's first row), -1 beside a track of -1.  The rows of a
+ * frame that no clip covers get -1 / 0 / -1 / -1.  Degenerate boxes get no special case: the NaNs travel.  One workgroup per
+ * clip; the predicted boxes and the tracks' words in LDS; ws holds the length and maximum of every track made,
+ * VD_TRACK_SORT_WS_PER_ROW bytes per (frame, row), then two tables of filter states per clip, VD_TRACK_SORT_WS_PER_CLIP bytes.
+ * 1 <= N <= 128, F >= 1, F * N < 2^31, V >= 1, num_class >= 1, t_min >= 1, 0 <= max_age <= 7, no threshold NaN; bboxes and
+ * out_tbox 16-byte, every other pointer 4-byte aligned.  The inputs are never written.  No atomics, bit-reproducible.
+ * vd_track_sort_ws_bytes: the bytes ws must hold, -1 for sizes that are not taken. */
+#define VD_TRACK_SORT_WS_PER_ROW 8
+#define VD_TRACK_SORT_WS_PER_CLIP 139264
+int64_t vd_track_sort_ws_bytes(int V, int F, int N);
+int vd_track_sort(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
+                  int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
+                  int32_t* out_len, float* out_score, float* out_tbox, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

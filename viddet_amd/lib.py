@@ -19,6 +19,8 @@ SEQ_NMS_WS_PER_ROW = 48                             # vd_seq_nms: workspace byte
 TRACK_MAX_ROWS, TRACK_MAX_ACTIVE = 128, 1024        # vd_track: rows per frame, active tracks = rows * (max_age + 1) (vd_track.hip)
 TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes per (frame, row) (VD_TRACK_WS_PER_ROW)
 TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of one stream's state (VD_TRACK_STATE_BYTES)
+TRACK_SORT_WS_PER_ROW = 8                           # vd_track_sort: workspace bytes per (frame, row) (VD_TRACK_SORT_WS_PER_ROW)
+TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per clip, two tables of 17 x 1024 state floats
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 MOT_MAX_ROWS = 128                                  # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
@@ -205,6 +207,9 @@ SIGNATURES = {
     "vd_track": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _i64, _p]),
     # the same tracker resumable: the active tracks carried from launch to launch in a state block (vd_track_live.hip)
     "vd_track_push": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p, _i64, _p, _p, _p, _p]),
+    # the detections of video clips linked into tracks by SORT: Kalman prediction, optimal assignment (vd_track_sort.hip)
+    "vd_track_sort_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_track_sort": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     # tubelet rescoring and gap filling over the tracks of video clips (vd_tubelet.hip)
     "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
     "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),

@@ -131,7 +131,7 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
     seq = parse_seq_nms(seq_nms, net.post_nms, "detect_video")
     trk = parse_track(track, net.post_nms, "detect_video")
     tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
-    net.last_tracks = None
+    net.last_tracks = net.last_track_boxes = None
     net.last_tubelet = net.last_pre_tubelet = None
     if net._k > 1:
         net._stream_split()                                       # the graph's own word, before anything touches the GPU
@@ -156,7 +156,11 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         res = ids, scores, bboxes
     if trk is not None:
         boxes = res[2] if trk[1] is None else res[2].clamp(0, float(trk[1]))
-        net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if trk[2] == "sort":                                      # SORT: the triple as ever, the filtered boxes beside it
+            *links, net.last_track_boxes = ops.track_sort(res[0], res[1], boxes, num_class=num_class, **trk[0])
+            net.last_tracks = tuple(links)
+        else:
+            net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
         if tub_kw is not None:
             net.last_pre_tubelet = res[0], res[1], boxes          # the rows the tracker saw
             out_t = ops.tubelet(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **tub_kw)
@@ -186,7 +190,8 @@ class VideoSession:
     frames is pushed to an ops.TrackState; last_tracks = (track, tlen, tscore), each (m,post_nms), is track_online_host's
     triple for those frames: ids counted over the clip, lengths and maxima so far.  Nothing is decided online: sigma_h and
     t_min (kept in track_decide) are for track.finalize_tracks on the concatenated triples of the finished clip, which gives
-    detect_video(track=...)'s last_tracks.
+    detect_video(track=...)'s last_tracks.  The session carries the IOU tracker only: track={'method': 'sort'}
+    has no resumable form yet and raises NotImplementedError.
 
     Seq-NMS is not a session option: it takes the best path through ALL frames of a clip, removes it and starts again until no
     row is alive, so no frame is final before the clip ends - it has no online form.  Run detect_video(seq_nms=...) on the
@@ -207,7 +212,10 @@ class VideoSession:
         self._trk_kw = self._trk_clip = self._trk = None
         trk = parse_track(track, net.post_nms, "open_video")
         if trk is not None:
-            self._trk_kw, self._trk_clip = trk
+            if trk[2] != "iou":
+                raise NotImplementedError("open_video with track method %r: it has no resumable form yet, only 'iou' has "
+                                          "(run detect_video on the finished clip)" % (trk[2],))
+            self._trk_kw, self._trk_clip = trk[:2]
             self.track_decide = dict(sigma_h=self._trk_kw.pop("sigma_h"), t_min=self._trk_kw.pop("t_min"))
         if net._k > 1:
             net._stream_split()                                   # the graph's own word, before anything touches the GPU

@@ -659,6 +659,53 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
     return out_track, out_len, out_score
 
 
+def track_sort(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.3, t_min=2, max_age=1,
+               ws=None):
+    """vd_track_sort (viddet_amd/sort.py::sort_host on the device, bit for bit, DESIGN.md 34): SORT - Kalman prediction, optimal
+    assignment.  The inputs are ops.track's.  Returns (track, tlen, tscore, tbox), new device tensors: ops.track's three (F,N)
+    and tbox (F,N,4) fp32, the filtered box of the row's track after this row's update (-1 beside a track of -1).  Launches on
+    the current stream; nothing is downloaded and nothing waits.  ws: a uint8 device tensor of >= 8*F*N + 139264*V bytes to
+    reuse, else one is allocated."""
+    from .track import check_params
+    sl, sh, si, t_min, max_age = check_params(sigma_l, sigma_h, sigma_iou, t_min, max_age, "track_sort")
+    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("track_sort: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TRACK_MAX_ROWS:
+        raise ValueError("track_sort: N=%d rows per frame, vd_track_sort takes at most %d" % (N, L.TRACK_MAX_ROWS))
+    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("track_sort: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                             % (name, n, t.dtype, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("track_sort: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("track_sort: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_WS_PER_CLIP * V
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("track_sort: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    out_track = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    out_len = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    out_score = torch.empty(F, N, dtype=torch.float32, device=bboxes.device)
+    out_tbox = torch.empty(F, N, 4, dtype=torch.float32, device=bboxes.device)
+    if F == 0 or N == 0:
+        return out_track, out_len, out_score, out_tbox
+    check(_lib().vd_track_sort(ptr(ids), ptr(scores), ptr(bboxes), ptr(clip_start), V, F, N, int(num_class), float(sl), float(sh),
+                               float(si), t_min, max_age, ptr(out_track), ptr(out_len), ptr(out_score), ptr(out_tbox), ptr(ws),
+                               int(ws.numel()), _s()), "vd_track_sort")
+    return out_track, out_len, out_score, out_tbox
+
+
 def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="avg", max_gap=7, drop_untracked=False, ws=None,
             stages=None):
     """vd_tubelet (viddet_amd/tubelet.py::tubelet_host on the device, bit for bit, DESIGN.md 32): ids (F,N[,1]), scores (F,N[,1])

@@ -146,18 +146,19 @@ def conv_fwd(x, wp, out, *, k, stride, pad, Co, ldo=None, scale=None, shift=None
 
 
 def conv_igemm_bf16(x, wb, out, *, N, Hi, Wi, Ci, Hg, Wg, in_stride, taps, Ho, Wo, Co, ldo, out_stride=1, out_oy=0, out_ox=0,
-                    scale=None, shift=None, residual=None, ldr=0, leaky=False, slope=0.1, tile=0, stats_part=None, nohalo=False,
+                    scale=None, shift=None, residual=None, ldr=0, leaky=False, slope=0.1, kfr=1, tile=0, stats_part=None, nohalo=False,
                     streamk_ws=None, splitk=False):
     """vd_conv_igemm_bf16: x / wb / residual bf16, out bf16 or fp32 (by its dtype); any output geometry; stats_part =
     fused BatchNorm statistics table [mtiles][2 * Co] (conv_bf16_mtiles).  streamk_ws: VD_CONV_STREAMK (bit-identical);
-    splitk=True with it: VD_CONV_SPLITK too (launches with too few tiles for the chip are cut along K)."""
+    splitk=True with it: VD_CONV_SPLITK too (launches with too few tiles for the chip are cut along K).  kfr: frames per
+    window of a conv with frame taps (dz != 0); a tap that leaves its window reads zeros."""
     d = ConvDesc()
     d.tile = tile
     d.in_, d.wp, d.out = ptr(x), ptr(wb), ptr(out)
     d.scale, d.shift, d.residual = ptr(scale), ptr(shift), ptr(residual)
     d.N, d.Hi, d.Wi, d.Ci, d.Hg, d.Wg, d.in_stride = N, Hi, Wi, Ci, Hg, Wg, in_stride
     _set_taps(d, taps)
-    d.Kfr, d.Ho, d.Wo, d.Co = 1, Ho, Wo, Co
+    d.Kfr, d.Ho, d.Wo, d.Co = kfr, Ho, Wo, Co
     d.out_stride, d.out_oy, d.out_ox, d.ldo, d.ldr = out_stride, out_oy, out_ox, ldo, ldr
     d.flags = (EPI_AFFINE if (scale is not None or shift is not None) else 0) | (EPI_LEAKY if leaky else 0) | \
               (EPI_RESIDUAL if residual is not None else 0) | (MATH_NOHALO if nohalo else 0)

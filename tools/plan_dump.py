@@ -52,7 +52,10 @@ def main():
     ap.add_argument("--conv-types", default=None, help="e.g. 21,21,2,2,2,2 with --k 3: yolo3_3ddarknet (the TdwNode passes)")
     ap.add_argument("--noback", action="store_true")
     ap.add_argument("--freeze-base", action="store_true")
-    ap.add_argument("--range-exact", action="store_true", help="two tensors in net._range_exact")
+    ap.add_argument("--range-exact", action="store_true",
+                    help="two tensors in net._range_exact, closed over the tensors derived from them (concat, pool, select, add)")
+    ap.add_argument("--range-exact-also", default=None, metavar="TENSOR",
+                    help="with --range-exact: one more tensor by name, e.g. n0.tr - the records behind n0.cat then leave the fp16 split")
     ap.add_argument("--syncbn", default=None, choices=["all", "reference"],
                     help="SyncBN on a one-rank gloo group (VD_FORCE_DIST=1 puts the exchanges in the plan)")
     ap.add_argument("--expect-tuned", type=int, default=None)
@@ -83,7 +86,9 @@ def main():
                                 **(dict(rnn_pos=a.rnn_pos) if a.rnn_pos else {}), **norm)   # (only when asked: older revisions have no such argument)
     if a.range_exact:
         bn = [n for n in net.conv_nodes if n.bn]
-        net._range_exact.update([bn[3].dst, "dz:" + bn[6].name])
+        net._range_exact.update([bn[3].dst, "dz:" + bn[6].name] + ([a.range_exact_also] if a.range_exact_also else []))
+        if hasattr(net, "_close_range_exact"):     # the rule covers what is derived from a flagged tensor: the outputs of
+            net._close_range_exact()               # concatenations, temporal pools, frame selections and adds behind it
     B, H = a.batch, a.size
     cuda = net.device.type == "cuda"
     extra = {}                      # further named tensors of the plan

@@ -1319,12 +1319,11 @@ class YOLOV3(object):
         # tensor is dense; those join this set through check_operand_ranges() when their channel scales spread too far.
         self._range_exact = set('dz:' + n.name for n in self.conv_nodes if n.head)
         # A correlation join's output mixes frame features with cost-volume maps (products of two features / C): no single
-        # BatchNorm bounds its channel scales, and the guard does not follow derived tensors.  So the convs that read it -
-        # directly or through the concatenation behind a transition - are range-exact by construction as well (forward and
-        # weight gradient: both take it as their operand).
-        corr_t = {n.dst for n in self.nodes if isinstance(n, CorrNode)}
-        corr_t |= {n.dst for n in self.nodes if isinstance(n, UpcatNode) and n.route in corr_t}
-        self._range_exact |= corr_t
+        # BatchNorm bounds its channel scales.  So the convs that read it - directly or through the concatenation behind a
+        # transition, which the closure below reaches - are range-exact by construction as well (forward and weight
+        # gradient: both take it as their operand).
+        self._range_exact |= {n.dst for n in self.nodes if isinstance(n, CorrNode)}
+        self._close_range_exact()
         self._guard = None
         # arena layout: [conv weights (fwd-packed) | bn gamma, beta, head bias]  -> wd / no_wd ranges
         off = 0
@@ -1692,24 +1691,67 @@ class YOLOV3(object):
             return None
         return bufs['amax:' + name].data_ptr()
 
+    def _close_range_exact(self):
+        """Close `_range_exact` over the tensors that only re-arrange a range-exact one: the output of a concatenation, a
+        temporal pool (max / mean / channel stacking), a frame selection or an add carries its sources' channels on, so it
+        is range-exact as soon as ANY source is - the conv behind `n0.cat` reads the very channels the guard flagged in
+        `n0.tr`.  One walk in node order (a source is produced before its reader).  A ConvNode's fused residual is NOT
+        followed: the cell's dst is leaky(bn(z)) + residual, a tensor with a BatchNorm of its own, which the guard
+        examines itself (the same holds for a TdwNode's residual: its operand name is the guard's for that cell).
+        Returns the nodes whose dst joined, in node order."""
+        added = []
+        for n in self.nodes:
+            if isinstance(n, (UpcatNode, PoolNode, SelNode, AddNode)) and n.dst not in self._range_exact and \
+                    any(t in self._range_exact for t in node_inputs(n)):
+                self._range_exact.add(n.dst)
+                added.append(n)
+        return added
+
+    def _concat_ranges(self, ups, thresh, ratios, flags, at):
+        """The guard's second source: a concatenation whose two sides differ in SCALE with no BatchNorm vector showing it
+        (every channel of the transition uniformly small against the route: two flat vectors, and the merged max-abs slot
+        keeps the larger side only).  For each UpcatNode of `ups`: min / max of the two sources' max-abs (each reduced over
+        its sub-slots) into ratios[at + j], the flag (ratio < thresh) into flags[at + j] - on the device, read with the
+        guard's flags.  The slots are those of the last fp32 training step; without one, and for a side that is all zeros
+        (nothing to lose: zero is staged exactly), nothing is flagged."""
+        flags[at:].zero_()
+        ratios[at:].fill_(1.0)
+        tp = getattr(self, '_last_train', None)
+        if not ups or tp is None or tp.get('storage', 'fp32') != 'fp32':
+            return
+        bufs = tp['bufs']
+        side = lambda t: bufs['amax:' + t].view(-1)[::L.AMAX_STRIDE][:L.AMAX_SLOTS].max()
+        for j, n in enumerate(ups):
+            if n.dst in self._range_exact:
+                continue
+            a, b = side(n.up), side(n.route)
+            lo, hi = torch.minimum(a, b), torch.maximum(a, b)
+            ratios[at + j] = torch.where(lo > 0, lo / hi.clamp_min(1e-37), torch.ones_like(lo))
+            flags[at + j] = ((lo > 0) & (lo < thresh * hi)).to(torch.int32)
+
     def check_operand_ranges(self, thresh=2.0 ** -16):
         """The data-driven half of the fp16 split's range rule (include/viddet_hip.h vd_range_guard).  One
-        small launch over the BatchNorm vectors of the network, then a read of its flags (synchronises: call it where the
-        host waits anyway - train_yolov3.py does at every log line).  A tensor whose per-channel scales spread over more
-        than 1 / thresh joins `_range_exact`; the plans are dropped and rebuilt with the range-exact arithmetic for its
-        consumers.  Returns {tensor name: min / max channel-scale ratio} of the newly flagged tensors."""
+        small launch over the BatchNorm vectors of the network, the max-abs ratio of every concatenation's two sides
+        (_concat_ranges), then a read of the flags (synchronises: call it where the host waits anyway - train_yolov3.py does
+        at every log line).  A tensor whose per-channel scales spread over more than 1 / thresh joins `_range_exact`, and
+        with it every tensor derived from it (_close_range_exact); the plans are dropped and rebuilt with the range-exact
+        arithmetic for their consumers.  Returns {tensor name: min / max channel-scale ratio} of the newly flagged tensors;
+        a derived tensor carries the smallest ratio of the sources that brought it in."""
         bn = [n for n in self.conv_nodes if n.bn]
         if not bn:
             return {}
+        ups = [n for n in self.nodes if isinstance(n, UpcatNode)]
         if getattr(self, '_guard', None) is None:
             arr = (L.GuardItem * len(bn))()
             for i, n in enumerate(bn):
                 arr[i].gamma, arr[i].beta, arr[i].scale, arr[i].C = n.gamma.data_ptr(), n.beta.data_ptr(), n.b_scale.data_ptr(), n.cout
             items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
-            self._guard = (items, torch.zeros(2 * len(bn), device=self.device), torch.zeros(2 * len(bn), dtype=torch.int32, device=self.device))
+            nf = 2 * len(bn) + len(ups)                    # [per BatchNorm: activation, gradient | per concatenation]
+            self._guard = (items, torch.zeros(nf, device=self.device), torch.zeros(nf, dtype=torch.int32, device=self.device))
         items, ratios, flags = self._guard
         L.check(L.load().vd_range_guard(items.data_ptr(), len(bn), float(thresh), ratios.data_ptr(), flags.data_ptr(), L.stream_ptr()),
                 'vd_range_guard')
+        self._concat_ranges(ups, float(thresh), ratios, flags, 2 * len(bn))
         if torch.distributed.is_available() and torch.distributed.is_initialized() and \
                 torch.distributed.get_world_size(self.process_group) > 1:
             # every rank takes the union: without SyncBN the ranks' invstd differ, and the ranks must run the same plans
@@ -1725,8 +1767,15 @@ class YOLOV3(object):
                     continue
                 if fl[2 * i + k] and name not in self._range_exact:
                     new[name] = float(ra[2 * i + k])
+        for j, n in enumerate(ups):
+            if fl[2 * len(bn) + j] and n.dst not in self._range_exact:
+                new[n.dst] = float(ra[2 * len(bn) + j])
         if new:
             self._range_exact.update(new)
+            # the derived tensors that join with them, so that the caller's log line names every tensor that moved (the set
+            # was closed before this call, so each of them has a source among the new names)
+            for n in self._close_range_exact():
+                new[n.dst] = min(new[t] for t in node_inputs(n) if t in new)
             self._drop_plans()
         return new
 

@@ -28,7 +28,10 @@ an interpolated box - and writes the rows after it beside everything else, under
 (with --track; no reference counterpart) scores every tracked twin with the MOT tracking metric (viddet_amd/mot_metric.py: MOTA,
 MOTP, id switches, fragmentations, IDF1, ... against the track ids of SyntheticTracks) on the rows read back from the
 twin's files, and writes mot.txt / mot_seq.txt / mot_tub.txt; `--device_metric` with the per-frame matching on the device
-(vd_mot_match).  Visualisation and the worst-video tool are out of scope.
+(vd_mot_match).  `--metrics hota` (with --track; no reference counterpart) scores the same rows with the HOTA tracking metric
+(viddet_amd/hota_metric.py: HOTA, DetA, AssA, LocA, ... over 19 localisation thresholds) and writes hota.txt /
+hota_seq.txt / hota_tub.txt; `--device_metric` with the per-frame matching on the device (vd_hota_match).  Visualisation and the
+worst-video tool are out of scope.
 """
 import argparse
 import os
@@ -47,6 +50,7 @@ from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticTrac
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.vid_metric import VIDDetectionMetric
 from viddet_amd.coco_metric import COCODetectionMetric
+from viddet_amd.hota_metric import HOTAMetric
 from viddet_amd.mot_metric import MOTMetric
 from viddet_amd.hierarchy import ClassTree, get_class_map, hierarchical_nms, iou  # noqa: F401  (detect_yolo3.py:698-789)
 from viddet_amd.model import yolo3_darknet53, yolo3_3ddarknet, check_conv_types
@@ -118,7 +122,8 @@ def parse_flags(argv=None):
       help="(no reference counterpart) --metrics vid and --metrics coco match detections and ground truth on the GPU (vd_vid_match, "
            "vd_coco_match: one workgroup per image; DeviceVIDDetectionMetric, DeviceCOCODetectionMetric): the same vid.txt / "
            "coco.txt as the host metrics write (DESIGN.md 25, 26).  --metrics mot likewise (vd_mot_match: one workgroup per clip; "
-           "DeviceMOTMetric): the same mot.txt (DESIGN.md 33)")
+           "DeviceMOTMetric): the same mot.txt (DESIGN.md 33).  --metrics hota likewise (vd_hota_match: a workgroup per frame; "
+           "DeviceHOTAMetric): the same hota.txt (DESIGN.md 35)")
     A("--seq_nms", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) sequence NMS (Han et al. 2016) over the detections of every clip, on the device "
            "(vd_seq_nms): boxes of adjacent frames are linked, the best sequence's rows take its score, what overlaps them is "
@@ -424,6 +429,16 @@ def check_flags(FLAGS):
                                       "clips and no ground-truth tracks")
         if getattr(FLAGS, "mult_out", False):
             raise NotImplementedError("--metrics mot does not combine with --mult_out: its rows are not the detections of one frame")
+    hota = "hota" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
+    if hota:
+        # the HOTA metric scores the same tracks against the same ground-truth tracks: refused where mot is
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--metrics hota needs --track: it scores the tracks of the tracked prediction sets (pred_trk, ...)")
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--metrics hota does not combine with several --dataset names: the combined set has no "
+                                      "clips and no ground-truth tracks")
+        if getattr(FLAGS, "mult_out", False):
+            raise NotImplementedError("--metrics hota does not combine with --mult_out: its rows are not the detections of one frame")
     if getattr(FLAGS, "seq_nms", False):
         # Seq-NMS links the frames of a clip: a set without clips has nothing to link
         if len(FLAGS.dataset) > 1:
@@ -502,16 +517,16 @@ def check_flags(FLAGS):
     coco = "coco" in [m.lower() for m in (getattr(FLAGS, "metrics", None) or [])]
     if FLAGS.model_agnostic:
         FLAGS.metric_agnostic = True                      # detect_yolo3.py:797-798
-    elif FLAGS.metric_agnostic and not (vid or mot):
+    elif FLAGS.metric_agnostic and not (vid or mot or hota):
         raise NotImplementedError("--metric_agnostic without --model_agnostic only acts inside VIDDetectionMetric and MOTMetric "
-                                  "(detect_yolo3.py:189-190): it needs --metrics vid or --metrics mot, the voc metric takes no "
-                                  "agnostic argument")
+                                  "(detect_yolo3.py:189-190): it needs --metrics vid or --metrics mot (or --metrics hota: "
+                                  "HOTAMetric), the voc metric takes no agnostic argument")
     if vid and len(FLAGS.dataset) > 1:
         raise NotImplementedError("--metrics vid does not combine with several --dataset names: the combined set has no "
                                   "tracks, so no motion IoUs")
-    if getattr(FLAGS, "device_metric", False) and not (vid or coco or mot):
-        raise NotImplementedError("--device_metric acts on --metrics vid, --metrics coco and --metrics mot only (train_yolov3.py "
-                                  "has the voc metric's)")
+    if getattr(FLAGS, "device_metric", False) and not (vid or coco or mot or hota):
+        raise NotImplementedError("--device_metric acts on --metrics vid, --metrics coco, --metrics mot and --metrics hota only "
+                                  "(train_yolov3.py has the voc metric's)")
     # detect_yolo3.py:795,872-882: conv_types[0] != 2 selects yolo3_3ddarknet(classes, conv_types=...) and nothing else
     ct = check_conv_types(FLAGS.conv_types, FLAGS.window[0])
     if ct is not None:
@@ -645,8 +660,8 @@ def main(argv=None):
     fmt = dict(frame_format="nv12", yuv_matrix=FLAGS.yuv_matrix, yuv_range=FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else {}
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
-    elif {"vid", "mot"} & {m.lower() for m in FLAGS.metrics}:
-        # the vid and mot metrics need tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
+    elif {"vid", "mot", "hota"} & {m.lower() for m in FLAGS.metrics}:
+        # the vid, mot and hota metrics need tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
         dataset = SyntheticTracks(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
                                   frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
                                   step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1, **fmt)
@@ -740,7 +755,8 @@ def main(argv=None):
                           seq=True)
     if trk is not None:
         # the tracked twins, after everything a run without --track writes: pred_trk / tracks.txt, pred_seq_trk / tracks_seq.txt
-        # (and with --metrics mot their mot.txt / mot_seq.txt; the plain twin's is what main() returns where no other metric ran)
+        # (and with --metrics mot / hota their mot.txt / mot_seq.txt, hota.txt / hota_seq.txt; the plain twin's - mot's where
+        # both ran - is what main() returns where no other metric ran)
         for bx, tr, is_seq in ((boxes, tracks, False), (boxes_seq, tracks_seq, True)):
             if bx is not None:
                 mot_result = save_tracks(FLAGS, dataset, bx, tr, is_seq)
@@ -776,18 +792,31 @@ def save_tracks(FLAGS, dataset, boxes, tracks, seq=False, tub=False):
     with open(out, "w") as f:
         for v, (ids, rows) in enumerate(per_clip):
             f.write("{} {} {} {:.4f}\n".format(v, len(ids), rows, rows / len(ids) if ids else 0.0))
-    if "mot" not in [m.lower() for m in FLAGS.metrics]:
+    metrics = [m.lower() for m in FLAGS.metrics]
+    if "mot" not in metrics and "hota" not in metrics:
         return None
-    # --metrics mot: what is scored is what is on disk - the rows read back from the twin's files
-    if FLAGS.device_metric:
-        from viddet_amd.device_mot_metric import DeviceMOTMetric as mot_class
-    else:
-        mot_class = MOTMetric
-    result = evaluate_tracks(mot_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset,
-                             load_tracked_predictions(save_dir, dataset, FLAGS.max_do))
-    # mot.txt / mot_seq.txt / mot_tub.txt, mot_ag*.txt under --model_agnostic, mot_ag_met*.txt under --metric_agnostic alone
-    write_results(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
-                               result_name("mot", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"), *result)
+    # --metrics mot / hota: what is scored is what is on disk - the rows read back from the twin's files
+    preds = load_tracked_predictions(save_dir, dataset, FLAGS.max_do)
+    result = None
+    if "mot" in metrics:
+        if FLAGS.device_metric:
+            from viddet_amd.device_mot_metric import DeviceMOTMetric as mot_class
+        else:
+            mot_class = MOTMetric
+        result = evaluate_tracks(mot_class(dataset, iou_thresh=0.5, agnostic=FLAGS.metric_agnostic), dataset, preds)
+        # mot.txt / mot_seq.txt / mot_tub.txt, mot_ag*.txt under --model_agnostic, mot_ag_met*.txt under --metric_agnostic alone
+        write_results(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
+                                   result_name("mot", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"), *result)
+    if "hota" in metrics:
+        if FLAGS.device_metric:
+            from viddet_amd.device_hota_metric import DeviceHOTAMetric as hota_class
+        else:
+            hota_class = HOTAMetric
+        hota_result = evaluate_tracks(hota_class(dataset, agnostic=FLAGS.metric_agnostic), dataset, preds)
+        # hota.txt / hota_seq.txt / hota_tub.txt, hota_ag*.txt, hota_ag_met*.txt: named as mot's
+        write_results(os.path.join(FLAGS.save_dir, FLAGS.save_prefix,
+                                   result_name("hota", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"), *hota_result)
+        result = hota_result if result is None else result
     return result
 
 

@@ -891,6 +891,34 @@ int vd_track_sort(const float* ids, const float* scores, const float* bboxes, co
                   int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
                   int32_t* out_len, float* out_score, float* out_tbox, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The per-frame matching of the HOTA tracking metric (vd_hota_eval.hip): what
+ * viddet_amd.hota_metric.hota_match_host computes, bit for bit, on all three outputs - Luiten et al., "HOTA: A Higher Order
+ * Metric for Evaluating Multi-Object Tracking" (IJCV 2021).  The inputs are vd_mot_match's; the ids are dense: a ground-truth row
+ * is eligible iff gt_cls >= 0 and 0 <= gt_id < A (A <= 1024), a prediction row iff it is a candidate of vd_seq_nms and
+ * 0 <= track < P; an eligible row is a candidate iff no lower eligible row of its frame carries its id.  Per clip [t0, t1):
+ *   1. q[g][j] = int(iou * 2^20) (vd_seq_nms's fp32 IoU; a NaN counts as 0) where both rows are candidates and (agnostic or the
+ *      classes are equal), else 0; a pair is admissible iff q > 0;
+ *   2. over all frames of the clip, in integers: with rq / cq the row and column sums of q in the frame,
+ *      pm[a][p] += (q << 20) / (rq[g] + cq[j] - q) per admissible pair of ids (a, p); cg[a], cp[p]: the candidate rows of an id;
+ *   3. A[a][p] = (pm << 20) / (((cg[a] + cp[p]) << 20) - pm), 0 where pm is 0;
+ *   4. every frame on its own: the score of an admissible pair is s = (A[a][p] * q) >> 20; the minimum-cost assignment of the
+ *      ground-truth candidates (row order) to the prediction candidates (row order) at cost 2^20 - s, a dummy column per row at
+ *      2^20, is vd_mot_match's - successive shortest augmenting paths with int64 potentials, among columns of equal least
+ *      slack the lowest; entered only when both pools hold a row;
+ *   5. match [F][G] int32: the prediction row, -1 an unmatched candidate, -2 no candidate; msim [F][G]: the pair's IoU, else 0;
+ *      mscore [F][G] int32: the pair's s, else 0.
+ * All three outputs are written in full; the rows of a frame that no clip covers get -2 / 0 / 0.  ws holds pm [V][A][P] int64,
+ * then cg [V][A] and cp [V][P] int32; it is cleared by the first launch, whatever it held.  Three launches: clear; pass 2 with a
+ * workgroup per frame (integer atomicAdd on ws: sums of integers, bit-reproducible); pass 4 with a workgroup per frame.
+ * 1 <= G, N <= 128, 1 <= F <= 2^22, V >= 1, 1 <= A <= 1024, P >= 1, num_class >= 1, agnostic 0 or 1; gt_boxes and bboxes 16-byte,
+ * ws 8-byte, every other pointer 4-byte aligned.  The inputs are never written.  vd_hota_ws_bytes: the bytes ws must hold,
+ * V * (8 * A * P + 4 * A + 4 * P), -1 for sizes that are not taken. */
+int64_t vd_hota_ws_bytes(int V, int A, int P);
+int vd_hota_match(const float* gt_boxes, const int32_t* gt_cls, const int32_t* gt_id, const float* ids, const float* scores,
+                  const float* bboxes, const int32_t* track, const int32_t* clip_start, int V, int F, int G, int N, int A, int P,
+                  int num_class, int agnostic, int32_t* match, float* msim, int32_t* mscore, void* ws, int64_t ws_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,8 @@ TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 MOT_MAX_ROWS = 128                                  # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
 MOT_WS_PER_ROW = 4                                  # vd_mot_match: workspace bytes per (frame, row) of either side (VD_MOT_WS_PER_ROW)
+HOTA_MAX_GT_IDS = 1024                              # vd_hota_match: dense ground-truth ids per clip (vd_hota_eval.hip)
+HOTA_MAX_FRAMES = 1 << 22                           # vd_hota_match: frames of one call
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -217,6 +219,9 @@ SIGNATURES = {
     # the per-frame matching of the MOT tracking metric on the device (vd_mot_eval.hip)
     "vd_mot_match_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_mot_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    # the per-frame matching of the HOTA tracking metric on the device (vd_hota_eval.hip)
+    "vd_hota_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_hota_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

@@ -830,6 +830,80 @@ def mot_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, clip_start=No
     return match, miou, flags, adm
 
 
+def hota_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, num_gt_id, num_track, clip_start=None, num_class=1,
+               agnostic=False, ws=None):
+    """vd_hota_match (viddet_amd/hota_metric.py::hota_match_host on the device, bit for bit, DESIGN.md 35): the tensors and
+    clip_start as ops.mot_match takes them, with dense ids: a label row takes part iff 0 <= gt_id < num_gt_id (A, at most 1024),
+    a prediction row iff 0 <= track < num_track (P); rows outside are no candidates, as rows with the id -1 are for the host
+    definition.  Returns (match (F,G) int32, msim (F,G) fp32, mscore (F,G) int32), new device tensors.  Launches on the current
+    stream; nothing is downloaded and nothing waits.  ws: a uint8 device tensor of >= hota_ws_bytes(V, A, P) bytes to reuse
+    (whatever it holds), else one is allocated."""
+    if type(agnostic).__name__ not in ("bool", "bool_"):
+        raise ValueError("hota_match: agnostic must be a bool, got %r" % (agnostic,))
+    for name, t in (("gt_boxes", gt_boxes), ("bboxes", bboxes)):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[-1] != 4:
+            raise ValueError("hota_match: %s must be (F,%s,4), got %r" % (name, "G" if name == "gt_boxes" else "N", tuple(getattr(t, "shape", ()))))
+    F, G, N = int(gt_boxes.shape[0]), int(gt_boxes.shape[1]), int(bboxes.shape[1])
+    if int(bboxes.shape[0]) != F:
+        raise ValueError("hota_match: gt_boxes holds %d frames, bboxes %d" % (F, int(bboxes.shape[0])))
+    if F > L.HOTA_MAX_FRAMES:
+        raise ValueError("hota_match: gt_boxes holds F=%d frames, vd_hota_match takes at most %d" % (F, L.HOTA_MAX_FRAMES))
+    if not 1 <= G <= L.MOT_MAX_ROWS:
+        raise ValueError("hota_match: gt_boxes holds G=%d label rows per frame, vd_hota_match takes 1 to %d" % (G, L.MOT_MAX_ROWS))
+    if not 1 <= N <= L.MOT_MAX_ROWS:
+        raise ValueError("hota_match: bboxes holds N=%d prediction rows per frame, vd_hota_match takes 1 to %d" % (N, L.MOT_MAX_ROWS))
+    for name, v, hi in (("num_gt_id", num_gt_id, L.HOTA_MAX_GT_IDS), ("num_track", num_track, 2 ** 31 - 1), ("num_class", num_class, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
+            raise ValueError("hota_match: %s must be an integer in [1, %d], got %r" % (name, hi, v))
+    A, P = int(num_gt_id), int(num_track)
+    f32, i32 = torch.float32, torch.int32
+    for name, t, n, dt in (("gt_boxes", gt_boxes, F * G * 4, f32), ("gt_cls", gt_cls, F * G, i32), ("gt_id", gt_id, F * G, i32),
+                           ("ids", ids, F * N, f32), ("scores", scores, F * N, f32), ("bboxes", bboxes, F * N * 4, f32),
+                           ("track", track, F * N, i32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("hota_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    for name, t, shape in (("gt_cls", gt_cls, (F, G)), ("gt_id", gt_id, (F, G)), ("track", track, (F, N))):
+        if tuple(t.shape) != shape:
+            raise ValueError("hota_match: %s must be %r, got %r" % (name, shape, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("hota_match: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("hota_match: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = hota_ws_bytes(V, A, P)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda \
+            or ws.data_ptr() % 8:
+        raise ValueError("hota_match: ws must be a contiguous, 8-byte aligned uint8 device tensor of >= %d bytes" % need)
+    dev = bboxes.device
+    match = torch.empty(F, G, dtype=i32, device=dev)
+    msim = torch.empty(F, G, dtype=f32, device=dev)
+    mscore = torch.empty(F, G, dtype=i32, device=dev)
+    if F == 0:
+        return match, msim, mscore
+    check(_lib().vd_hota_match(ptr(gt_boxes), ptr(gt_cls), ptr(gt_id), ptr(ids), ptr(scores), ptr(bboxes), ptr(track), ptr(clip_start),
+                               V, F, G, N, A, P, int(num_class), int(bool(agnostic)), ptr(match), ptr(msim), ptr(mscore), ptr(ws),
+                               int(ws.numel()), _s()), "vd_hota_match")
+    return match, msim, mscore
+
+
+def hota_ws_bytes(V, num_gt_id, num_track):
+    """the bytes of vd_hota_match's workspace for V clips: V * (8 * A * P + 4 * A + 4 * P); ValueError beyond what is taken"""
+    V, A, P = int(V), int(num_gt_id), int(num_track)
+    if V < 1 or not 1 <= A <= L.HOTA_MAX_GT_IDS or not 1 <= P <= 2 ** 31 - 1 or V > 2 ** 31 - 1 or V * (8 * A * P + 4 * A + 4 * P) >= 2 ** 47:
+        raise ValueError("hota_match: a workspace for V=%d clips, num_gt_id=%d and num_track=%d is beyond what is taken" % (V, A, P))
+    return V * (8 * A * P + 4 * A + 4 * P)
+
+
 class TrackState:
     """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
     device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -

@@ -20,7 +20,8 @@ predictions and results are written as without it, the rescored ones beside them
 reference counterpart) links the detections of every clip into tracks on the device (vd_track): every prediction
 set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
 clip; everything else is written as without the flag; `--track_method sort` links them with SORT instead (vd_track_sort, DESIGN.md
-34; not with --live).  `--live` (with --stream; no reference counterpart) sends every clip
+34; not with --live), `--track_method byte` with BYTE, SORT with a second association of the low-score rows (vd_track_byte,
+DESIGN.md 36; not with --live).  `--live` (with --stream; no reference counterpart) sends every clip
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
 the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
 pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
@@ -146,20 +147,30 @@ def parse_flags(argv=None):
            "those of --stream byte for byte, --track included (its online ids are decided at the clip's end).  Not with "
            "--seq_nms, which has no online form")
     A("--live_push", type=int, default=1, help="--live: frames per push (default 1)")
-    A("--track_method", default="iou", choices=["iou", "sort"],
-      help="--track: iou (the default, vd_track) or sort (vd_track_sort, DESIGN.md 34): SORT of Bewley et al. 2016 - every track is "
+    A("--track_method", default="iou", choices=["iou", "sort", "byte"],
+      help="--track: iou (the default, vd_track), sort (vd_track_sort, DESIGN.md 34): SORT of Bewley et al. 2016 - every track is "
            "predicted by a constant-velocity Kalman filter and the predictions are matched to the frame's boxes by an optimal "
-           "assignment, so a track survives missed frames of a moving object and crossing objects keep their ids.  The same files "
-           "are written.  Not with --live")
+           "assignment, so a track survives missed frames of a moving object and crossing objects keep their ids - or byte "
+           "(vd_track_byte, DESIGN.md 36): BYTE of Zhang et al. 2022 - SORT with two associations a frame: the boxes scored at "
+           "least --track_det first, then the tracks left over against the lower-scored boxes, which never start a track, so a "
+           "track survives a dip of its object's score and low-score clutter starts none.  The same files are written.  sort and "
+           "byte: not with --live")
     A("--track_iou", type=float, default=None,
-      help="--track: a box joins a track where its IoU to the track's last box (sort: its predicted box) is at least this "
-           "(default: iou 0.5, sort 0.3)")
-    A("--track_low", type=float, default=0.0, help="--track: detections scored below this take no part")
+      help="--track: a box joins a track where its IoU to the track's last box (sort, byte: its predicted box) is at least this "
+           "(default: iou 0.5, sort 0.3, byte 0.2)")
+    A("--track_low", type=float, default=None,
+      help="--track: detections scored below this take no part (default: iou and sort 0.0, byte 0.1)")
+    A("--track_det", type=float, default=None,
+      help="--track_method byte: a detection scored at least this is a high-score box, matched first (default 0.5)")
+    A("--track_new", type=float, default=None,
+      help="--track_method byte: an unmatched high-score box starts a track where its score is at least this (default 0.6)")
+    A("--track_iou2", type=float, default=None,
+      help="--track_method byte: the IoU threshold of the second association, low-score boxes against the tracks left over (default 0.5)")
     A("--track_high", type=float, default=0.5, help="--track: a track is kept where its best score is at least this")
     A("--track_min_len", type=int, default=2, help="--track: a track is kept where it holds at least this many boxes")
     A("--track_max_age", type=int, default=None,
       help="--track: the frames in a row a track may go without a box before it is closed, 0 to 7 (default: iou 0, sort 1, "
-           "the papers' values)")
+           "the papers' values; byte 7)")
     A("--tubelet", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) with --track: a tubelet pass over every tracked clip on the device (vd_tubelet): the rows "
            "of a track take the track's score, the frames a track skipped get a linearly interpolated box, every frame is "
@@ -174,16 +185,27 @@ def parse_flags(argv=None):
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
     FLAGS = ap.parse_args(argv)
-    # --track_iou / --track_max_age left out: the linking method's own defaults (iou: 0.5 and 0, sort: 0.3 and 1)
-    if FLAGS.track_method == "sort":
-        from viddet_amd.sort import DEFAULTS as track_defaults
-    else:
-        from viddet_amd.track import DEFAULTS as track_defaults
-    if FLAGS.track_iou is None:
-        FLAGS.track_iou = track_defaults["sigma_iou"]
-    if FLAGS.track_max_age is None:
-        FLAGS.track_max_age = track_defaults["max_age"]
+    # --track_iou / --track_max_age / --track_low left out: the linking method's own defaults (iou: 0.5, 0 and 0.0, sort: 0.3, 1
+    # and 0.0, byte: 0.2, 7 and 0.1); byte's own three flags stay None beside another method, where check_flags refuses them
+    track_defaults = _track_defaults(FLAGS.track_method)
+    for flag, key in (("track_iou", "sigma_iou"), ("track_max_age", "max_age"), ("track_low", "sigma_l")) + _BYTE_FLAGS:
+        if getattr(FLAGS, flag) is None and key in track_defaults:
+            setattr(FLAGS, flag, track_defaults[key])
     return FLAGS
+
+
+_BYTE_FLAGS = (("track_det", "sigma_d"), ("track_new", "sigma_new"), ("track_iou2", "sigma_iou2"))   # --track_method byte's own
+
+
+def _track_defaults(method):
+    """the DEFAULTS of a --track_method"""
+    if method == "sort":
+        from viddet_amd.sort import DEFAULTS
+    elif method == "byte":
+        from viddet_amd.byte import DEFAULTS
+    else:
+        from viddet_amd.track import DEFAULTS
+    return DEFAULTS
 
 
 def _collect(boxes, dataset, ids, scores, bboxes, sidxs, W):
@@ -207,25 +229,30 @@ def seq_nms_args(FLAGS):
 
 def track_args(FLAGS):
     """the dict net.detect_video and link_rows take, None without --track: ops.track's parameters and, with --track_method
-    sort, `method`; --track_iou and --track_max_age left out take the method's defaults (iou: 0.5 and 0, sort: 0.3 and 1)"""
+    sort or byte, `method` (byte: sigma_d, sigma_new and sigma_iou2 too); --track_iou, --track_max_age and --track_low left out
+    take the method's defaults (iou: 0.5, 0 and 0.0, sort: 0.3, 1 and 0.0, byte: 0.2, 7 and 0.1)"""
     if not getattr(FLAGS, "track", False):
         return None
     method = getattr(FLAGS, "track_method", "iou")
-    if method == "sort":
-        from viddet_amd.sort import DEFAULTS
-    else:
-        from viddet_amd.track import DEFAULTS
-    iou, age = getattr(FLAGS, "track_iou", None), getattr(FLAGS, "track_max_age", None)
-    args = dict(sigma_iou=DEFAULTS["sigma_iou"] if iou is None else iou, sigma_l=FLAGS.track_low, sigma_h=FLAGS.track_high,
-                t_min=FLAGS.track_min_len, max_age=DEFAULTS["max_age"] if age is None else age)
+    DEFAULTS = _track_defaults(method)
+
+    def given(flag, key):
+        v = getattr(FLAGS, flag, None)
+        return DEFAULTS[key] if v is None else v
+
+    args = dict(sigma_iou=given("track_iou", "sigma_iou"), sigma_l=given("track_low", "sigma_l"), sigma_h=FLAGS.track_high,
+                t_min=FLAGS.track_min_len, max_age=given("track_max_age", "max_age"))
+    if method == "byte":
+        args.update({key: given(flag, key) for flag, key in _BYTE_FLAGS})
     return dict(args, method=method) if method != "iou" else args
 
 
 def link_rows(ids, scores, bboxes, track, **kw):
-    """the track id of every row: ops.track, or with track_args' method 'sort' ops.track_sort, on the rows of whole clips"""
+    """the track id of every row: ops.track, or with track_args' method 'sort' ops.track_sort and with 'byte' ops.track_byte, on
+    the rows of whole clips"""
     from viddet_amd import ops
     track = dict(track)
-    link = ops.track_sort if track.pop("method", "iou") == "sort" else ops.track
+    link = dict(iou=ops.track, sort=ops.track_sort, byte=ops.track_byte)[track.pop("method", "iou")]
     return link(ids, scores, bboxes, **kw, **track)[0]
 
 
@@ -471,17 +498,23 @@ def check_flags(FLAGS):
         if not getattr(FLAGS, "stream", False) and getattr(FLAGS, "synthetic_videos", None) is None:
             raise NotImplementedError("--track needs clips: give --stream or --synthetic_videos (the plain synthetic set is "
                                       "unrelated still images)")
-        if getattr(FLAGS, "track_method", "iou") not in ("iou", "sort"):
-            raise NotImplementedError("--track_method must be iou or sort, got %r" % (FLAGS.track_method,))
+        if getattr(FLAGS, "track_method", "iou") not in ("iou", "sort", "byte"):
+            raise NotImplementedError("--track_method must be iou, sort or byte, got %r" % (FLAGS.track_method,))
+        for flag, _ in _BYTE_FLAGS:
+            if getattr(FLAGS, "track_method", "iou") != "byte" and getattr(FLAGS, flag, None) is not None:
+                raise NotImplementedError("--%s belongs to --track_method byte: --track_method %s has no such threshold"
+                                          % (flag, getattr(FLAGS, "track_method", "iou")))
         if getattr(FLAGS, "track_method", "iou") != "iou" and getattr(FLAGS, "live", False):
             raise NotImplementedError("--track_method %s does not combine with --live: it has no resumable form yet, a live "
                                       "session carries the iou tracker only" % FLAGS.track_method)
+        from viddet_amd.byte import check_byte_params
         from viddet_amd.track import check_params
         try:
-            check_params(who="--track", **{k: v for k, v in track_args(FLAGS).items() if k != "method"})
+            params = {k: v for k, v in track_args(FLAGS).items() if k != "method"}
+            (check_byte_params if getattr(FLAGS, "track_method", "iou") == "byte" else check_params)(who="--track", **params)
         except ValueError as e:
-            names = dict(sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high", t_min="--track_min_len",
-                         max_age="--track_max_age")
+            names = dict(sigma_iou2="--track_iou2", sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high",
+                         t_min="--track_min_len", max_age="--track_max_age", sigma_d="--track_det", sigma_new="--track_new")
             msg = str(e)
             for k, flag in names.items():
                 msg = msg.replace("--track: " + k, flag)

@@ -891,6 +891,28 @@ int vd_track_sort(const float* ids, const float* scores, const float* bboxes, co
                   int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
                   int32_t* out_len, float* out_score, float* out_tbox, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The detections of video clips linked into tracks by BYTE (vd_track_byte.hip): what
+ * viddet_amd.byte.byte_host computes, bit for bit, on all four outputs - Zhang et al., "ByteTrack: Multi-Object Tracking by
+ * Associating Every Detection Box" (ECCV 2022).  Everything is vd_track_sort's - the arguments, the candidates (score >=
+ * sigma_l), the filter, the cost of a cell, the assignment, the update, the decision at the clip's end, the outputs, the
+ * workspace (vd_track_byte_ws_bytes gives vd_track_sort_ws_bytes' figure: VD_TRACK_SORT_WS_PER_ROW per (frame, row) and
+ * VD_TRACK_SORT_WS_PER_CLIP per clip), the limits and the alignment - but the frame's association, which is made twice:
+ *   first    rows = the HIGH rows (candidates with score >= sigma_d) in row order, columns = ALL active tracks in order of
+ *            creation, then a dummy per row; admissible iff equal classes and iou(predicted box, row box) >= sigma_iou
+ *   second   rows = the LOW rows (every other candidate) in row order, the same columns in the same places; a track is eligible
+ *            iff the first association did not match it AND its miss count on entry to the frame is 0, every cell of another
+ *            track's column is forbidden; admissible iff eligible, equal classes and iou >= sigma_iou2
+ * Either is entered only when it has a row and a track is active.  A track matched by either is updated with its row; every
+ * other track's miss count grows by one.  Start: the high rows that the first association left without a track and whose score
+ * >= sigma_new, in row order; a low row, and a high row below sigma_new, that found no track gets -1 / 0 / -1 / -1.  No order
+ * among the thresholds is demanded (sigma_l > sigma_d leaves no low rows); none may be NaN.  One workgroup of 256 threads per
+ * clip, 51,344 bytes of LDS; the inputs are never written.  No atomics, bit-reproducible. */
+int64_t vd_track_byte_ws_bytes(int V, int F, int N);
+int vd_track_byte(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
+                  int num_class, float sigma_l, float sigma_d, float sigma_new, float sigma_h, float sigma_iou, float sigma_iou2,
+                  int t_min, int max_age, int32_t* out_track, int32_t* out_len, float* out_score, float* out_tbox, void* ws,
+                  int64_t ws_bytes, void* stream);
+
 /* ---- The per-frame matching of the HOTA tracking metric (vd_hota_eval.hip): what
  * viddet_amd.hota_metric.hota_match_host computes, bit for bit, on all three outputs - Luiten et al., "HOTA: A Higher Order
  * Metric for Evaluating Multi-Object Tracking" (IJCV 2021).  The inputs are vd_mot_match's; the ids are dense: a ground-truth row

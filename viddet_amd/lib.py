@@ -212,6 +212,9 @@ SIGNATURES = {
     # the detections of video clips linked into tracks by SORT: Kalman prediction, optimal assignment (vd_track_sort.hip)
     "vd_track_sort_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_track_sort": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    # ... and by BYTE: a second association of the low-score rows (vd_track_byte.hip); the workspace is vd_track_sort's
+    "vd_track_byte_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_track_byte": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
     # tubelet rescoring and gap filling over the tracks of video clips (vd_tubelet.hip)
     "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
     "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),

@@ -156,8 +156,9 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         res = ids, scores, bboxes
     if trk is not None:
         boxes = res[2] if trk[1] is None else res[2].clamp(0, float(trk[1]))
-        if trk[2] == "sort":                                      # SORT: the triple as ever, the filtered boxes beside it
-            *links, net.last_track_boxes = ops.track_sort(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if trk[2] in ("sort", "byte"):                            # SORT, BYTE: the triple as ever, the filtered boxes beside it
+            link = ops.track_sort if trk[2] == "sort" else ops.track_byte
+            *links, net.last_track_boxes = link(res[0], res[1], boxes, num_class=num_class, **trk[0])
             net.last_tracks = tuple(links)
         else:
             net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
@@ -191,7 +192,7 @@ class VideoSession:
     triple for those frames: ids counted over the clip, lengths and maxima so far.  Nothing is decided online: sigma_h and
     t_min (kept in track_decide) are for track.finalize_tracks on the concatenated triples of the finished clip, which gives
     detect_video(track=...)'s last_tracks.  The session carries the IOU tracker only: track={'method': 'sort'}
-    has no resumable form yet and raises NotImplementedError.
+    and track={'method': 'byte'} have no resumable form yet and raise NotImplementedError.
 
     Seq-NMS is not a session option: it takes the best path through ALL frames of a clip, removes it and starts again until no
     row is alive, so no frame is final before the clip ends - it has no online form.  Run detect_video(seq_nms=...) on the

@@ -2264,8 +2264,10 @@ class YOLOV3(object):
         re-sorted rows).  The returned tensors are what the call returns without it; last_tracks = (track, tlen, tscore),
         each (T,post_nms), holds the result and is None after a call without `track`.  A further key `method`: 'iou' (the
         default, the IOU tracker) or 'sort' (SORT: Kalman prediction and an optimal assignment, ops.track_sort, DESIGN.md 34;
-        the missing parameters then take viddet_amd.sort's defaults, sigma_iou 0.3 and max_age 1); with 'sort'
-        last_track_boxes (T,post_nms,4) holds the filtered box of every tracked row, otherwise it is None.
+        the missing parameters then take viddet_amd.sort's defaults, sigma_iou 0.3 and max_age 1) or 'byte' (BYTE: SORT with
+        a second association of the low-score rows, ops.track_byte; it takes sigma_d, sigma_new and sigma_iou2
+        as well, and the missing parameters take viddet_amd.byte's defaults); with 'sort' and 'byte' last_track_boxes
+        (T,post_nms,4) holds the filtered box of every tracked row, otherwise it is None.
 
         tubelet: None (the default), True, or a dict of rescore / max_gap / drop_untracked; needs `track` - the rows the tracker
         saw (those of Seq-NMS where that is on, clipped where track's `clip` is given) go through the tubelet pass on the device
@@ -2282,8 +2284,8 @@ class YOLOV3(object):
         whose length nobody knows - session.push(frames) returns the detections that are final by now, session.flush() ends
         the clip.  Refused where detect_video is, in the same words, and while another session of this net has
         frames in flight.  Seq-NMS has no online form and is no option here; nor is the tubelet pass: a hole is
-        known only once its track resumes, after the frame has been given out.  track={'method': 'sort'} raises
-        NotImplementedError: SORT has no resumable form yet."""
+        known only once its track resumes, after the frame has been given out.  track={'method': 'sort'} and
+        track={'method': 'byte'} raise NotImplementedError: SORT and BYTE have no resumable form yet."""
         if self._live is not None:
             raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))
         from .live import VideoSession

@@ -660,6 +660,40 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
     return out_track, out_len, out_score
 
 
+def _kalman_link_args(who, ids, scores, bboxes, clip_start, ws):
+    """The tensor checks, clip offsets, workspace and outputs that ops.track_sort and ops.track_byte share ->
+    (V, F, N, clip_start on the device or None, ws, (out_track, out_len, out_score, out_tbox))"""
+    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("%s: bboxes must be (F,N,4), got %r" % (who, tuple(bboxes.shape)))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TRACK_MAX_ROWS:
+        raise ValueError("%s: N=%d rows per frame, vd_%s takes at most %d" % (who, N, who, L.TRACK_MAX_ROWS))
+    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("%s: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                             % (who, name, n, t.dtype, tuple(t.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("%s: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (who, clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("%s: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (who, F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_WS_PER_CLIP * V
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("%s: ws must be a contiguous uint8 device tensor of >= %d bytes" % (who, need))
+    outs = (torch.empty(F, N, dtype=torch.int32, device=bboxes.device), torch.empty(F, N, dtype=torch.int32, device=bboxes.device),
+            torch.empty(F, N, dtype=torch.float32, device=bboxes.device), torch.empty(F, N, 4, dtype=torch.float32, device=bboxes.device))
+    return V, F, N, clip_start, ws, outs
+
+
 def track_sort(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.3, t_min=2, max_age=1,
                ws=None):
     """vd_track_sort (viddet_amd/sort.py::sort_host on the device, bit for bit, DESIGN.md 34): SORT - Kalman prediction, optimal
@@ -669,42 +703,32 @@ def track_sort(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, s
     reuse, else one is allocated."""
     from .track import check_params
     sl, sh, si, t_min, max_age = check_params(sigma_l, sigma_h, sigma_iou, t_min, max_age, "track_sort")
-    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("track_sort: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TRACK_MAX_ROWS:
-        raise ValueError("track_sort: N=%d rows per frame, vd_track_sort takes at most %d" % (N, L.TRACK_MAX_ROWS))
-    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("track_sort: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                             % (name, n, t.dtype, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("track_sort: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("track_sort: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_WS_PER_CLIP * V
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("track_sort: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
-    out_track = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
-    out_len = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
-    out_score = torch.empty(F, N, dtype=torch.float32, device=bboxes.device)
-    out_tbox = torch.empty(F, N, 4, dtype=torch.float32, device=bboxes.device)
+    V, F, N, clip_start, ws, outs = _kalman_link_args("track_sort", ids, scores, bboxes, clip_start, ws)
     if F == 0 or N == 0:
-        return out_track, out_len, out_score, out_tbox
+        return outs
     check(_lib().vd_track_sort(ptr(ids), ptr(scores), ptr(bboxes), ptr(clip_start), V, F, N, int(num_class), float(sl), float(sh),
-                               float(si), t_min, max_age, ptr(out_track), ptr(out_len), ptr(out_score), ptr(out_tbox), ptr(ws),
+                               float(si), t_min, max_age, ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(ws),
                                int(ws.numel()), _s()), "vd_track_sort")
-    return out_track, out_len, out_score, out_tbox
+    return outs
+
+
+def track_byte(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.1, sigma_d=0.5, sigma_new=0.6, sigma_iou=0.2,
+               sigma_iou2=0.5, sigma_h=0.5, t_min=2, max_age=7, ws=None):
+    """vd_track_byte (viddet_amd/byte.py::byte_host on the device, bit for bit, DESIGN.md 36): BYTE - SORT's filter and
+    assignment, made twice a frame: the rows scored >= sigma_d against every track, then the other candidates against the tracks
+    that are left and were seen in the last frame; only a row scored >= sigma_new starts a track.  The inputs, the checks and
+    the returned (track, tlen, tscore, tbox) are ops.track_sort's.  Launches on the current stream; nothing is downloaded and
+    nothing waits.  ws: a uint8 device tensor of >= 8*F*N + 139264*V bytes to reuse, else one is allocated."""
+    from .byte import check_byte_params
+    sl, sd, sn, si, si2, sh, t_min, max_age = check_byte_params(sigma_l, sigma_d, sigma_new, sigma_iou, sigma_iou2, sigma_h, t_min,
+                                                                max_age, "track_byte")
+    V, F, N, clip_start, ws, outs = _kalman_link_args("track_byte", ids, scores, bboxes, clip_start, ws)
+    if F == 0 or N == 0:
+        return outs
+    check(_lib().vd_track_byte(ptr(ids), ptr(scores), ptr(bboxes), ptr(clip_start), V, F, N, int(num_class), float(sl), float(sd),
+                               float(sn), float(sh), float(si), float(si2), t_min, max_age, ptr(outs[0]), ptr(outs[1]),
+                               ptr(outs[2]), ptr(outs[3]), ptr(ws), int(ws.numel()), _s()), "vd_track_byte")
+    return outs
 
 
 def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="avg", max_gap=7, drop_untracked=False, ws=None,

@@ -31,7 +31,7 @@ _F = np.float32
 MAX_AGE = 7                                       # max_age lies in [0, MAX_AGE]
 MAX_ACTIVE = MAX_ROWS * (MAX_AGE + 1)             # the active-track table of vd_track
 DEFAULTS = dict(sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0)
-METHODS = ("iou", "sort")                         # the linking methods of `track=`: this module's, viddet_amd/sort.py's
+METHODS = ("iou", "sort", "byte")                 # the linking methods of `track=`: this module's, viddet_amd/sort.py's, byte.py's
 
 
 def check_params(sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0, who="track"):
@@ -53,25 +53,33 @@ def check_params(sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0, wh
 
 
 def parse_option(track, post_nms, who):
-    """The `track=` option of `who` (detect_video, open_video): None / False -> None; True or a dict of the five parameters,
-    `clip` and `method` -> (the five parameters, the method's defaults filled in, `clip` or None, the method: 'iou', this
-    module's tracker and the default, or 'sort', viddet_amd/sort.py's).  A ValueError names what is not usable."""
+    """The `track=` option of `who` (detect_video, open_video): None / False -> None; True or a dict of the method's parameters,
+    `clip` and `method` -> (the parameters, the method's defaults filled in, `clip` or None, the method: 'iou', this module's
+    tracker and the default, 'sort', viddet_amd/sort.py's, or 'byte', viddet_amd/byte.py's, which takes sigma_d, sigma_new and
+    sigma_iou2 beside the five).  A ValueError names what is not usable."""
     if track is None or track is False:
         return None
     kw = {} if track is True else dict(track)
     clip = kw.pop("clip", None)
     method = kw.pop("method", "iou")
     if method not in METHODS:
-        raise ValueError("%s: track method must be 'iou' or 'sort', got %r" % (who, method))
-    unknown = sorted(set(kw) - set(DEFAULTS))
-    if unknown:
-        raise ValueError("%s: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age (and clip, method), got %s"
-                         % (who, ", ".join(unknown)))
+        raise ValueError("%s: track method must be 'iou' or 'sort', got %r (or 'byte')" % (who, method))
     defaults = DEFAULTS
     if method == "sort":
         from .sort import DEFAULTS as defaults
+    elif method == "byte":
+        from .byte import DEFAULTS as defaults
+    unknown = sorted(set(kw) - set(defaults))
+    if unknown:
+        extra = ", sigma_d, sigma_new, sigma_iou2" if method == "byte" else ""
+        raise ValueError("%s: track takes sigma_l, sigma_h, sigma_iou, t_min and max_age%s (and clip, method), got %s"
+                         % (who, extra, ", ".join(unknown)))
     kw = dict(defaults, **kw)
-    check_params(who=who + " with track", **kw)
+    if method == "byte":
+        from .byte import check_byte_params
+        check_byte_params(who=who + " with track", **kw)
+    else:
+        check_params(who=who + " with track", **kw)
     if post_nms > TRACK_MAX_ROWS:
         raise ValueError("%s with track: post_nms=%d rows per frame, the tracker takes at most %d" % (who, post_nms, TRACK_MAX_ROWS))
     return kw, clip, method

@@ -25,7 +25,10 @@ DESIGN.md 36; not with --live).  `--live` (with --stream; no reference counterpa
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
 the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
 pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
-an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.  `--metrics mot`
+an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.
+`--track_smooth` (with --track; no reference counterpart) smooths the boxes of every tracked clip along its tracks on the device
+(vd_track_smooth, DESIGN.md 37: the Rauch-Tung-Striebel smoother of SORT's Kalman filter) and writes the rows with their smoothed
+boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --live, --seq_nms or --tubelet.  `--metrics mot`
 (with --track; no reference counterpart) scores every tracked twin with the MOT tracking metric (viddet_amd/mot_metric.py: MOTA,
 MOTP, id switches, fragmentations, IDF1, ... against the track ids of SyntheticTracks) on the rows read back from the
 twin's files, and writes mot.txt / mot_seq.txt / mot_tub.txt; `--device_metric` with the per-frame matching on the device
@@ -181,6 +184,14 @@ def parse_flags(argv=None):
     A("--tubelet_max_gap", type=int, default=7, help="--tubelet: holes of up to this many frames are filled, 0 (none) to 7")
     A("--tubelet_drop_untracked", type=_bool, nargs="?", const=True, default=False,
       help="--tubelet: the rows that no kept track holds are dropped")
+    A("--track_smooth", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --track: the boxes of every tracked clip are smoothed along its tracks on the device "
+           "(vd_track_smooth): the Rauch-Tung-Striebel smoother of SORT's Kalman filter estimates every box of a track from the "
+           "frames before and after it.  Everything a run without the flag writes is written unchanged; the smoothed rows go to "
+           "pred_smo, their twin with track ids to pred_smo_trk, tracks_smo.txt and the --metrics files *_smo.txt (DESIGN.md 37).  "
+           "Not with --live (a frame's smoothed box needs the frames after it), --seq_nms or --tubelet")
+    A("--track_smooth_gap", type=int, default=7,
+      help="--track_smooth: a track is cut where it skips more than this many frames, 0 to 7")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -264,6 +275,13 @@ def tubelet_args(FLAGS):
                 drop_untracked=FLAGS.tubelet_drop_untracked)
 
 
+def smooth_args(FLAGS):
+    """the dict net.detect_video and ops.smooth take, None without --track_smooth"""
+    if not getattr(FLAGS, "track_smooth", False):
+        return None
+    return dict(max_gap=FLAGS.track_smooth_gap)
+
+
 def _collect_tracks(tracks, dataset, ids, track, sidxs):
     """the track id of every row _collect files, in its order, under the same image path"""
     ids, track = ids.cpu().numpy(), track.cpu().numpy()
@@ -282,14 +300,16 @@ def clip_offsets(sidxs, frames_per_video):
     return cs + [len(sidxs)]
 
 
-def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None, tubelet=None):
+def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None, tubelet=None, smooth=None):
     """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
     (--device_resize: raw frames, resized on the device).  seq_nms (a dict of link_thresh / nms_thresh / rescore): every
     batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored).
     track (a dict of ops.track's parameters): the outputs stay on the device likewise and ONE ops.track call per prediction set
     follows; returns (boxes, rescored or None, tracks, tracks of the rescored or None).  tubelet (a dict of ops.tubelet's
     parameters, with track and without seq_nms): ONE ops.tubelet call over all tracked clips follows; the rows after the pass
-    and their track ids are returned as a fifth and a sixth element."""
+    and their track ids are returned as a fifth and a sixth element.  smooth (a dict of ops.smooth's parameter, with track and
+    without seq_nms and tubelet): ONE ops.smooth call over all tracked clips follows; the rows with their smoothed boxes and
+    their track ids are returned as that fifth and sixth element."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     boxes = dict()
     if max_do < 0:
@@ -333,6 +353,10 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
                 out = ops.tubelet(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **tubelet)
                 _collect(boxes_tub, dataset, out[0], out[1], out[2], sidxs, W)
                 _collect_tracks(tracks_tub, dataset, out[0], out[4], sidxs)
+            elif smooth is not None:
+                sbox, _ = ops.smooth(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **smooth)
+                _collect(boxes_tub, dataset, ids, scores, sbox, sidxs, W)
+                _collect_tracks(tracks_tub, dataset, ids, linked, sidxs)
         if seq_nms is not None:
             out = ops.seq_nms(ids, scores, bboxes, clip_start=cs, num_class=C, **seq_nms)
             _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
@@ -340,7 +364,7 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
                 _collect_tracks(tracks_seq, dataset, out[0], link_rows(out[0], out[1], out[2], track, clip_start=cs, num_class=C), sidxs)
     if track is None:
         return boxes, boxes_seq
-    if tubelet is not None:
+    if tubelet is not None or smooth is not None:
         return boxes, None, tracks, None, boxes_tub, tracks_tub
     return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
@@ -367,7 +391,7 @@ def live_clip(net, frames, step, chunk, push, track=None):
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None):
+                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
@@ -375,7 +399,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     the plain rows ahead of Seq-NMS are linked by a call of their own; returns (boxes, rescored or None, tracks, tracks of the
     rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead.  tubelet (a dict,
     with track, without seq_nms and live): handed to detect_video as well; the plain rows are the ones it keeps in
-    net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element."""
+    net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element.  smooth
+    (a dict, with track, without seq_nms, live and tubelet): handed to detect_video likewise; the plain boxes are the ones it
+    keeps in net.last_pre_smooth, and the rows with their smoothed boxes and their track ids are that fifth and sixth element."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
@@ -400,6 +426,12 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             _collect_tracks(tracks_tub, dataset, out[0], net.last_tubelet[1], sidxs)
             ids, scores, bboxes = net.last_pre_tubelet                     # the plain rows, clipped as _collect clips them
             _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
+        elif smooth is not None:
+            ids, scores, sbox = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, smooth=smooth, **trk_kw)
+            _collect(boxes_tub, dataset, ids, scores, sbox, sidxs, W)
+            _collect_tracks(tracks_tub, dataset, ids, net.last_tracks[0], sidxs)
+            bboxes = net.last_pre_smooth                                   # the plain boxes, clipped as _collect clips them
+            _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
         elif seq_nms is None:
             ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, **trk_kw)
             if track is not None:
@@ -418,7 +450,7 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         c += x.shape[0]
         if c > max_do:
             break
-    if tubelet is not None:
+    if tubelet is not None or smooth is not None:
         return boxes, None, tracks, None, boxes_tub, tracks_tub
     if track is not None:
         return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
@@ -428,16 +460,23 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
 def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False, tub=False):
     """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag;
     seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq; trk: the twin of either whose lines end in the
-    track id of --track, `_trk` last; tub: the rows after the pass of --tubelet, under pred_tub / pred_ag_tub"""
-    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + ("_tub" if tub else "")
+    track id of --track, `_trk` last; tub: the rows after the pass of --tubelet, under pred_tub / pred_ag_tub ('smo': those of
+    --track_smooth, under pred_smo / pred_ag_smo)"""
+    return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + _pass_tail(tub)
                         + ("_trk" if trk else ""))
+
+
+def _pass_tail(tub):
+    """what the files of the rows after a pass over the tracks carry in their names: True (--tubelet) _tub, 'smo'
+    (--track_smooth) _smo, False nothing"""
+    return "_tub" if tub is True else "_" + tub if tub else ""
 
 
 def result_name(metric_name, model_agnostic=False, metric_agnostic=False, seq=False, tub=False):
     """detect_yolo3.py:920-925 (--model_agnostic sets --metric_agnostic, :797-798; `_met` marks a class-agnostic metric over a
     per-class model, which only the vid metric has); seq: the metric of the predictions rescored by --seq_nms, `_seq` last; tub:
-    the metric of the rows after the pass of --tubelet, `_tub` last"""
-    tail = ("_seq" if seq else "") + ("_tub" if tub else "")
+    the metric of the rows after the pass of --tubelet, `_tub` last ('smo': of --track_smooth, `_smo`)"""
+    tail = ("_seq" if seq else "") + _pass_tail(tub)
     if model_agnostic:
         return metric_name + "_ag" + tail
     return (metric_name + "_ag_met" if metric_agnostic else metric_name) + tail
@@ -539,6 +578,24 @@ def check_flags(FLAGS):
             for k, flag in (("max_gap", "--tubelet_max_gap"), ("drop_untracked", "--tubelet_drop_untracked"), ("rescore", "--tubelet_rescore")):
                 msg = msg.replace("--tubelet: " + k, flag)
             raise NotImplementedError(msg)
+    if getattr(FLAGS, "track_smooth", False):
+        # the smoother runs over the tracks of a finished clip
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--track_smooth needs --track: the pass runs over the tracks of a clip")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_smooth does not combine with --live: a frame's smoothed box needs the frames after "
+                                      "it - the pass has no online form")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--track_smooth does not combine with --seq_nms: net.detect_video composes the two, the "
+                                      "script would need a further family of prediction sets")
+        if getattr(FLAGS, "tubelet", False):
+            raise NotImplementedError("--track_smooth does not combine with --tubelet: net.detect_video composes the two, the "
+                                      "script keeps one extra family of files at a time")
+        from viddet_amd.smooth import check_params as check_smooth
+        try:
+            check_smooth(who="--track_smooth", **smooth_args(FLAGS))
+        except ValueError as e:
+            raise NotImplementedError(str(e).replace("--track_smooth: max_gap", "--track_smooth_gap"))
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
     for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
@@ -743,6 +800,9 @@ def main(argv=None):
     tub = tubelet_args(FLAGS)
     if tub is not None:
         seq_kw = dict(seq_kw, tubelet=tub)
+    smo = smooth_args(FLAGS)
+    if smo is not None:
+        seq_kw = dict(seq_kw, smooth=smo)
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
@@ -750,7 +810,7 @@ def main(argv=None):
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None
-    if tub is not None:
+    if tub is not None or smo is not None:                                 # check_flags: one of the two at most
         boxes, boxes_seq, tracks, tracks_seq, boxes_tub, tracks_tub = boxes
     elif trk is not None:
         boxes, boxes_seq, tracks, tracks_seq = boxes
@@ -797,15 +857,18 @@ def main(argv=None):
                     result = mot_result
     if boxes_tub is not None:
         # the rows after the tubelet pass, last: pred_tub, vid_tub.txt, coco_tub.txt, ..., pred_tub_trk, tracks_tub.txt
-        save_and_evaluate(FLAGS, dataset, boxes_tub, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, tub=True),
-                          tub=True)
-        save_tracks(FLAGS, dataset, boxes_tub, tracks_tub, tub=True)
+        # (--track_smooth: the rows with their smoothed boxes, pred_smo, vid_smo.txt, ..., pred_smo_trk, tracks_smo.txt)
+        tail = True if tub is not None else "smo"
+        save_and_evaluate(FLAGS, dataset, boxes_tub, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, tub=tail),
+                          tub=tail)
+        save_tracks(FLAGS, dataset, boxes_tub, tracks_tub, tub=tail)
     return result
 
 
 def save_tracks(FLAGS, dataset, boxes, tracks, seq=False, tub=False):
     """--track: the twin of a prediction set - its files' lines with `,track` appended (every row, -1 too) - and one line
-    `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt (tub: pred_tub_trk, tracks_tub.txt)"""
+    `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt (tub: pred_tub_trk, tracks_tub.txt; 'smo':
+    pred_smo_trk, tracks_smo.txt)"""
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=seq, trk=True, tub=tub)
     os.makedirs(save_dir, exist_ok=True)
     n = len(dataset) if FLAGS.max_do < 0 else min(FLAGS.max_do, len(dataset))
@@ -885,7 +948,7 @@ def evaluate_tracks(metric, dataset, predictions):
 
 def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False, tub=False):
     """The tail of main(): the prediction files under save_dir, then --metrics on what was saved; seq names the result files
-    of the predictions rescored by --seq_nms, tub those of the rows after the pass of --tubelet."""
+    of the predictions rescored by --seq_nms, tub those of the rows after the pass of --tubelet ('smo': of --track_smooth)."""
     save_predictions(save_dir, dataset, boxes, max_do=FLAGS.max_do)
     metrics = [m.lower() for m in FLAGS.metrics]
     out_dir = os.path.join(FLAGS.save_dir, FLAGS.save_prefix)
@@ -917,7 +980,7 @@ def save_and_evaluate(FLAGS, dataset, boxes, save_dir, seq=False, tub=False):
         else:
             coco_class = COCODetectionMetric
         # get_metric :186: the detections' JSON beside pred/, removed again (cleanup); no time stamp in its name
-        metric = coco_class(dataset, os.path.join(out_dir, "coco_results" + ("_seq" if seq else "") + ("_tub" if tub else "")), use_time=False, cleanup=True, data_shape=None)
+        metric = coco_class(dataset, os.path.join(out_dir, "coco_results" + ("_seq" if seq else "") + _pass_tail(tub)), use_time=False, cleanup=True, data_shape=None)
         coco_result = evaluate_by_sample_id(metric, dataset, preds)
         write_results(os.path.join(out_dir, result_name("coco", FLAGS.model_agnostic, FLAGS.metric_agnostic, seq, tub) + ".txt"),
                       *coco_result)

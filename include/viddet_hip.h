@@ -823,6 +823,40 @@ int vd_tubelet_stages(const float* ids, const float* scores, const float* bboxes
                       float* out_scores, float* out_bboxes, int32_t* perm, int32_t* track_out, int32_t* dropped, void* ws,
                       int64_t ws_bytes, int stages, void* stream);
 
+/* ---- Fixed-interval (Rauch-Tung-Striebel) smoothing of the boxes of video clips along their tracks (vd_track_smooth.hip,
+ * DESIGN.md 37): what viddet_amd.smooth.smooth_host computes, bit for bit, on both outputs.  ids, scores, bboxes, clip_start, V,
+ * F, N, num_class: as vd_seq_nms takes them; track [F][N] int32: the out_track of vd_track / vd_track_sort / vd_track_byte (any
+ * table is safe).  Per clip [t0, t1):
+ *   1. members: vd_tubelet's step 1 - a present row is a member of track u = track[t][i] iff 0 <= u < (t1 - t0) * N and no lower
+ *      row of its frame is a member of u already;
+ *   2. segments: a track's members in frame order, cut where two consecutive members lie more than max_gap + 1 frames apart;
+ *   3. forward, for a segment of n >= 2 members: the Kalman filter of vd_track_sort (start at the first member's box, predict
+ *      once per frame of a gap, update with every member's box);
+ *   4. backward: from the last member's posterior state, one Rauch-Tung-Striebel step per frame of every gap, the gap's
+ *      predicted states recomputed from the earlier member's posterior (smooth.py states every operation and its order);
+ *   5. out_sbox [F][N][4]: the box of a member's smoothed state; a member whose smoothed box is not finite, the member of a
+ *      segment of one, a row that is no member and every row of a frame that no clip covers keep the bits of their input box.
+ *      out_slen [F][N] int32: the members of the row's segment, 0 for a row that is no member.
+ * Both outputs are written in full.  A row index read back from the workspace is checked against the clip's rows before it
+ * indexes anything and a walk only ever moves to a strictly later (forward) or earlier (backward) frame.  ws holds
+ * VD_TRACK_SMOOTH_WS_PER_ROW bytes per (frame, row): the member id, the predecessor, the successor and the 17-float posterior
+ * state.  Four launches (one fewer without clip_start): clear, members per (clip, frame), links per (clip, frame), segments (a
+ * thread per row, a segment's first member does the work).  1 <= N <= 128, F >= 1, F * N < 2^31, V >= 1, num_class >= 1,
+ * 0 <= max_gap <= 7; bboxes and out_sbox 16-byte, every other pointer 4-byte aligned.  The inputs are never written.  No atomics,
+ * bit-reproducible.  vd_track_smooth_ws_bytes: the bytes ws must hold, -1 for sizes that are not taken. */
+#define VD_TRACK_SMOOTH_WS_PER_ROW 80
+int64_t vd_track_smooth_ws_bytes(int F, int N);
+int vd_track_smooth(const float* ids, const float* scores, const float* bboxes, const int32_t* track, const int32_t* clip_start,
+                    int V, int F, int N, int num_class, int max_gap, float* out_sbox, int32_t* out_slen, void* ws, int64_t ws_bytes,
+                    void* stream);
+/* the same, for timing the launches one by one (tools/smooth_probe.py): stages is a mask of 1 (clear), 2 (members), 4 (links),
+ * 8 (segments); vd_track_smooth is stages 15.  With fewer the outputs may stay unwritten; whatever the workspace holds, a row
+ * index read from it is checked against the clip's rows and a walk moves to a strictly later or earlier frame only, so a launch
+ * that meets a workspace no earlier launch filled stays inside it and ends. */
+int vd_track_smooth_stages(const float* ids, const float* scores, const float* bboxes, const int32_t* track,
+                           const int32_t* clip_start, int V, int F, int N, int num_class, int max_gap, float* out_sbox,
+                           int32_t* out_slen, void* ws, int64_t ws_bytes, int stages, void* stream);
+
 /* ---- The per-frame matching of the MOT tracking metric (vd_mot_eval.hip): what
  * viddet_amd.mot_metric.mot_match_host computes, bit for bit, on all four outputs.  gt_boxes [F][G][4] fp32, gt_cls, gt_id
  * [F][G] int32: the label rows (corner boxes, class, ground-truth track id); ids, scores, bboxes, clip_start, V, F, N, num_class: as

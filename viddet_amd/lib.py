@@ -23,7 +23,8 @@ TRACK_SORT_WS_PER_ROW = 8                           # vd_track_sort: workspace b
 TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per clip, two tables of 17 x 1024 state floats
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
-MOT_MAX_ROWS = 128                                  # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
+TRACK_SMOOTH_WS_PER_ROW = 80                        # vd_track_smooth: workspace bytes per (frame, row) (VD_TRACK_SMOOTH_WS_PER_ROW)
+MOT_MAX_ROWS = 128                                 # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
 MOT_WS_PER_ROW = 4                                  # vd_mot_match: workspace bytes per (frame, row) of either side (VD_MOT_WS_PER_ROW)
 HOTA_MAX_GT_IDS = 1024                              # vd_hota_match: dense ground-truth ids per clip (vd_hota_eval.hip)
 HOTA_MAX_FRAMES = 1 << 22                           # vd_hota_match: frames of one call
@@ -219,6 +220,10 @@ SIGNATURES = {
     "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
     "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "vd_tubelet_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _i, _p]),
+    # Rauch-Tung-Striebel smoothing of the boxes along the tracks of video clips (vd_track_smooth.hip)
+    "vd_track_smooth_ws_bytes": (_i64, [_i, _i]),
+    "vd_track_smooth": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
+    "vd_track_smooth_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _i, _p]),
     # the per-frame matching of the MOT tracking metric on the device (vd_mot_eval.hip)
     "vd_mot_match_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_mot_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),

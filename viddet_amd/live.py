@@ -12,6 +12,7 @@ import torch
 
 from . import ops
 from .seq_nms import parse_option as parse_seq_nms
+from .smooth import parse_option as parse_smooth
 from .stream import StreamPlanner
 from .track import parse_option as parse_track
 from .tubelet import parse_option as parse_tubelet
@@ -119,9 +120,10 @@ def _follow(rows, perm):
     return torch.where(perm >= 0, old, torch.full_like(old, -1))
 
 
-def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None):
+def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None):
     """YOLOV3.detect_video (its docstring is the description): a clip whose end is known is one push and one flush of the
-    planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> tubelet on the finished clip."""
+    planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> smooth -> tubelet on the
+    finished clip."""
     why = net._stream_refusal()
     if why is not None:
         raise NotImplementedError("detect_video with " + why)
@@ -131,8 +133,10 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
     seq = parse_seq_nms(seq_nms, net.post_nms, "detect_video")
     trk = parse_track(track, net.post_nms, "detect_video")
     tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
+    smo_kw = parse_smooth(smooth, trk is not None, "detect_video")
     net.last_tracks = net.last_track_boxes = None
     net.last_tubelet = net.last_pre_tubelet = None
+    net.last_smooth = net.last_pre_smooth = None
     if net._k > 1:
         net._stream_split()                                       # the graph's own word, before anything touches the GPU
     step, chunk = int(step), int(chunk)
@@ -162,6 +166,10 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
             net.last_tracks = tuple(links)
         else:
             net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if smo_kw is not None:                                    # the boxes the tracker saw, smoothed along its tracks
+            net.last_pre_smooth = boxes
+            boxes, net.last_smooth = ops.smooth(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **smo_kw)
+            res = res[0], res[1], boxes
         if tub_kw is not None:
             net.last_pre_tubelet = res[0], res[1], boxes          # the rows the tracker saw
             out_t = ops.tubelet(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **tub_kw)

@@ -790,6 +790,61 @@ def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="a
     return out_ids, out_scores, out_bboxes, perm, track_out, dropped
 
 
+def smooth(ids, scores, bboxes, track, clip_start=None, num_class=1, max_gap=7, ws=None, stages=None):
+    """vd_track_smooth (viddet_amd/smooth.py::smooth_host on the device, bit for bit, DESIGN.md 37): ids (F,N[,1]), scores
+    (F,N[,1]) and bboxes (F,N,4) are contiguous fp32 device tensors, N <= 128; track (F,N) a contiguous int32 device tensor, the
+    first result of ops.track / ops.track_sort / ops.track_byte; clip_start as ops.seq_nms takes it.  Returns (sbox, slen), new
+    device tensors: sbox (F,N,4) fp32, the Rauch-Tung-Striebel smoothed box of every member of a segment of two or more members
+    and the input box elsewhere; slen (F,N) int32, the members of the row's segment.  Launches on the current stream; nothing is
+    downloaded and nothing waits.  ws: a uint8 device tensor of >= 80*F*N bytes to reuse, else one is allocated.  stages (a mask
+    of 1, 2, 4, 8; tools/smooth_probe.py): only those of the four launches are made (vd_track_smooth_stages) and the outputs may
+    stay unwritten."""
+    from .smooth import check_params
+    max_gap = check_params(max_gap, "smooth")
+    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("smooth: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TUBELET_MAX_ROWS:
+        raise ValueError("smooth: N=%d rows per frame, vd_track_smooth takes at most %d" % (N, L.TUBELET_MAX_ROWS))
+    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
+        raise ValueError("smooth: num_class must be an integer >= 1, got %r" % (num_class,))
+    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
+                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("smooth: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(track.shape) != (F, N):
+        raise ValueError("smooth: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("smooth: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("smooth: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TRACK_SMOOTH_WS_PER_ROW * F * N
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("smooth: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    sbox = torch.empty_like(bboxes)
+    slen = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
+    if F == 0 or N == 0:
+        return sbox, slen
+    args = (ptr(ids), ptr(scores), ptr(bboxes), ptr(track), ptr(clip_start), V, F, N, int(num_class), max_gap, ptr(sbox), ptr(slen),
+            ptr(ws), int(ws.numel()))
+    if stages is None:
+        check(_lib().vd_track_smooth(*args, _s()), "vd_track_smooth")
+    else:
+        check(_lib().vd_track_smooth_stages(*args, int(stages), _s()), "vd_track_smooth_stages")
+    return sbox, slen
+
+
 def mot_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, clip_start=None, num_class=1, iou_thresh=0.5, agnostic=False,
               ws=None):
     """vd_mot_match (viddet_amd/mot_metric.py::mot_match_host on the device, bit for bit, DESIGN.md 33): gt_boxes (F,G,4) fp32,

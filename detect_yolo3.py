@@ -28,7 +28,11 @@ pass over every tracked clip on the device (vd_tubelet) - a track'
 an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.
 `--track_smooth` (with --track; no reference counterpart) smooths the boxes of every tracked clip along its tracks on the device
 (vd_track_smooth, DESIGN.md 37: the Rauch-Tung-Striebel smoother of SORT's Kalman filter) and writes the rows with their smoothed
-boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --live, --seq_nms or --tubelet.  `--metrics mot`
+boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --live, --seq_nms or --tubelet.
+`--track_stitch` (with --track; no reference counterpart) re-links the track fragments of every tracked clip across gaps of up to
+--track_stitch_gap frames on the device (vd_track_stitch) and writes the rows under their stitched ids beside
+everything else, under pred_sti_trk, tracks_sti.txt and mot_sti.txt / hota_sti.txt - the detections do not change, so there is no
+pred_sti; not with --live, --seq_nms, --tubelet or --track_smooth.  `--metrics mot`
 (with --track; no reference counterpart) scores every tracked twin with the MOT tracking metric (viddet_amd/mot_metric.py: MOTA,
 MOTP, id switches, fragmentations, IDF1, ... against the track ids of SyntheticTracks) on the rows read back from the
 twin's files, and writes mot.txt / mot_seq.txt / mot_tub.txt; `--device_metric` with the per-frame matching on the device
@@ -192,6 +196,17 @@ def parse_flags(argv=None):
            "Not with --live (a frame's smoothed box needs the frames after it), --seq_nms or --tubelet")
     A("--track_smooth_gap", type=int, default=7,
       help="--track_smooth: a track is cut where it skips more than this many frames, 0 to 7")
+    A("--track_stitch", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --track: the track fragments of every tracked clip are re-linked across long gaps on "
+           "the device (vd_track_stitch): a track's filter state at its last row is extrapolated over the gap and matched to the "
+           "first rows of later tracks, and every chain takes its first fragment's id.  Everything a run without the flag writes "
+           "is written unchanged; the rows under their stitched ids go to pred_sti_trk, tracks_sti.txt and the --metrics files "
+           "mot_sti.txt / hota_sti.txt (DESIGN.md 38).  Not with --live (a fragment's successor is known only later), --seq_nms, "
+           "--tubelet or --track_smooth")
+    A("--track_stitch_gap", type=int, default=None,
+      help="--track_stitch: a tail is extrapolated over at most this many frames, 1 to 32 (default 30)")
+    A("--track_stitch_iou", type=float, default=None,
+      help="--track_stitch: the least IoU of an extrapolated tail and a head (default 0.3)")
     A("--synthetic_classes", type=int, default=None, help="classes per dataset of the synthetic combined set (default: the datasets' own counts)")
     A("--random_init", type=_bool, nargs="?", const=True, default=False,
       help="skip load_parameters (no checkpoint available offline)")
@@ -300,7 +315,16 @@ def clip_offsets(sidxs, frames_per_video):
     return cs + [len(sidxs)]
 
 
-def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None, tubelet=None, smooth=None):
+def stitch_args(FLAGS):
+    """the dict net.detect_video and ops.stitch take, None without --track_stitch"""
+    if not getattr(FLAGS, "track_stitch", False):
+        return None
+    gap, iou = getattr(FLAGS, "track_stitch_gap", None), getattr(FLAGS, "track_stitch_iou", None)
+    return dict(max_gap=30 if gap is None else gap, sigma_iou=0.3 if iou is None else iou)
+
+
+def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input_nms=0.45, track=None, tubelet=None, smooth=None,
+           stitch=None):
     """detect_yolo3.py:198-272.  data_shape: the size the network detects at where the loader's frames are not that size
     (--device_resize: raw frames, resized on the device).  seq_nms (a dict of link_thresh / nms_thresh / rescore): every
     batch's outputs stay on the device, and ONE ops.seq_nms call over all clips follows the loop; returns (boxes, rescored).
@@ -309,7 +333,9 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
     parameters, with track and without seq_nms): ONE ops.tubelet call over all tracked clips follows; the rows after the pass
     and their track ids are returned as a fifth and a sixth element.  smooth (a dict of ops.smooth's parameter, with track and
     without seq_nms and tubelet): ONE ops.smooth call over all tracked clips follows; the rows with their smoothed boxes and
-    their track ids are returned as that fifth and sixth element."""
+    their track ids are returned as that fifth and sixth element.  stitch (a dict of ops.stitch's parameters, with track and
+    without the three): ONE ops.stitch call over all tracked clips follows; the fifth element is None - the rows are the plain
+    ones - and the sixth holds their stitched ids."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     boxes = dict()
     if max_do < 0:
@@ -357,6 +383,9 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
                 sbox, _ = ops.smooth(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **smooth)
                 _collect(boxes_tub, dataset, ids, scores, sbox, sidxs, W)
                 _collect_tracks(tracks_tub, dataset, ids, linked, sidxs)
+            elif stitch is not None:
+                _collect_tracks(tracks_tub, dataset, ids, ops.stitch(ids, scores, bboxes, linked, clip_start=cs, num_class=C, **stitch)[0],
+                                sidxs)
         if seq_nms is not None:
             out = ops.seq_nms(ids, scores, bboxes, clip_start=cs, num_class=C, **seq_nms)
             _collect(boxes_seq, dataset, out[0], out[1], out[2], sidxs, W)
@@ -366,6 +395,8 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
         return boxes, boxes_seq
     if tubelet is not None or smooth is not None:
         return boxes, None, tracks, None, boxes_tub, tracks_tub
+    if stitch is not None:
+        return boxes, None, tracks, None, None, tracks_tub
     return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
 
@@ -391,7 +422,7 @@ def live_clip(net, frames, step, chunk, push, track=None):
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None):
+                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
@@ -401,7 +432,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     with track, without seq_nms and live): handed to detect_video as well; the plain rows are the ones it keeps in
     net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element.  smooth
     (a dict, with track, without seq_nms, live and tubelet): handed to detect_video likewise; the plain boxes are the ones it
-    keeps in net.last_pre_smooth, and the rows with their smoothed boxes and their track ids are that fifth and sixth element."""
+    keeps in net.last_pre_smooth, and the rows with their smoothed boxes and their track ids are that fifth and sixth element.
+    stitch (a dict, with track, without the four): handed to detect_video likewise; the tracker's ids are the ones it keeps in
+    net.last_pre_stitch, the fifth element is None and the sixth holds the stitched ids of the plain rows."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
@@ -432,6 +465,10 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             _collect_tracks(tracks_tub, dataset, ids, net.last_tracks[0], sidxs)
             bboxes = net.last_pre_smooth                                   # the plain boxes, clipped as _collect clips them
             _collect_tracks(tracks, dataset, ids, net.last_tracks[0], sidxs)
+        elif stitch is not None:
+            ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, stitch=stitch, **trk_kw)
+            _collect_tracks(tracks, dataset, ids, net.last_pre_stitch[0], sidxs)
+            _collect_tracks(tracks_tub, dataset, ids, net.last_tracks[0], sidxs)
         elif seq_nms is None:
             ids, scores, bboxes = net.detect_video(torch.from_numpy(x), step=step, chunk=chunk, **trk_kw)
             if track is not None:
@@ -452,6 +489,8 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             break
     if tubelet is not None or smooth is not None:
         return boxes, None, tracks, None, boxes_tub, tracks_tub
+    if stitch is not None:
+        return boxes, None, tracks, None, None, tracks_tub
     if track is not None:
         return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
     return boxes if seq_nms is None else (boxes, boxes_seq)
@@ -461,14 +500,14 @@ def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False, tub=Fa
     """detect_yolo3.py:275-279, 333-337: predictions of an agnostic model live beside the per-class ones, under pred_ag;
     seq: the predictions rescored by --seq_nms, under pred_seq / pred_ag_seq; trk: the twin of either whose lines end in the
     track id of --track, `_trk` last; tub: the rows after the pass of --tubelet, under pred_tub / pred_ag_tub ('smo': those of
-    --track_smooth, under pred_smo / pred_ag_smo)"""
+    --track_smooth, under pred_smo / pred_ag_smo; 'sti': the twin under the stitched ids of --track_stitch, pred_sti_trk)"""
     return os.path.join(save_dir, save_prefix, ("pred_ag" if agnostic else "pred") + ("_seq" if seq else "") + _pass_tail(tub)
                         + ("_trk" if trk else ""))
 
 
 def _pass_tail(tub):
     """what the files of the rows after a pass over the tracks carry in their names: True (--tubelet) _tub, 'smo'
-    (--track_smooth) _smo, False nothing"""
+    (--track_smooth) _smo, 'sti' (--track_stitch) _sti, False nothing"""
     return "_tub" if tub is True else "_" + tub if tub else ""
 
 
@@ -596,6 +635,32 @@ def check_flags(FLAGS):
             check_smooth(who="--track_smooth", **smooth_args(FLAGS))
         except ValueError as e:
             raise NotImplementedError(str(e).replace("--track_smooth: max_gap", "--track_smooth_gap"))
+    if getattr(FLAGS, "track_stitch", False):
+        # the stitching pass runs over the tracks of a finished clip
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--track_stitch needs --track: the pass runs over the tracks of a clip")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_stitch does not combine with --live: a fragment's successor is known only later - "
+                                      "the pass has no online form")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--track_stitch does not combine with --seq_nms: net.detect_video composes the two, the "
+                                      "script would need a further family of tracked twins")
+        if getattr(FLAGS, "tubelet", False):
+            raise NotImplementedError("--track_stitch does not combine with --tubelet: net.detect_video composes the two, the "
+                                      "script keeps one extra family of files at a time")
+        if getattr(FLAGS, "track_smooth", False):
+            raise NotImplementedError("--track_stitch does not combine with --track_smooth: net.detect_video composes the two, "
+                                      "the script keeps one extra family of files at a time")
+        from viddet_amd.stitch import check_params as check_stitch
+        try:
+            check_stitch(who="--track_stitch", **stitch_args(FLAGS))
+        except ValueError as e:
+            raise NotImplementedError(str(e).replace("--track_stitch: max_gap", "--track_stitch_gap")
+                                      .replace("--track_stitch: sigma_iou", "--track_stitch_iou"))
+    else:
+        for flag in ("track_stitch_gap", "track_stitch_iou"):
+            if getattr(FLAGS, flag, None) is not None:
+                raise NotImplementedError("--%s needs --track_stitch: it is a parameter of that pass" % flag)
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
     # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
     for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
@@ -803,6 +868,9 @@ def main(argv=None):
     smo = smooth_args(FLAGS)
     if smo is not None:
         seq_kw = dict(seq_kw, smooth=smo)
+    sti = stitch_args(FLAGS)
+    if sti is not None:
+        seq_kw = dict(seq_kw, stitch=sti)
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
@@ -810,7 +878,7 @@ def main(argv=None):
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None
-    if tub is not None or smo is not None:                                 # check_flags: one of the two at most
+    if tub is not None or smo is not None or sti is not None:              # check_flags: one of the three at most
         boxes, boxes_seq, tracks, tracks_seq, boxes_tub, tracks_tub = boxes
     elif trk is not None:
         boxes, boxes_seq, tracks, tracks_seq = boxes
@@ -862,13 +930,16 @@ def main(argv=None):
         save_and_evaluate(FLAGS, dataset, boxes_tub, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, tub=tail),
                           tub=tail)
         save_tracks(FLAGS, dataset, boxes_tub, tracks_tub, tub=tail)
+    if sti is not None:
+        # the plain rows under their stitched ids, last: pred_sti_trk, tracks_sti.txt, mot_sti.txt, hota_sti.txt
+        save_tracks(FLAGS, dataset, boxes, tracks_tub, tub="sti")
     return result
 
 
 def save_tracks(FLAGS, dataset, boxes, tracks, seq=False, tub=False):
     """--track: the twin of a prediction set - its files' lines with `,track` appended (every row, -1 too) - and one line
     `clip tracks rows mean_len` per clip in tracks.txt / tracks_seq.txt (tub: pred_tub_trk, tracks_tub.txt; 'smo':
-    pred_smo_trk, tracks_smo.txt)"""
+    pred_smo_trk, tracks_smo.txt; 'sti': the plain rows under the ids of --track_stitch, pred_sti_trk, tracks_sti.txt)"""
     save_dir = pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=seq, trk=True, tub=tub)
     os.makedirs(save_dir, exist_ok=True)
     n = len(dataset) if FLAGS.max_do < 0 else min(FLAGS.max_do, len(dataset))

@@ -857,6 +857,37 @@ int vd_track_smooth_stages(const float* ids, const float* scores, const float* b
                            const int32_t* clip_start, int V, int F, int N, int num_class, int max_gap, float* out_sbox,
                            int32_t* out_slen, void* ws, int64_t ws_bytes, int stages, void* stream);
 
+/* ---- The track fragments of video clips re-linked across long gaps (vd_track_stitch.hip): what
+ * viddet_amd.stitch.stitch_host computes, bit for bit, on all five outputs.  ids, scores, bboxes, clip_start, V, F, N,
+ * num_class: as vd_seq_nms takes them; track [F][N] int32: the out_track of vd_track / vd_track_sort / vd_track_byte (any table
+ * is safe).  Per clip [t0, t1):
+ *   1. members: vd_track_smooth's step 1; a track is an id with at least one member;
+ *   2. participants: the tracks in ascending id, the first VD_TRACK_STITCH_MAX_TRACKS of them; the others enter no link, keep
+ *      their id, length and maximum and are counted in out_overflow[clip];
+ *   3. a participant's tail: the Kalman filter of vd_track_sort run over all its members (start at the first member's box,
+ *      predict once per frame between two members, update with every member's box), with the last member's frame and class;
+ *      its head: the first member's input box, frame and class;
+ *   4. tail a and head b are admissible iff a != b, 1 <= g = head frame - tail frame <= max_gap, the classes are equal and
+ *      iou(the box of a's state after g predictions, b's box) >= sigma_iou (vd_seq_nms's fp32 IoU, the track side first); the
+ *      links are the minimum-cost assignment of vd_track_sort over the admissible pairs at cost 2^20 - int(iou * 2^20), a dummy
+ *      column per row at 2^27, rows (tails) and columns (heads) in ascending id; entered only with two or more participants;
+ *   5. out_track [F][N] int32: the id of the first track of the row's chain of links, out_len [F][N] int32: the members of the
+ *      chain, out_score [F][N]: its maximum score (`if s > m: m = s` over a track's members in frame order, then over the chain's
+ *      tracks in chain order); -1 / 0 / -1 for a row that is no member and for every row of a frame that no clip covers.
+ *      out_stitches [V] int32: the links of every clip; out_overflow [V] int32: its tracks beyond the participants.
+ * All five outputs are written in full.  ws holds VD_TRACK_STITCH_WS_PER_ROW bytes per (frame, row): the member id of the row and
+ * 24 words per track id (a clip's ids lie in [0, (t1 - t0) * N)).  Two launches (one without clip_start): fill, then one
+ * workgroup per clip.  1 <= N <= 128, F >= 1, F * N < 2^31, V >= 1, num_class >= 1, 1 <= max_gap <= VD_TRACK_STITCH_MAX_GAP,
+ * sigma_iou not NaN; bboxes 16-byte, every other pointer 4-byte aligned.  The inputs are never written.  No atomics,
+ * bit-reproducible.  vd_track_stitch_ws_bytes: the bytes ws must hold, -1 for sizes that are not taken. */
+#define VD_TRACK_STITCH_MAX_TRACKS 512
+#define VD_TRACK_STITCH_MAX_GAP 32
+#define VD_TRACK_STITCH_WS_PER_ROW 100
+int64_t vd_track_stitch_ws_bytes(int F, int N);
+int vd_track_stitch(const float* ids, const float* scores, const float* bboxes, const int32_t* track, const int32_t* clip_start,
+                    int V, int F, int N, int num_class, int max_gap, float sigma_iou, int32_t* out_track, int32_t* out_len,
+                    float* out_score, int32_t* out_stitches, int32_t* out_overflow, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- The per-frame matching of the MOT tracking metric (vd_mot_eval.hip): what
  * viddet_amd.mot_metric.mot_match_host computes, bit for bit, on all four outputs.  gt_boxes [F][G][4] fp32, gt_cls, gt_id
  * [F][G] int32: the label rows (corner boxes, class, ground-truth track id); ids, scores, bboxes, clip_start, V, F, N, num_class: as

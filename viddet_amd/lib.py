@@ -24,6 +24,8 @@ TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per cli
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 TRACK_SMOOTH_WS_PER_ROW = 80                        # vd_track_smooth: workspace bytes per (frame, row) (VD_TRACK_SMOOTH_WS_PER_ROW)
+STITCH_MAX_TRACKS, STITCH_MAX_GAP = 512, 32         # vd_track_stitch: participants per clip, frames of a gap (vd_track_stitch.hip)
+TRACK_STITCH_WS_PER_ROW = 100                       # vd_track_stitch: workspace bytes per (frame, row) (VD_TRACK_STITCH_WS_PER_ROW)
 MOT_MAX_ROWS = 128                                 # vd_mot_match: label rows and prediction rows per frame (vd_mot_eval.hip)
 MOT_WS_PER_ROW = 4                                  # vd_mot_match: workspace bytes per (frame, row) of either side (VD_MOT_WS_PER_ROW)
 HOTA_MAX_GT_IDS = 1024                              # vd_hota_match: dense ground-truth ids per clip (vd_hota_eval.hip)
@@ -224,6 +226,9 @@ SIGNATURES = {
     "vd_track_smooth_ws_bytes": (_i64, [_i, _i]),
     "vd_track_smooth": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vd_track_smooth_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _i, _p]),
+    # track fragments re-linked across long gaps: filter tails extrapolated, matched to heads (vd_track_stitch.hip)
+    "vd_track_stitch_ws_bytes": (_i64, [_i, _i]),
+    "vd_track_stitch": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _i64, _p]),
     # the per-frame matching of the MOT tracking metric on the device (vd_mot_eval.hip)
     "vd_mot_match_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_mot_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _p, _p, _p, _p, _i64, _p]),

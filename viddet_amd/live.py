@@ -13,6 +13,7 @@ import torch
 from . import ops
 from .seq_nms import parse_option as parse_seq_nms
 from .smooth import parse_option as parse_smooth
+from .stitch import parse_option as parse_stitch
 from .stream import StreamPlanner
 from .track import parse_option as parse_track
 from .tubelet import parse_option as parse_tubelet
@@ -120,10 +121,10 @@ def _follow(rows, perm):
     return torch.where(perm >= 0, old, torch.full_like(old, -1))
 
 
-def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None):
+def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None):
     """YOLOV3.detect_video (its docstring is the description): a clip whose end is known is one push and one flush of the
-    planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> smooth -> tubelet on the
-    finished clip."""
+    planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> stitch -> smooth ->
+    tubelet on the finished clip."""
     why = net._stream_refusal()
     if why is not None:
         raise NotImplementedError("detect_video with " + why)
@@ -134,9 +135,11 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
     trk = parse_track(track, net.post_nms, "detect_video")
     tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
     smo_kw = parse_smooth(smooth, trk is not None, "detect_video")
+    sti_kw = parse_stitch(stitch, trk is not None, "detect_video")
     net.last_tracks = net.last_track_boxes = None
     net.last_tubelet = net.last_pre_tubelet = None
     net.last_smooth = net.last_pre_smooth = None
+    net.last_stitch = net.last_pre_stitch = None
     if net._k > 1:
         net._stream_split()                                       # the graph's own word, before anything touches the GPU
     step, chunk = int(step), int(chunk)
@@ -166,6 +169,10 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
             net.last_tracks = tuple(links)
         else:
             net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if sti_kw is not None:                                    # the fragments re-linked: the later passes take these ids
+            net.last_pre_stitch = net.last_tracks
+            *links, stitches, overflow = ops.stitch(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **sti_kw)
+            net.last_tracks, net.last_stitch = tuple(links), (stitches, overflow)
         if smo_kw is not None:                                    # the boxes the tracker saw, smoothed along its tracks
             net.last_pre_smooth = boxes
             boxes, net.last_smooth = ops.smooth(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **smo_kw)

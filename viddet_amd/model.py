@@ -2241,7 +2241,7 @@ class YOLOV3(object):
         if n < dst.shape[0]:
             dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
 
-    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None):
+    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None):
         """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
         (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
         (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
@@ -2282,9 +2282,17 @@ class YOLOV3(object):
         estimated from the frames before and after it; a track is cut where it skips more than max_gap frames).  The order is
         Seq-NMS -> track -> smooth -> tubelet: the smoothed boxes replace the tracker's in what is returned and in what the
         tubelet pass gets; ids and scores are untouched.  last_pre_smooth holds the boxes ahead of the pass, last_smooth its
-        slen (T,post_nms); both are None after a call without it.  last_tracks and last_track_boxes are as without it."""
+        slen (T,post_nms); both are None after a call without it.  last_tracks and last_track_boxes are as without it.
+
+        stitch: None (the default), True, or {'max_gap': g, 'sigma_iou': s}; needs `track` - the fragments a tracker leaves
+        where an object was missed for more than max_age frames are re-linked on the device (ops.stitch, DESIGN.md 38: every
+        track's filter state at its last row is extrapolated over up to max_gap frames and matched to the first rows of later
+        tracks).  The order is Seq-NMS -> track -> stitch -> smooth -> tubelet, so the later passes take the stitched table.
+        last_pre_stitch holds the tracker's (track, tlen, tscore), last_tracks the stitched triple, last_stitch = (stitches,
+        overflow), each (1,); last_track_boxes stays the tracker's.  A call without it sets last_stitch and last_pre_stitch to
+        None.  open_video takes no such argument: a fragment's successor is known only later."""
         from .live import detect_video
-        return detect_video(self, frames, step, chunk, seq_nms, track, tubelet, smooth)
+        return detect_video(self, frames, step, chunk, seq_nms, track, tubelet, smooth, stitch)
 
     def open_video(self, step=1, chunk=8, track=None):
         """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and
@@ -2292,7 +2300,8 @@ class YOLOV3(object):
         the clip.  Refused where detect_video is, in the same words, and while another session of this net has
         frames in flight.  Seq-NMS has no online form and is no option here; nor is the tubelet pass: a hole is
         known only once its track resumes, after the frame has been given out.  The `smooth` option of detect_video (DESIGN.md
-        37) is none here either: a frame's smoothed box needs the frames after it.  track={'method': 'sort'} and
+        37) is none here either: a frame's smoothed box needs the frames after it; nor is `stitch`: a fragment's
+        successor is known only later.  track={'method': 'sort'} and
         track={'method': 'byte'} raise NotImplementedError: SORT and BYTE have no resumable form yet."""
         if self._live is not None:
             raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))

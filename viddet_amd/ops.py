@@ -845,6 +845,61 @@ def smooth(ids, scores, bboxes, track, clip_start=None, num_class=1, max_gap=7, 
     return sbox, slen
 
 
+def stitch(ids, scores, bboxes, track, clip_start=None, num_class=1, max_gap=30, sigma_iou=0.3, ws=None):
+    """vd_track_stitch (viddet_amd/stitch.py::stitch_host on the device, bit for bit, DESIGN.md 38): ids (F,N[,1]), scores
+    (F,N[,1]) and bboxes (F,N,4) are contiguous fp32 device tensors, N <= 128; track (F,N) a contiguous int32 device tensor, the
+    first result of ops.track / ops.track_sort / ops.track_byte; clip_start as ops.seq_nms takes it.  Returns (strack, tlen,
+    tscore, stitches, overflow), new device tensors: (F,N) int32, int32 and fp32 - the id of the first track of the row's chain
+    of re-linked fragments, the chain's members and its maximum score, -1 / 0 / -1 for a row in no track - and (V,) int32 twice,
+    the links of every clip and its tracks beyond the first 512, which enter no link.  Launches on the current stream; nothing
+    is downloaded and nothing waits.  ws: a uint8 device tensor of >= 100*F*N bytes to reuse, else one is allocated."""
+    from .stitch import check_params
+    max_gap, sigma_iou = check_params(max_gap, sigma_iou, "stitch")
+    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("stitch: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.TUBELET_MAX_ROWS:
+        raise ValueError("stitch: N=%d rows per frame, vd_track_stitch takes at most %d" % (N, L.TUBELET_MAX_ROWS))
+    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
+        raise ValueError("stitch: num_class must be an integer >= 1, got %r" % (num_class,))
+    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
+                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("stitch: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if tuple(track.shape) != (F, N):
+        raise ValueError("stitch: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("stitch: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("stitch: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    need = L.TRACK_STITCH_WS_PER_ROW * F * N
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("stitch: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    dev = bboxes.device
+    strack = torch.empty(F, N, dtype=torch.int32, device=dev)
+    tlen = torch.empty(F, N, dtype=torch.int32, device=dev)
+    tscore = torch.empty(F, N, dtype=torch.float32, device=dev)
+    stitches = torch.empty(V, dtype=torch.int32, device=dev)
+    overflow = torch.empty(V, dtype=torch.int32, device=dev)
+    if F == 0 or N == 0:
+        return strack, tlen, tscore, stitches.zero_(), overflow.zero_()
+    check(_lib().vd_track_stitch(ptr(ids), ptr(scores), ptr(bboxes), ptr(track), ptr(clip_start), V, F, N, int(num_class), max_gap,
+                                 float(sigma_iou), ptr(strack), ptr(tlen), ptr(tscore), ptr(stitches), ptr(overflow), ptr(ws),
+                                 int(ws.numel()), _s()), "vd_track_stitch")
+    return strack, tlen, tscore, stitches, overflow
+
+
 def mot_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, clip_start=None, num_class=1, iou_thresh=0.5, agnostic=False,
               ws=None):
     """vd_mot_match (viddet_amd/mot_metric.py::mot_match_host on the device, bit for bit, DESIGN.md 33): gt_boxes (F,G,4) fp32,

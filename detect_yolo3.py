@@ -21,7 +21,8 @@ reference counterpart) links the detections of every clip into tracks on the dev
 set gets a twin, pred_trk / pred_seq_trk, whose lines end in the row's track id, and tracks.txt / tracks_seq.txt count them per
 clip; everything else is written as without the flag; `--track_method sort` links them with SORT instead (vd_track_sort, DESIGN.md
 34; not with --live), `--track_method byte` with BYTE, SORT with a second association of the low-score rows (vd_track_byte,
-DESIGN.md 36; not with --live).  `--live` (with --stream; no reference counterpart) sends every clip
+DESIGN.md 36; not with --live); `--track_online` lifts both refusals: the live session then carries the SORT or BYTE tracker
+itself from push to push (vd_track_kf_push).  `--live` (with --stream; no reference counterpart) sends every clip
 through a live session (net.open_video) in pushes of --live_push frames and a flush, as a camera would hand it over:
 the files and results are those of --stream byte for byte.  `--tubelet` (with --track; no reference counterpart) runs a tubelet
 pass over every tracked clip on the device (vd_tubelet) - a track's rows take its score, the frames it skipped get
@@ -161,7 +162,12 @@ def parse_flags(argv=None):
            "(vd_track_byte, DESIGN.md 36): BYTE of Zhang et al. 2022 - SORT with two associations a frame: the boxes scored at "
            "least --track_det first, then the tracks left over against the lower-scored boxes, which never start a track, so a "
            "track survives a dip of its object's score and low-score clutter starts none.  The same files are written.  sort and "
-           "byte: not with --live")
+           "byte: not with --live, unless --track_online is given")
+    A("--track_online", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --stream --live --track --track_method sort|byte: the live session carries that "
+           "tracker from push to push on the device (net.open_video(track={..., 'online': True}), vd_track_kf_push, DESIGN.md "
+           "39); the files and results are those of the --stream run byte for byte.  Not without --live and not with "
+           "--track_method iou, whose tracker is always online")
     A("--track_iou", type=float, default=None,
       help="--track: a box joins a track where its IoU to the track's last box (sort, byte: its predicted box) is at least this "
            "(default: iou 0.5, sort 0.3, byte 0.2)")
@@ -403,32 +409,38 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
 def live_clip(net, frames, step, chunk, push, track=None):
     """--live: detect_video(frames, step, chunk, track) by way of a live session - pushes of `push` frames, then a flush ->
     (ids, scores, bboxes, the (track, tlen, tscore) of detect_video's last_tracks or None).  The session's online tracker
-    decides nothing; finalize_tracks decides at the clip's end, from the rows the session gave out."""
+    decides nothing; finalize_tracks decides at the clip's end, from the rows the session gave out.  Where the session keeps
+    the filtered boxes of its rows (track with 'method': 'sort' or 'byte' and 'online': True), they are collected too and a
+    fourth array, detect_video's last_track_boxes, ends the tuple."""
     session = net.open_video(step=step, chunk=chunk, track=track)
-    outs, trks = [], []
+    outs, trks, tboxes = [], [], []
     for a in range(0, frames.shape[0], push):
         outs.append(session.push(frames[a:a + push])[1:])
         trks.append(session.last_tracks)
+        tboxes.append(session.last_track_boxes)
     outs.append(session.flush()[1:])
     trks.append(session.last_tracks)
+    tboxes.append(session.last_track_boxes)
     ids, scores, bboxes = (torch.cat(t) for t in zip(*outs))
     assert ids.shape[0] == frames.shape[0], "the session gave out %d of %d frames" % (ids.shape[0], frames.shape[0])
     if track is None:
         return ids, scores, bboxes, None
     from viddet_amd.track import finalize_tracks
     online = [torch.cat(t).cpu().numpy() for t in zip(*trks)]
-    final = finalize_tracks(*online, **session.track_decide)
+    tbox = None if tboxes[0] is None else torch.cat(tboxes).cpu().numpy()
+    final = finalize_tracks(*online, tbox=tbox, **session.track_decide)
     return ids, scores, bboxes, tuple(torch.from_numpy(a) for a in final)
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None):
+                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None, track_online=False):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
     ones detect_video keeps in net.last_plain.  track (a dict): handed to detect_video too, which links the rows it returns;
     the plain rows ahead of Seq-NMS are linked by a call of their own; returns (boxes, rescored or None, tracks, tracks of the
-    rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead.  tubelet (a dict,
+    rescored or None).  live (--live_push, a number of frames): every clip goes through live_clip instead, with track_online
+    (--track_online) on a session that carries the SORT or BYTE tracker of `track` itself.  tubelet (a dict,
     with track, without seq_nms and live): handed to detect_video as well; the plain rows are the ones it keeps in
     net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element.  smooth
     (a dict, with track, without seq_nms, live and tubelet): handed to detect_video likewise; the plain boxes are the ones it
@@ -450,7 +462,10 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         W = data_shape if device_resize else x.shape[-2]
         trk_kw = {} if track is None else dict(track=dict(track, clip=W))  # the tracker sees the boxes as they are saved too
         if live is not None:
-            ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, trk_kw.get("track"))
+            live_trk = trk_kw.get("track")
+            if track_online and live_trk is not None:                      # the session carries the method's own tracker
+                live_trk = dict(live_trk, online=True)
+            ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, live_trk)
             if track is not None:
                 _collect_tracks(tracks, dataset, ids, last[0], sidxs)
         elif tubelet is not None:
@@ -582,9 +597,17 @@ def check_flags(FLAGS):
             if getattr(FLAGS, "track_method", "iou") != "byte" and getattr(FLAGS, flag, None) is not None:
                 raise NotImplementedError("--%s belongs to --track_method byte: --track_method %s has no such threshold"
                                           % (flag, getattr(FLAGS, "track_method", "iou")))
-        if getattr(FLAGS, "track_method", "iou") != "iou" and getattr(FLAGS, "live", False):
+        if getattr(FLAGS, "track_method", "iou") != "iou" and getattr(FLAGS, "live", False) and not getattr(FLAGS, "track_online", False):
             raise NotImplementedError("--track_method %s does not combine with --live: it has no resumable form yet, a live "
                                       "session carries the iou tracker only" % FLAGS.track_method)
+        if getattr(FLAGS, "track_online", False):
+            # the resumable form of sort and byte is a live session's: refused elsewhere, never ignored
+            if not getattr(FLAGS, "live", False):
+                raise NotImplementedError("--track_online needs --live: it makes the live session (net.open_video) carry the "
+                                          "--track_method's tracker; without --live every clip is tracked at its end")
+            if getattr(FLAGS, "track_method", "iou") == "iou":
+                raise NotImplementedError("--track_online does not combine with --track_method iou: that tracker is always "
+                                          "online in a live session; the flag belongs to --track_method sort and byte")
         from viddet_amd.byte import check_byte_params
         from viddet_amd.track import check_params
         try:
@@ -597,6 +620,8 @@ def check_flags(FLAGS):
             for k, flag in names.items():
                 msg = msg.replace("--track: " + k, flag)
             raise NotImplementedError(msg)
+    elif getattr(FLAGS, "track_online", False):
+        raise NotImplementedError("--track_online needs --track: it chooses how a live session carries the tracker")
     if getattr(FLAGS, "tubelet", False):
         # the tubelet pass runs over the tracks of a finished clip
         if not getattr(FLAGS, "track", False):
@@ -874,7 +899,7 @@ def main(argv=None):
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
-                              live=FLAGS.live_push if FLAGS.live else None, **seq_kw)
+                              live=FLAGS.live_push if FLAGS.live else None, track_online=FLAGS.track_online, **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None

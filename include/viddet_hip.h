@@ -978,6 +978,31 @@ int vd_track_byte(const float* ids, const float* scores, const float* bboxes, co
                   int t_min, int max_age, int32_t* out_track, int32_t* out_len, float* out_score, float* out_tbox, void* ws,
                   int64_t ws_bytes, void* stream);
 
+/* ---- The Kalman trackers in resumable form, for streams of frames that never say where they end (vd_track_kf_live.hip, DESIGN.md
+ * 39): what viddet_amd.byte.byte_online_host computes, bit for bit, on all four outputs - and, with sigma_d = sigma_new =
+ * sigma_l (the low list is then empty, the second association never entered, sigma_iou2 unused: pass sigma_iou), what
+ * viddet_amd.sort.sort_online_host computes.  One launch runs vd_track_byte's frame body - predict, the two associations,
+ * update, start - with the same arithmetic and tie rules on the F frames of V streams - ids, scores [V][F][N], bboxes
+ * [V][F][N][4] - starting from each stream's state and leaving the new state behind; nothing is decided on the device, so
+ * sigma_h and t_min are no arguments (track.finalize_tracks decides on the host, once a clip has ended).  state: V blocks of
+ * VD_TRACK_KF_STATE_BYTES, each
+ *   int32 n_active, next_id, cur, unused (16 bytes); int32 class[1024], id[1024], misses[1024], length[1024], float
+ *   maximum[1024] - the active tracks in order of creation, the first n_active entries live; float table[2][17][1024] - their
+ *   filter states, field-major, table `cur` current.
+ * A block of all zero bytes is a fresh stream; n_active is clamped into [0, 1024] and cur into {0, 1} before either indexes
+ * anything; the filter tables are used in place; the live words and the header are written back with ordinary stores.  Outputs,
+ * written in full, [V][F][N]: out_track int32 (the row's track id, a creation number counted over the whole stream from 0, one
+ * counter for all classes; -1 for a row that is no candidate or that neither found nor started a track), out_len int32 (the rows
+ * of its track so far, this one included; 0 beside -1), out_score (the track's maximum score so far; -1 beside -1), out_tbox
+ * [V][F][N][4] (the posterior box of the row's track after this row's update; -1 beside -1).  A stream hands out at most N ids
+ * per frame: the caller keeps frames * N below 2^31.  One workgroup of 256 threads per stream, 51,344 bytes of LDS, no workspace,
+ * no atomics, bit-reproducible; the inputs are never written.  1 <= N <= 128, F >= 1, V >= 1, num_class >= 1, 0 <= max_age <= 7,
+ * no threshold NaN; bboxes, out_tbox and state 16-byte, every other pointer 4-byte aligned. */
+#define VD_TRACK_KF_STATE_BYTES 159760
+int vd_track_kf_push(const float* ids, const float* scores, const float* bboxes, int V, int F, int N, int num_class, float sigma_l,
+                     float sigma_d, float sigma_new, float sigma_iou, float sigma_iou2, int max_age, void* state,
+                     int64_t state_bytes, int32_t* out_track, int32_t* out_len, float* out_score, float* out_tbox, void* stream);
+
 /* ---- The per-frame matching of the HOTA tracking metric (vd_hota_eval.hip): what
  * viddet_amd.hota_metric.hota_match_host computes, bit for bit, on all three outputs - Luiten et al., "HOTA: A Higher Order
  * Metric for Evaluating Multi-Object Tracking" (IJCV 2021).  The inputs are vd_mot_match's; the ids are dense: a ground-truth row

@@ -38,13 +38,17 @@ Stated departures from the ByteTrack code: the filter is Bewley's (SORT's), not 
 there is no score fusion into the cost; there is no "unconfirmed" stage, because t_min decides at the clip's end; only admissible
 pairs enter the assignment; tracks are per class; a lost track's velocity is not zeroed beyond kf_predict's own `s + ds <= 0` rule.
 
+`byte_online_host` is steps 1 to 5 on a stream that never says where it ends, a state carried from call to call (DESIGN.md 39;
+vd_track_kf_push, `ops.KalmanTrackState`, equals it bit for bit); track.finalize_tracks is step 6 on its rows, once a clip has
+ended.
+
 This module imports NumPy only.
 """
 import numpy as np
 
 from .mot_metric import FORBIDDEN, assign_host
 from .seq_nms import _clips, row_classes
-from .sort import _KEYS, association_cost, kf_box, kf_cat, kf_predict, kf_start, kf_take, kf_update, measure, new_state
+from .sort import _KEYS, association_cost, kf_box, kf_cat, kf_predict, kf_start, kf_take, kf_update, measure, new_state, online_rows
 from .track import check_params
 
 _F = np.float32
@@ -181,3 +185,31 @@ def byte_host(ids, scores, bboxes, clip_start=None, num_class=None, sigma_l=0.1,
         stats["active"], stats["closed"], stats["tracks"] = n_active, n_closed, kept_per_clip
         stats["first"], stats["second"] = n_first, n_second
     return track, tlen, tscore, tbox
+
+
+def byte_online_host(state, ids, scores, bboxes, num_class=None, sigma_l=0.1, sigma_d=0.5, sigma_new=0.6, sigma_iou=0.2,
+                     sigma_iou2=0.5, max_age=7, stats=None):
+    """BYTE on a stream that never says where it ends (vd_track_kf_push, `ops.KalmanTrackState`, equals it bit
+    for bit): byte_host's frame loop on byte_step, unchanged, on the given frames, starting from `state` (None: a fresh stream;
+    else an earlier call's, which is not changed) -> (the new state, track, tlen, tscore, tbox), per row as
+    sort.sort_online_host gives them: the id counted over the whole stream, the length and the maximum so far, the posterior
+    box.  Nothing is decided here, so sigma_h and t_min are no arguments: track.finalize_tracks(..., tbox=) makes byte_host's
+    arrays of a finished clip's rows.  Pushing a clip in pieces gives what one call on all of it gives; where sigma_d =
+    sigma_new = sigma_l it is sort_online_host.  `stats`, a dict, receives per frame 'active', 'closed', 'first' and 'second'."""
+    sl, sd, sn, si, si2, _, _, max_age = check_byte_params(sigma_l, sigma_d, sigma_new, sigma_iou, sigma_iou2, 0.5, 1, max_age,
+                                                           "byte_online_host")
+    sc, cls, bboxes = online_rows(ids, scores, bboxes, num_class, sl)
+    F, N = sc.shape
+    track = np.full((F, N), -1, dtype=np.int32)
+    tlen = np.zeros((F, N), dtype=np.int32)
+    tscore = np.full((F, N), -1, dtype=_F)
+    tbox = np.full((F, N, 4), -1, dtype=_F)
+    counts = np.zeros((4, F), dtype=np.int64)                     # active, closed, first, second
+    state = new_state() if state is None else state
+    for t in range(F):
+        state, track[t], tlen[t], tscore[t], tbox[t], counts[1, t], counts[2, t], counts[3, t] = byte_step(
+            state, cls[t], sc[t], bboxes[t], sd, sn, si, si2, max_age)
+        counts[0, t] = len(state["id"])
+    if stats is not None:
+        stats["active"], stats["closed"], stats["first"], stats["second"] = counts
+    return state, track, tlen, tscore, tbox

@@ -21,6 +21,7 @@ TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes 
 TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of one stream's state (VD_TRACK_STATE_BYTES)
 TRACK_SORT_WS_PER_ROW = 8                           # vd_track_sort: workspace bytes per (frame, row) (VD_TRACK_SORT_WS_PER_ROW)
 TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per clip, two tables of 17 x 1024 state floats
+TRACK_KF_STATE_BYTES = 159760                       # vd_track_kf_push: bytes of one stream's state (VD_TRACK_KF_STATE_BYTES)
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 TRACK_SMOOTH_WS_PER_ROW = 80                        # vd_track_smooth: workspace bytes per (frame, row) (VD_TRACK_SMOOTH_WS_PER_ROW)
@@ -218,6 +219,8 @@ SIGNATURES = {
     # ... and by BYTE: a second association of the low-score rows (vd_track_byte.hip); the workspace is vd_track_sort's
     "vd_track_byte_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_track_byte": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    # the two resumable: tracks and filter states carried from launch to launch in a state block (vd_track_kf_live.hip)
+    "vd_track_kf_push": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _p, _i64, _p, _p, _p, _p, _p]),
     # tubelet rescoring and gap filling over the tracks of video clips (vd_tubelet.hip)
     "vd_tubelet_ws_bytes": (_i64, [_i, _i]),
     "vd_tubelet": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),

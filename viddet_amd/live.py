@@ -6,7 +6,8 @@ that are final by now, `flush()` ends the clip.  Over any way of cutting a clip 
 concatenated results are torch.equal to `net.detect_video(clip, step, chunk)`: both run the one engine, in exactly the
 launch groups stream.StreamPlanner forms - the fp32 operand scales are per tensor, so any other grouping would round
 differently.  With `track`, the emitted rows go through a resumable tracker on the device
-(ops.TrackState, vd_track_push) whose state survives from push to push.
+(ops.TrackState, vd_track_push; with track={'method': 'sort' | 'byte', 'online': True} ops.KalmanTrackState, vd_track_kf_push,
+DESIGN.md 39) whose state survives from push to push.
 """
 import torch
 
@@ -16,6 +17,7 @@ from .smooth import parse_option as parse_smooth
 from .stitch import parse_option as parse_stitch
 from .stream import StreamPlanner
 from .track import parse_option as parse_track
+from .track import split_online
 from .tubelet import parse_option as parse_tubelet
 
 
@@ -206,8 +208,13 @@ class VideoSession:
     frames is pushed to an ops.TrackState; last_tracks = (track, tlen, tscore), each (m,post_nms), is track_online_host's
     triple for those frames: ids counted over the clip, lengths and maxima so far.  Nothing is decided online: sigma_h and
     t_min (kept in track_decide) are for track.finalize_tracks on the concatenated triples of the finished clip, which gives
-    detect_video(track=...)'s last_tracks.  The session carries the IOU tracker only: track={'method': 'sort'}
-    and track={'method': 'byte'} have no resumable form yet and raise NotImplementedError.
+    detect_video(track=...)'s last_tracks.  Without a further word the session carries the IOU tracker only:
+    track={'method': 'sort'} and track={'method': 'byte'} raise NotImplementedError.  With
+    'online': True in the dict (a bool; open_video's word alone, detect_video does not take it) the session carries that
+    tracker: the emitted frames go to an ops.KalmanTrackState (vd_track_kf_push), last_tracks is the triple of
+    sort_online_host / byte_online_host and last_track_boxes (None for 'iou') their tbox (m,post_nms,4);
+    finalize_tracks(*triples, tbox=boxes, **track_decide) on the finished clip gives detect_video's last_tracks and
+    last_track_boxes.  'method': 'iou' with 'online': True is the session as ever: that tracker is always online.
 
     Seq-NMS is not a session option: it takes the best path through ALL frames of a clip, removes it and starts again until no
     row is alive, so no frame is final before the clip ends - it has no online form.  Run detect_video(seq_nms=...) on the
@@ -226,12 +233,14 @@ class VideoSession:
             raise ValueError("open_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
         self.track_decide = None
         self._trk_kw = self._trk_clip = self._trk = None
+        self._trk_method = "iou"
+        track, online = split_online(track, "open_video")
         trk = parse_track(track, net.post_nms, "open_video")
         if trk is not None:
-            if trk[2] != "iou":
+            if trk[2] != "iou" and not online:
                 raise NotImplementedError("open_video with track method %r: it has no resumable form yet, only 'iou' has "
                                           "(run detect_video on the finished clip)" % (trk[2],))
-            self._trk_kw, self._trk_clip = trk[:2]
+            self._trk_kw, self._trk_clip, self._trk_method = trk
             self.track_decide = dict(sigma_h=self._trk_kw.pop("sigma_h"), t_min=self._trk_kw.pop("t_min"))
         if net._k > 1:
             net._stream_split()                                   # the graph's own word, before anything touches the GPU
@@ -243,7 +252,7 @@ class VideoSession:
         self._shape = None                                        # (shape of a frame, dtype), fixed by the clip's first push
         self._hw = None
         self.frames_out = 0
-        self.last_rows = self.last_overflow = self.last_tracks = None
+        self.last_rows = self.last_overflow = self.last_tracks = self.last_track_boxes = None
 
     def __repr__(self):
         return "<VideoSession step=%d chunk=%d: %d frames in, %d out>" % (self.step, self.chunk, self.frames_in, self.frames_out)
@@ -263,9 +272,18 @@ class VideoSession:
         self.last_rows, self.last_overflow = out['rows'], out['overflow']
         if self._trk_kw is not None:
             if self._trk is None:
-                self._trk = ops.TrackState(1, net.post_nms, 1 if net.agnostic else net.num_class, device=net.device, **self._trk_kw)
+                num_class = 1 if net.agnostic else net.num_class
+                if self._trk_method == "iou":
+                    self._trk = ops.TrackState(1, net.post_nms, num_class, device=net.device, **self._trk_kw)
+                else:                                             # SORT, BYTE: the filter states travel with the tracks
+                    self._trk = ops.KalmanTrackState(1, net.post_nms, num_class, method=self._trk_method, device=net.device,
+                                                     **self._trk_kw)
             boxes = out['bboxes'] if self._trk_clip is None else out['bboxes'].clamp(0, float(self._trk_clip))
-            self.last_tracks = self._trk.push(out['ids'], out['scores'], boxes)
+            if self._trk_method == "iou":
+                self.last_tracks = self._trk.push(out['ids'], out['scores'], boxes)
+            else:                                                 # the triple as ever, the filtered boxes beside it
+                *links, self.last_track_boxes = self._trk.push(out['ids'], out['scores'], boxes)
+                self.last_tracks = tuple(links)
         t0 = self.frames_out
         self.frames_out += out['ids'].shape[0]
         return t0, out['ids'], out['scores'], out['bboxes']

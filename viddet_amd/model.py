@@ -2302,7 +2302,9 @@ class YOLOV3(object):
         known only once its track resumes, after the frame has been given out.  The `smooth` option of detect_video (DESIGN.md
         37) is none here either: a frame's smoothed box needs the frames after it; nor is `stitch`: a fragment's
         successor is known only later.  track={'method': 'sort'} and
-        track={'method': 'byte'} raise NotImplementedError: SORT and BYTE have no resumable form yet."""
+        track={'method': 'byte'} raise NotImplementedError unless the dict also says 'online': True (a bool, this method's
+        word alone): the session then carries that tracker from push to push on the device (ops.KalmanTrackState, DESIGN.md
+        39) and keeps the filtered boxes of the emitted frames in session.last_track_boxes."""
         if self._live is not None:
             raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))
         from .live import VideoSession

@@ -1089,6 +1089,84 @@ class TrackState:
         return out_track, out_len, out_score
 
 
+class KalmanTrackState:
+    """SORT or BYTE on V streams that never say where they end (vd_track_kf_push; viddet_amd/sort.py::sort_online_host and
+    viddet_amd/byte.py::byte_online_host on the device, bit for bit, DESIGN.md 39): owns the state tensor
+    (V, VD_TRACK_KF_STATE_BYTES) uint8 - the tracks' words and their filter states; all zero is a fresh stream - and the fixed
+    parameters: method 'sort' (sigma_l, sigma_iou, max_age; sort.DEFAULTS where left out) or 'byte' (sigma_l, sigma_d,
+    sigma_new, sigma_iou, sigma_iou2, max_age; byte.DEFAULTS), without sigma_h and t_min, since nothing is decided online.
+    push(ids, scores, bboxes) runs the next F frames of every stream, the tensors as TrackState.push takes them, ->
+    (track, tlen, tscore, tbox), new device tensors: TrackState's three and tbox of the leading shape + (N,4), the posterior
+    box of the row's track after this row's update (-1 beside a track of -1).  Launches on the current stream; nothing is
+    downloaded and nothing waits.  A push that could take frames * N past 2**31 - 1 is refused (counted on the host).  reset()
+    starts every stream afresh."""
+
+    def __init__(self, V=1, N=100, num_class=1, method="sort", device="cuda", **params):
+        who = "KalmanTrackState"
+        if method == "iou":
+            raise ValueError("%s: method 'iou' has no filter to carry: ops.TrackState is its resumable form" % who)
+        if method not in ("sort", "byte"):
+            raise ValueError("%s: method must be 'sort' or 'byte', got %r" % (who, method))
+        if method == "sort":
+            from .sort import DEFAULTS
+        else:
+            from .byte import DEFAULTS
+        names = [k for k in DEFAULTS if k not in ("sigma_h", "t_min")]
+        unknown = sorted(set(params) - set(names))
+        if unknown:
+            raise ValueError("%s: method %r takes %s, got %s" % (who, method, ", ".join(names), ", ".join(unknown)))
+        kw = dict({k: DEFAULTS[k] for k in names}, **params)
+        if method == "sort":
+            # SORT on BYTE's frame body: every candidate is a high row that may start a track, the second association never runs
+            from .track import check_params
+            sl, _, si, _, age = check_params(sigma_h=0.5, t_min=1, who=who, **kw)
+            sd, sn, si2 = sl, sl, si
+        else:
+            from .byte import check_byte_params
+            sl, sd, sn, si, si2, _, _, age = check_byte_params(sigma_h=0.5, t_min=1, who=who, **kw)
+        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
+                raise ValueError("%s: %s must be an integer in [1, %d], got %r" % (who, name, hi, v))
+        self.method, self.params = method, kw
+        self.sigma_l, self.sigma_d, self.sigma_new, self.sigma_iou, self.sigma_iou2 = (float(v) for v in (sl, sd, sn, si, si2))
+        self.max_age = age
+        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
+        self.state = torch.zeros(self.V, L.TRACK_KF_STATE_BYTES, dtype=torch.uint8, device=device)
+        self.frames = 0                               # pushed to every stream since the last reset
+
+    def reset(self):
+        self.state.zero_()
+        self.frames = 0
+
+    def push(self, ids, scores, bboxes):
+        V, N = self.V, self.N
+        lead = tuple(bboxes.shape[:-2])
+        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
+            raise ValueError("KalmanTrackState.push: bboxes must be (%d,F,%d,4)%s, got %r"
+                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
+        F = int(lead[-1])
+        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
+            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("KalmanTrackState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                                 % (name, n, t.dtype, tuple(t.shape)))
+        if (self.frames + F) * N > 2 ** 31 - 1:
+            raise ValueError("KalmanTrackState.push: %d + %d frames of %d rows could hand out more than 2**31 - 1 track ids; "
+                             "reset() the state (a new clip) first" % (self.frames, F, N))
+        dev = bboxes.device
+        out_track = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+        out_len = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
+        out_score = torch.empty(lead + (N,), dtype=torch.float32, device=dev)
+        out_tbox = torch.empty(lead + (N, 4), dtype=torch.float32, device=dev)
+        if F == 0:
+            return out_track, out_len, out_score, out_tbox
+        check(_lib().vd_track_kf_push(ptr(ids), ptr(scores), ptr(bboxes), V, F, N, self.num_class, self.sigma_l, self.sigma_d,
+                                      self.sigma_new, self.sigma_iou, self.sigma_iou2, self.max_age, ptr(self.state),
+                                      int(self.state.numel()), ptr(out_track), ptr(out_len), ptr(out_score), ptr(out_tbox), _s()),
+              "vd_track_kf_push")
+        self.frames += F
+        return out_track, out_len, out_score, out_tbox
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

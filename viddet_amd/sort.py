@@ -43,6 +43,10 @@ Stated departures from Bewley's code: it solves the assignment over ALL pairs an
 afterwards, here only admissible pairs enter; tracks are per class; there is no min_hits gate on output - t_min and sigma_h
 decide at the clip's end, as track_host does.  The defaults sigma_iou 0.3 and max_age 1 are the paper's.
 
+`sort_online_host` is steps 1 to 4 on a stream that never says where it ends, a state carried from call to call (DESIGN.md 39;
+vd_track_kf_push, `ops.KalmanTrackState`, equals it bit for bit); track.finalize_tracks is step 5 on its rows, once a clip has
+ended.
+
 This module imports NumPy only.
 """
 import numpy as np
@@ -240,3 +244,47 @@ def sort_host(ids, scores, bboxes, clip_start=None, num_class=None, sigma_l=0.0,
     if stats is not None:
         stats["active"], stats["closed"], stats["tracks"] = n_active, n_closed, kept_per_clip
     return track, tlen, tscore, tbox
+
+
+def online_rows(ids, scores, bboxes, num_class, sigma_l):
+    """The frames of one push as (sc (F,N), cls (F,N) with -1 for a row that is no candidate, bboxes (F,N,4)), float32: what
+    sort_host and byte_host make of a clip"""
+    ids = np.asarray(ids, dtype=_F)
+    scores = np.asarray(scores, dtype=_F)
+    bboxes = np.asarray(bboxes, dtype=_F)
+    if bboxes.ndim != 3 or bboxes.shape[2] != 4 or ids.size != bboxes.shape[0] * bboxes.shape[1] or scores.size != ids.size:
+        raise ValueError("expected ids (F,N,1), scores (F,N,1), bboxes (F,N,4), got %r %r %r" % (ids.shape, scores.shape, bboxes.shape))
+    F, N = bboxes.shape[0], bboxes.shape[1]
+    sc = scores.reshape(F, N)
+    cls = row_classes(ids.reshape(F, N), sc, num_class)
+    with np.errstate(invalid="ignore"):
+        cls = np.where(sc >= sigma_l, cls, -1)
+    return sc, cls, bboxes
+
+
+def sort_online_host(state, ids, scores, bboxes, num_class=None, sigma_l=0.0, sigma_iou=0.3, max_age=1, stats=None):
+    """SORT on a stream that never says where it ends (vd_track_kf_push, `ops.KalmanTrackState`, equals it bit
+    for bit): sort_host's frame loop on sort_step, unchanged, on the given frames, starting from `state` (None: a fresh stream;
+    else an earlier call's, which is not changed) -> (the new state, track, tlen, tscore, tbox).  Per row, (F,N) and (F,N,4):
+    `track` int32, the id of the row's track - a creation number counted over the whole stream - or -1 for a row that is no
+    candidate; `tlen` int32, the rows of its track so far, this one included (0 beside -1); `tscore` float32, the track's
+    maximum score so far (-1 beside -1); `tbox` float32, the track's posterior box after this row's update (-1 beside -1).
+    Nothing is decided here, so sigma_h and t_min are no arguments: track.finalize_tracks(..., tbox=) makes sort_host's arrays
+    of a finished clip's rows.  Pushing a clip in pieces gives what one call on all of it gives.  `stats`, a dict, receives per
+    frame 'active' and 'closed'."""
+    sl, _, si, _, max_age = check_params(sigma_l, 0.5, sigma_iou, 1, max_age, "sort_online_host")
+    sc, cls, bboxes = online_rows(ids, scores, bboxes, num_class, sl)
+    F, N = sc.shape
+    track = np.full((F, N), -1, dtype=np.int32)
+    tlen = np.zeros((F, N), dtype=np.int32)
+    tscore = np.full((F, N), -1, dtype=_F)
+    tbox = np.full((F, N, 4), -1, dtype=_F)
+    n_active = np.zeros(F, dtype=np.int64)
+    n_closed = np.zeros(F, dtype=np.int64)
+    state = new_state() if state is None else state
+    for t in range(F):
+        state, track[t], tlen[t], tscore[t], tbox[t], n_closed[t] = sort_step(state, cls[t], sc[t], bboxes[t], si, max_age)
+        n_active[t] = len(state["id"])
+    if stats is not None:
+        stats["active"], stats["closed"] = n_active, n_closed
+    return state, track, tlen, tscore, tbox

@@ -85,6 +85,19 @@ def parse_option(track, post_nms, who):
     return kw, clip, method
 
 
+def split_online(track, who):
+    """The `online` word of open_video's `track=` option, which parse_option does not know (detect_video refuses it as an unknown
+    key): track -> (track without the key, online: bool, False where it is not given).  `online: True` asks a session to carry
+    the method's tracker from push to push; a ValueError names a value that is no bool."""
+    if not isinstance(track, dict) or "online" not in track:
+        return track, False
+    rest = dict(track)
+    online = rest.pop("online")
+    if type(online).__name__ not in ("bool", "bool_"):
+        raise ValueError("%s: track's online must be a bool, got %r" % (who, online))
+    return rest, bool(online)
+
+
 def track_host(ids, scores, bboxes, clip_start=None, num_class=None, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.5, t_min=2, max_age=0,
                stats=None):
     """ids (F,N[,1]), scores (F,N[,1]), bboxes (F,N,4) -> (track (F,N) int32: the row's track id, -1 for a row that is no
@@ -211,17 +224,25 @@ def track_online_host(state, ids, scores, bboxes, num_class=None, sigma_l=0.0, s
     return dict(next_id=next_id, active=active), track, tlen, tscore
 
 
-def finalize_tracks(track, tlen, tscore, sigma_h=0.5, t_min=2):
+def finalize_tracks(track, tlen, tscore, sigma_h=0.5, t_min=2, tbox=None):
     """track_online_host's three outputs over ALL frames of one finished clip, (F,N) each -> track_host's three arrays: a
     track's length and maximum are the largest `tlen` and `tscore` among its rows (both only grow, and its last row carries
     them); it is kept iff its maximum >= sigma_h and it holds at least t_min rows; the rows of a dropped track become
-    -1 / 0 / -1.  Ids are not renumbered."""
+    -1 / 0 / -1.  Ids are not renumbered.  tbox (F,N,4): the fourth output of sort.sort_online_host / byte.byte_online_host;
+    given it, a fourth array comes back, sort_host's / byte_host's `tbox`: the row's box where its track is kept, -1 where it
+    is dropped."""
     _, sh, _, t_min, _ = check_params(0.0, sigma_h, 0.5, t_min, 0, "finalize_tracks")
     track = np.asarray(track, dtype=np.int32)
     tlen = np.asarray(tlen, dtype=np.int32)
     tscore = np.asarray(tscore, dtype=_F)
     if track.ndim != 2 or tlen.shape != track.shape or tscore.shape != track.shape:
         raise ValueError("expected track, tlen and tscore (F,N), got %r %r %r" % (track.shape, tlen.shape, tscore.shape))
+    if tbox is not None:
+        tbox = np.asarray(tbox, dtype=_F)
+        if tbox.shape != track.shape + (4,):
+            raise ValueError("expected tbox %r beside track %r, got %r" % (track.shape + (4,), track.shape, tbox.shape))
+        first = finalize_tracks(track, tlen, tscore, sigma_h, t_min)
+        return first + (np.where((first[0] >= 0)[..., None], tbox, _F(-1)).astype(_F),)
     on = track >= 0
     if not on.any():
         return np.full(track.shape, -1, np.int32), np.zeros(track.shape, np.int32), np.full(track.shape, -1, _F)

@@ -29,7 +29,9 @@ pass over every tracked clip on the device (vd_tubelet) - a track'
 an interpolated box - and writes the rows after it beside everything else, under pred_tub, pred_tub_trk and *_tub.
 `--track_smooth` (with --track; no reference counterpart) smooths the boxes of every tracked clip along its tracks on the device
 (vd_track_smooth, DESIGN.md 37: the Rauch-Tung-Striebel smoother of SORT's Kalman filter) and writes the rows with their smoothed
-boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --live, --seq_nms or --tubelet.
+boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --seq_nms or --tubelet, and with --live only
+beside `--track_smooth_lag L`: the live session then smooths in fixed-lag form itself, every frame L frames late
+(vd_track_smooth_push), and the same files are written with the session's boxes.
 `--track_stitch` (with --track; no reference counterpart) re-links the track fragments of every tracked clip across gaps of up to
 --track_stitch_gap frames on the device (vd_track_stitch) and writes the rows under their stitched ids beside
 everything else, under pred_sti_trk, tracks_sti.txt and mot_sti.txt / hota_sti.txt - the detections do not change, so there is no
@@ -199,9 +201,16 @@ def parse_flags(argv=None):
            "(vd_track_smooth): the Rauch-Tung-Striebel smoother of SORT's Kalman filter estimates every box of a track from the "
            "frames before and after it.  Everything a run without the flag writes is written unchanged; the smoothed rows go to "
            "pred_smo, their twin with track ids to pred_smo_trk, tracks_smo.txt and the --metrics files *_smo.txt (DESIGN.md 37).  "
-           "Not with --live (a frame's smoothed box needs the frames after it), --seq_nms or --tubelet")
+           "Not with --live (a frame's smoothed box needs the frames after it) unless --track_smooth_lag is given, not with "
+           "--seq_nms or --tubelet")
     A("--track_smooth_gap", type=int, default=7,
       help="--track_smooth: a track is cut where it skips more than this many frames, 0 to 7")
+    A("--track_smooth_lag", type=int, default=None,
+      help="(no reference counterpart) with --stream --live --track --track_smooth: the live session smooths the boxes itself in "
+           "fixed-lag form (net.open_video(smooth={'lag': L}), vd_track_smooth_push, DESIGN.md 40): every frame comes out this "
+           "many frames late, 0 to 15, its boxes estimated from the frames before it and that many after it.  It lifts the "
+           "refusal of --track_smooth beside --live; the files are those of the --stream --track --track_smooth run, with the "
+           "session's boxes.  Not without --live and not without --track_smooth")
     A("--track_stitch", type=_bool, nargs="?", const=True, default=False,
       help="(no reference counterpart) with --track: the track fragments of every tracked clip are re-linked across long gaps on "
            "the device (vd_track_stitch): a track's filter state at its last row is extrapolated over the gap and matched to the "
@@ -406,21 +415,25 @@ def detect(net, dataset, loader, max_do=-1, data_shape=None, seq_nms=None, input
     return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
 
 
-def live_clip(net, frames, step, chunk, push, track=None):
+def live_clip(net, frames, step, chunk, push, track=None, smooth=None):
     """--live: detect_video(frames, step, chunk, track) by way of a live session - pushes of `push` frames, then a flush ->
     (ids, scores, bboxes, the (track, tlen, tscore) of detect_video's last_tracks or None).  The session's online tracker
     decides nothing; finalize_tracks decides at the clip's end, from the rows the session gave out.  Where the session keeps
     the filtered boxes of its rows (track with 'method': 'sort' or 'byte' and 'online': True), they are collected too and a
-    fourth array, detect_video's last_track_boxes, ends the tuple."""
-    session = net.open_video(step=step, chunk=chunk, track=track)
-    outs, trks, tboxes = [], [], []
+    fourth array, detect_video's last_track_boxes, ends the tuple.  smooth (open_video's dict, with 'lag'): the
+    session smooths the boxes along the online tracker's tracks and gives every frame out 'lag' frames late; the boxes
+    returned are the smoothed ones, and a fifth element holds the boxes ahead of the pass (session.last_pre_smooth)."""
+    session = net.open_video(step=step, chunk=chunk, track=track, **({} if smooth is None else dict(smooth=smooth)))
+    outs, trks, tboxes, pres = [], [], [], []
     for a in range(0, frames.shape[0], push):
         outs.append(session.push(frames[a:a + push])[1:])
         trks.append(session.last_tracks)
         tboxes.append(session.last_track_boxes)
+        pres.append(session.last_pre_smooth)
     outs.append(session.flush()[1:])
     trks.append(session.last_tracks)
     tboxes.append(session.last_track_boxes)
+    pres.append(session.last_pre_smooth)
     ids, scores, bboxes = (torch.cat(t) for t in zip(*outs))
     assert ids.shape[0] == frames.shape[0], "the session gave out %d of %d frames" % (ids.shape[0], frames.shape[0])
     if track is None:
@@ -429,11 +442,14 @@ def live_clip(net, frames, step, chunk, push, track=None):
     online = [torch.cat(t).cpu().numpy() for t in zip(*trks)]
     tbox = None if tboxes[0] is None else torch.cat(tboxes).cpu().numpy()
     final = finalize_tracks(*online, tbox=tbox, **session.track_decide)
+    if smooth is not None:
+        return ids, scores, bboxes, tuple(torch.from_numpy(a) for a in final), torch.cat(pres)
     return ids, scores, bboxes, tuple(torch.from_numpy(a) for a in final)
 
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
-                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None, track_online=False):
+                  seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None, track_online=False,
+                  smooth_lag=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
@@ -444,7 +460,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     with track, without seq_nms and live): handed to detect_video as well; the plain rows are the ones it keeps in
     net.last_pre_tubelet, and the rows after the pass and their track ids are returned as a fifth and a sixth element.  smooth
     (a dict, with track, without seq_nms, live and tubelet): handed to detect_video likewise; the plain boxes are the ones it
-    keeps in net.last_pre_smooth, and the rows with their smoothed boxes and their track ids are that fifth and sixth element.
+    keeps in net.last_pre_smooth, and the rows with their smoothed boxes and their track ids are that fifth and sixth element;
+    with live and smooth_lag (--track_smooth_lag) the live session smooths in fixed-lag form itself and the same
+    six elements come from its rows, the track ids finalize_tracks' as ever.
     stitch (a dict, with track, without the four): handed to detect_video likewise; the tracker's ids are the ones it keeps in
     net.last_pre_stitch, the fifth element is None and the sixth holds the stitched ids of the plain rows."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
@@ -465,7 +483,13 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
             live_trk = trk_kw.get("track")
             if track_online and live_trk is not None:                      # the session carries the method's own tracker
                 live_trk = dict(live_trk, online=True)
-            ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, live_trk)
+            if smooth is not None:                                         # the session's own fixed-lag smoother
+                ids, scores, sbox, last, bboxes = live_clip(net, torch.from_numpy(x), step, chunk, live, live_trk,
+                                                            dict(smooth, lag=smooth_lag))
+                _collect(boxes_tub, dataset, ids, scores, sbox, sidxs, W)
+                _collect_tracks(tracks_tub, dataset, ids, last[0], sidxs)
+            else:
+                ids, scores, bboxes, last = live_clip(net, torch.from_numpy(x), step, chunk, live, live_trk)
             if track is not None:
                 _collect_tracks(tracks, dataset, ids, last[0], sidxs)
         elif tubelet is not None:
@@ -642,11 +666,23 @@ def check_flags(FLAGS):
             for k, flag in (("max_gap", "--tubelet_max_gap"), ("drop_untracked", "--tubelet_drop_untracked"), ("rescore", "--tubelet_rescore")):
                 msg = msg.replace("--tubelet: " + k, flag)
             raise NotImplementedError(msg)
+    if getattr(FLAGS, "track_smooth_lag", None) is not None:
+        # the fixed-lag form of the smoother is a live session's: refused elsewhere, never ignored
+        if not getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_smooth_lag needs --live: it makes the live session (net.open_video) smooth the "
+                                      "boxes itself, every frame that many frames late; without --live --track_smooth smooths "
+                                      "every clip at its end")
+        if not getattr(FLAGS, "track_smooth", False):
+            raise NotImplementedError("--track_smooth_lag needs --track_smooth: it chooses how late a live session gives out "
+                                      "the smoothed boxes")
+        from viddet_amd.smooth_lag import MAX_LAG
+        if not 0 <= FLAGS.track_smooth_lag <= MAX_LAG:
+            raise NotImplementedError("--track_smooth_lag must be an integer in [0, %d], got %r" % (MAX_LAG, FLAGS.track_smooth_lag))
     if getattr(FLAGS, "track_smooth", False):
-        # the smoother runs over the tracks of a finished clip
+        # the smoother runs over the tracks of a finished clip - or, with --track_smooth_lag, of a live session
         if not getattr(FLAGS, "track", False):
             raise NotImplementedError("--track_smooth needs --track: the pass runs over the tracks of a clip")
-        if getattr(FLAGS, "live", False):
+        if getattr(FLAGS, "live", False) and getattr(FLAGS, "track_smooth_lag", None) is None:
             raise NotImplementedError("--track_smooth does not combine with --live: a frame's smoothed box needs the frames after "
                                       "it - the pass has no online form")
         if getattr(FLAGS, "seq_nms", False):
@@ -899,7 +935,8 @@ def main(argv=None):
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
-                              live=FLAGS.live_push if FLAGS.live else None, track_online=FLAGS.track_online, **seq_kw)
+                              live=FLAGS.live_push if FLAGS.live else None, track_online=FLAGS.track_online,
+                              smooth_lag=FLAGS.track_smooth_lag, **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None

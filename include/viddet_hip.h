@@ -857,6 +857,39 @@ int vd_track_smooth_stages(const float* ids, const float* scores, const float* b
                            const int32_t* clip_start, int V, int F, int N, int num_class, int max_gap, float* out_sbox,
                            int32_t* out_slen, void* ws, int64_t ws_bytes, int stages, void* stream);
 
+/* ---- The same smoother in fixed-lag form, resumable, for streams of frames that never say where they end
+ * (vd_track_smooth_live.hip): what viddet_amd.smooth_lag.smooth_lag_host computes, bit for bit, on both outputs.
+ * One launch takes the next F >= 0 frames of V streams - ids, scores, track [V][F][N], bboxes [V][F][N][4]; track the out_track
+ * of vd_track_push / vd_track_kf_push, ids counted over the stream (any table is safe) - starting from each stream's state and
+ * leaving the new state behind, and emits the frames that became final: frame u once frame u + lag has been taken, every frame
+ * taken with flush != 0 (the new frames first, then the rest against the last frame; the state's header is zeroed: a fresh
+ * stream).  An emitted frame u is smoothed against the horizon h = min(u + lag, the last frame taken):
+ *   members as vd_track_smooth finds them, with the causal bound 0 <= track[t][i] < (t + 1) * N (t the stream's frame); a
+ *   member's predecessor is the member of its id in the nearest of the max_gap + 1 frames before it; the forward filter is
+ *   vd_track_smooth's; the backward pass starts at the last member of the row's segment at a frame <= h; out_sbox and out_slen
+ *   follow vd_track_smooth's step 5 on the segment truncated behind h.
+ * state: V blocks of VD_TRACK_SMOOTH_LIVE_STATE_BYTES, each a ring of 16 frame slots (frame t lives in slot t % 16) of 128 rows:
+ *   int32 frames (taken so far), emitted (given out so far), two unused words (16 bytes); int32 slot_frame[16], the frame a
+ *   slot holds (64 bytes); then, indexed by e = slot * 128 + row, int32 mem[2048] (the id the row is a member of, -1: none),
+ *   prev_frame[2048], prev_row[2048] (the segment's member before this one as (stream frame, row), -1: none), next_frame[2048],
+ *   next_row[2048] (the one after it), pos[2048] (the member's position in its segment, from 0); float box[2048][4] (the input
+ *   box); float post[17][2048] (the member's posterior state, field-major).
+ * A block of all zero bytes is a fresh stream.  The contents are never trusted: the counts are clamped before they index, a
+ * (frame, row) word is checked - the row against [0, N), the frame against the window of the ring, the slot's stored frame
+ * against the frame expected - before it indexes, a walk moves to a strictly later (forward) or earlier (backward) frame only
+ * and makes at most 16 steps.  Outputs [V][m][N][4] and [V][m][N], written in full, m the frames that become final in this
+ * call: every stream of a launch must have taken the same number of frames, so that m is one number, which the caller knows
+ * from its own frame count T: without flush m = max(0, T + F - lag) - max(0, T - lag), with flush m = T + F - max(0, T - lag).
+ * m is checked against F, lag and flush; a stream whose state disagrees with it gets the surplus rows zeroed.  ids, scores,
+ * bboxes and track may be NULL where F == 0, the outputs where m == 0.  One workgroup of 256 threads per stream, 8,768 bytes of
+ * LDS, no workspace, no atomics, bit-reproducible; the inputs are never written.  1 <= N <= 128, F >= 0, V >= 1, num_class >= 1,
+ * 0 <= lag <= 15, 0 <= max_gap <= 7; the caller keeps frames * N below 2^31; bboxes, out_sbox and state 16-byte, every other
+ * pointer 4-byte aligned. */
+#define VD_TRACK_SMOOTH_LIVE_STATE_BYTES 221264
+int vd_track_smooth_push(const float* ids, const float* scores, const float* bboxes, const int32_t* track, int V, int F, int N,
+                         int num_class, int lag, int max_gap, int flush, void* state, int64_t state_bytes, int m, float* out_sbox,
+                         int32_t* out_slen, void* stream);
+
 /* ---- The track fragments of video clips re-linked across long gaps (vd_track_stitch.hip): what
  * viddet_amd.stitch.stitch_host computes, bit for bit, on all five outputs.  ids, scores, bboxes, clip_start, V, F, N,
  * num_class: as vd_seq_nms takes them; track [F][N] int32: the out_track of vd_track / vd_track_sort / vd_track_byte (any table

@@ -29,6 +29,7 @@
 #pragma clang fp contract(off)
 
 #include "vd_track_kf.h"
+#include "vd_track_smooth_math.h"
 
 namespace {
 
@@ -78,40 +79,6 @@ __device__ inline void smo_store(float* st, int64_t rows, int64_t row, const Kf&
     }
     st[15 * rows + row] = s.r;
     st[16 * rows + row] = s.p;
-}
-
-// the smoothed mean: x, xd of the three pairs and the aspect
-struct Sm {
-    float x[3], xd[3], r;
-};
-
-// smooth.py's rts_step: S at the later frame, f the filtered state and p = kf_predict(f) -> S at f's frame
-__device__ inline void smo_back(Sm& S, const Kf& f, const Kf& p) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float A = f.p00[i] + f.p01[i], B = f.p01[i], C = f.p01[i] + f.p11[i], D = f.p11[i];
-        const float det = p.p00[i] * p.p11[i] - p.p01[i] * p.p01[i];
-        const float c00 = (A * p.p11[i] - B * p.p01[i]) / det;
-        const float c01 = (B * p.p00[i] - A * p.p01[i]) / det;
-        const float c10 = (C * p.p11[i] - D * p.p01[i]) / det;
-        const float c11 = (D * p.p00[i] - C * p.p01[i]) / det;
-        const float dx = S.x[i] - p.x[i], dxd = S.xd[i] - p.xd[i];
-        S.x[i] = f.x[i] + (c00 * dx + c01 * dxd);
-        S.xd[i] = f.xd[i] + (c10 * dx + c11 * dxd);
-    }
-    S.r = f.r + (f.p / p.p) * (S.r - p.r);
-}
-
-__device__ inline bool finite4(const float4 b) {
-    return (__float_as_uint(b.x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(b.y) & 0x7f800000u) != 0x7f800000u &&
-           (__float_as_uint(b.z) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(b.w) & 0x7f800000u) != 0x7f800000u;
-}
-
-// a row is present iff seq_nms.row_classes makes it a candidate: id >= 0 (NaN is not), a finite score, a class below num_class
-__device__ inline bool row_present(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return false;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class;
 }
 
 __device__ inline void clip_of(const int32_t* __restrict__ clip_start, int v, int F, int& t0, int& t1) {

@@ -22,6 +22,7 @@ TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of on
 TRACK_SORT_WS_PER_ROW = 8                           # vd_track_sort: workspace bytes per (frame, row) (VD_TRACK_SORT_WS_PER_ROW)
 TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per clip, two tables of 17 x 1024 state floats
 TRACK_KF_STATE_BYTES = 159760                       # vd_track_kf_push: bytes of one stream's state (VD_TRACK_KF_STATE_BYTES)
+TRACK_SMOOTH_LIVE_STATE_BYTES = 221264              # vd_track_smooth_push: bytes of one stream's state (VD_TRACK_SMOOTH_LIVE_STATE_BYTES)
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
 TUBELET_WS_PER_ROW = 24                             # vd_tubelet: workspace bytes per (frame, row) (VD_TUBELET_WS_PER_ROW)
 TRACK_SMOOTH_WS_PER_ROW = 80                        # vd_track_smooth: workspace bytes per (frame, row) (VD_TRACK_SMOOTH_WS_PER_ROW)
@@ -229,6 +230,8 @@ SIGNATURES = {
     "vd_track_smooth_ws_bytes": (_i64, [_i, _i]),
     "vd_track_smooth": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _p]),
     "vd_track_smooth_stages": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _i64, _i, _p]),
+    # the same smoother in fixed-lag form, resumable: the last 16 frames' members carried in a state block (vd_track_smooth_live.hip)
+    "vd_track_smooth_push": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i64, _i, _p, _p, _p]),
     # track fragments re-linked across long gaps: filter tails extrapolated, matched to heads (vd_track_stitch.hip)
     "vd_track_stitch_ws_bytes": (_i64, [_i, _i]),
     "vd_track_stitch": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _i64, _p]),

@@ -7,13 +7,15 @@ concatenated results are torch.equal to `net.detect_video(clip, step, chunk)`: b
 launch groups stream.StreamPlanner forms - the fp32 operand scales are per tensor, so any other grouping would round
 differently.  With `track`, the emitted rows go through a resumable tracker on the device
 (ops.TrackState, vd_track_push; with track={'method': 'sort' | 'byte', 'online': True} ops.KalmanTrackState, vd_track_kf_push,
-DESIGN.md 39) whose state survives from push to push.
+DESIGN.md 39) whose state survives from push to push.  With `smooth={'lag': L}` the tracked frames go through a fixed-lag
+smoother on the device as well (ops.SmoothLagState, vd_track_smooth_push) and come out L frames later.
 """
 import torch
 
 from . import ops
 from .seq_nms import parse_option as parse_seq_nms
 from .smooth import parse_option as parse_smooth
+from .smooth_lag import parse_option as parse_smooth_lag
 from .stitch import parse_option as parse_stitch
 from .stream import StreamPlanner
 from .track import parse_option as parse_track
@@ -216,6 +218,18 @@ class VideoSession:
     finalize_tracks(*triples, tbox=boxes, **track_decide) on the finished clip gives detect_video's last_tracks and
     last_track_boxes.  'method': 'iou' with 'online': True is the session as ever: that tracker is always online.
 
+    smooth: None, or {'lag': L} / {'lag': L, 'max_gap': g} with L in [0, 15]; needs `track` ('iou' as it is, 'sort' / 'byte'
+    with 'online': True).  True is refused: a latency must be chosen.  The fixed-lag form of detect_video's smooth (DESIGN.md
+    40): every emitted batch goes to the tracker as ever, then the boxes the tracker saw (clamped by `clip`) and its ids go to
+    an ops.SmoothLagState (vd_track_smooth_push).  push / flush then return (t0, ids, scores, bboxes) for the frames whose
+    SMOOTHED boxes are final - L frames later than without the option; the ids, scores, rows, overflow, track triples and
+    tbox of the frames still waiting are held back on the device and come out with their frame, so last_rows, last_overflow,
+    last_tracks and last_track_boxes always describe the frames just returned, frames_out counts returned frames,
+    last_pre_smooth holds those frames' boxes ahead of the pass and last_smooth their slen (both None without the option).
+    Nothing is decided online: rows of a track that finalize_tracks drops later are smoothed too - the stated departure from
+    detect_video(track=..., smooth=...), which smooths the decided table; where nothing is dropped and L is at least the
+    clip's length less one, the two are equal bit for bit.  flush() resets both states.
+
     Seq-NMS is not a session option: it takes the best path through ALL frames of a clip, removes it and starts again until no
     row is alive, so no frame is final before the clip ends - it has no online form.  Run detect_video(seq_nms=...) on the
     finished clip instead.
@@ -224,7 +238,7 @@ class VideoSession:
     and no other session of the net accepts frames; net(x) is not affected.  Changing parameters, set_precision, set_nms or
     set_device_resize while frames are in flight is not supported: flush() first."""
 
-    def __init__(self, net, step=1, chunk=8, track=None):
+    def __init__(self, net, step=1, chunk=8, track=None, smooth=None):
         why = net._stream_refusal()
         if why is not None:
             raise NotImplementedError("open_video with " + why)
@@ -242,6 +256,8 @@ class VideoSession:
                                           "(run detect_video on the finished clip)" % (trk[2],))
             self._trk_kw, self._trk_clip, self._trk_method = trk
             self.track_decide = dict(sigma_h=self._trk_kw.pop("sigma_h"), t_min=self._trk_kw.pop("t_min"))
+        self._smo_kw = parse_smooth_lag(smooth, trk is not None, "open_video")
+        self._smo = self._held = None                             # the smoother's state; the frames that wait for their boxes
         if net._k > 1:
             net._stream_split()                                   # the graph's own word, before anything touches the GPU
         self.net, self.step, self.chunk = net, step, chunk
@@ -253,6 +269,7 @@ class VideoSession:
         self._hw = None
         self.frames_out = 0
         self.last_rows = self.last_overflow = self.last_tracks = self.last_track_boxes = None
+        self.last_pre_smooth = self.last_smooth = None
 
     def __repr__(self):
         return "<VideoSession step=%d chunk=%d: %d frames in, %d out>" % (self.step, self.chunk, self.frames_in, self.frames_out)
@@ -265,8 +282,9 @@ class VideoSession:
     def stream_stats(self):
         return self._eng.stats
 
-    def _run(self, acts, frames, T):
-        """the planner's actions on `frames` (the clip's frames from _buf0 on) -> (t0, ids, scores, bboxes) of the frames they emit"""
+    def _run(self, acts, frames, T, last=False):
+        """the planner's actions on `frames` (the clip's frames from _buf0 on) -> (t0, ids, scores, bboxes) of the frames they emit
+        (with smooth: of the frames whose smoothed boxes are final by now; last: the clip ends here, all of them)"""
         net = self.net
         out = self._eng.run(acts, frames, self._buf0, T, self._hw)
         self.last_rows, self.last_overflow = out['rows'], out['overflow']
@@ -284,9 +302,38 @@ class VideoSession:
             else:                                                 # the triple as ever, the filtered boxes beside it
                 *links, self.last_track_boxes = self._trk.push(out['ids'], out['scores'], boxes)
                 self.last_tracks = tuple(links)
+            if self._smo_kw is not None:
+                return self._smooth(out, boxes, last)
         t0 = self.frames_out
         self.frames_out += out['ids'].shape[0]
         return t0, out['ids'], out['scores'], out['bboxes']
+
+    def _smooth(self, out, boxes, last):
+        """the frames the engine just emitted (`boxes`: as the tracker saw them) behind the ones that wait; the frames whose
+        smoothed boxes are final leave the queue, every last_* word cut to them"""
+        net = self.net
+        if self._smo is None:
+            self._smo = ops.SmoothLagState(1, net.post_nms, 1 if net.agnostic else net.num_class, device=net.device, **self._smo_kw)
+        new = dict(ids=out['ids'], scores=out['scores'], pre=boxes, rows=out['rows'], overflow=out['overflow'])
+        for k, t in zip(("track", "tlen", "tscore"), self.last_tracks):
+            new[k] = t
+        if self.last_track_boxes is not None:
+            new["tbox"] = self.last_track_boxes
+        held = new if self._held is None else {k: torch.cat([self._held[k], new[k]]) for k in new}
+        t0, sbox, slen = self._smo.push(out['ids'], out['scores'], boxes.contiguous(), new["track"])
+        if last:
+            _, sbox2, slen2 = self._smo.flush()
+            sbox, slen = torch.cat([sbox, sbox2]), torch.cat([slen, slen2])
+        m = sbox.shape[0]
+        give = {k: t[:m] for k, t in held.items()}
+        self._held = {k: t[m:] for k, t in held.items()} if m < held['ids'].shape[0] else None
+        self.last_rows, self.last_overflow = give['rows'], give['overflow']
+        self.last_tracks = give['track'], give['tlen'], give['tscore']
+        self.last_track_boxes = give.get('tbox')
+        self.last_pre_smooth, self.last_smooth = give['pre'], slen
+        assert t0 == self.frames_out, "the smoother gave out frame %d, the session is at %d" % (t0, self.frames_out)
+        self.frames_out += m
+        return t0, give['ids'], give['scores'], sbox
 
     # ------------------------------------------------------------------ the public two
     def push(self, frames):
@@ -316,13 +363,15 @@ class VideoSession:
     def flush(self):
         net = self.net
         if self.frames_in == 0:                                   # nothing in flight: an empty clip emits nothing
-            return self._run([], None, 0)
+            return self._run([], None, 0, last=True)
         T = self.frames_in
-        res = self._run(self._plan.flush(), self._buf, T)
+        res = self._run(self._plan.flush(), self._buf, T, last=True)
         self._buf, self._buf0, self._shape, self._hw = None, 0, None, None
         self.frames_out = 0
         if self._trk is not None:
             self._trk.reset()
+        if self._smo is not None:                                 # flush() left it fresh
+            self._held = None
         if net._live is self:
             net._live = None
         return res

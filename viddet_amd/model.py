@@ -2294,13 +2294,17 @@ class YOLOV3(object):
         from .live import detect_video
         return detect_video(self, frames, step, chunk, seq_nms, track, tubelet, smooth, stitch)
 
-    def open_video(self, step=1, chunk=8, track=None):
+    def open_video(self, step=1, chunk=8, track=None, smooth=None):
         """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and
         whose length nobody knows - session.push(frames) returns the detections that are final by now, session.flush() ends
         the clip.  Refused where detect_video is, in the same words, and while another session of this net has
         frames in flight.  Seq-NMS has no online form and is no option here; nor is the tubelet pass: a hole is
         known only once its track resumes, after the frame has been given out.  The `smooth` option of detect_video (DESIGN.md
-        37) is none here either: a frame's smoothed box needs the frames after it; nor is `stitch`: a fragment's
+        37) is none here either: a frame's smoothed box needs the frames after it - but smooth={'lag': L} or {'lag': L,
+        'max_gap': g} (L in [0, 15]; needs `track`; True is refused, a latency must be chosen) is its fixed-lag form
+        (ops.SmoothLagState): every frame comes out L frames later, its boxes smoothed along the online tracker's
+        tracks against the frames before it and the L frames after it; session.last_pre_smooth / last_smooth hold the boxes
+        ahead of the pass and slen.  Nor is `stitch` an option: a fragment's
         successor is known only later.  track={'method': 'sort'} and
         track={'method': 'byte'} raise NotImplementedError unless the dict also says 'online': True (a bool, this method's
         word alone): the session then carries that tracker from push to push on the device (ops.KalmanTrackState, DESIGN.md
@@ -2308,7 +2312,7 @@ class YOLOV3(object):
         if self._live is not None:
             raise RuntimeError("open_video: %r has frames in flight on this net: flush() it first" % (self._live,))
         from .live import VideoSession
-        return VideoSession(self, step, chunk, track)
+        return VideoSession(self, step, chunk, track, smooth)
 
     def extract_features(self, x):
         """extract_base_features.py:127-130: f1 = features[:15](x), f2 = features[15:24](f1), f3 = features[24:](f2) in

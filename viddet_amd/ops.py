@@ -1167,6 +1167,84 @@ class KalmanTrackState:
         return out_track, out_len, out_score, out_tbox
 
 
+class SmoothLagState:
+    """Fixed-lag smoothing of the boxes of V streams along their tracks (vd_track_smooth_push;
+    viddet_amd/smooth_lag.py::smooth_lag_host on the device, bit for bit, DESIGN.md 40): owns the state tensor
+    (V, VD_TRACK_SMOOTH_LIVE_STATE_BYTES) uint8 - the last 16 frames' members, boxes, posterior states and links; all zero is a
+    fresh stream - and the fixed parameters lag (0..15, no default: a latency must be chosen) and max_gap (0..7).
+    push(ids, scores, bboxes, track) takes the next F frames of every stream - the tensors as KalmanTrackState.push takes
+    them, and track (V,F,N) or (F,N) int32, the per-row ids of an online tracker counted over the stream - and returns
+    (t0, sbox, slen), new device tensors for the m frames [t0, t0 + m) that became final: frame u is final once frame u + lag
+    has been taken; sbox of the leading shape (m,N,4) fp32 (with V: (V,m,N,4)) and slen (m,N) int32.  m == 0 gives empty
+    tensors.  flush() emits the frames still waiting and leaves the state fresh; reset() zeroes the state and the count.
+    Every stream takes the same frames, so m is one number, counted on the host: launches on the current stream, nothing is
+    downloaded and nothing waits.  A push that could take frames * N past 2**31 - 1 is refused."""
+
+    def __init__(self, V=1, N=100, num_class=1, lag=None, max_gap=7, device="cuda"):
+        from .smooth_lag import check_params
+        who = "SmoothLagState"
+        if lag is None:
+            raise ValueError("%s: lag must be given: a frame comes out `lag` frames late, an integer in [0, 15]" % who)
+        self.lag, self.max_gap = check_params(lag, max_gap, who)
+        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
+                raise ValueError("%s: %s must be an integer in [1, %d], got %r" % (who, name, hi, v))
+        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
+        self.state = torch.zeros(self.V, L.TRACK_SMOOTH_LIVE_STATE_BYTES, dtype=torch.uint8, device=device)
+        self.frames = 0                               # taken from every stream since the last reset
+        self._lead = (self.V,) if self.V > 1 else ()  # the outputs' leading shape: the last push's
+
+    @property
+    def emitted(self):
+        """the frames given out since the last reset"""
+        return max(0, self.frames - self.lag)
+
+    def reset(self):
+        self.state.zero_()
+        self.frames = 0
+
+    def _launch(self, ids, scores, bboxes, track, lead, F, flush):
+        V, N = self.V, self.N
+        t0 = self.emitted
+        m = (self.frames + F if flush else max(0, self.frames + F - self.lag)) - t0
+        dev = self.state.device
+        sbox = torch.empty(lead + (m, N, 4), dtype=torch.float32, device=dev)
+        slen = torch.empty(lead + (m, N), dtype=torch.int32, device=dev)
+        if F or flush:
+            args = (0, 0, 0, 0) if F == 0 else (ptr(ids), ptr(scores), ptr(bboxes), ptr(track))
+            check(_lib().vd_track_smooth_push(*args, V, F, N, self.num_class, self.lag, self.max_gap, 1 if flush else 0,
+                                              ptr(self.state), int(self.state.numel()), m, ptr(sbox) if m else 0,
+                                              ptr(slen) if m else 0, _s()), "vd_track_smooth_push")
+        self.frames += F
+        return t0, sbox, slen
+
+    def push(self, ids, scores, bboxes, track):
+        V, N = self.V, self.N
+        lead = tuple(bboxes.shape[:-2])
+        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
+            raise ValueError("SmoothLagState.push: bboxes must be (%d,F,%d,4)%s, got %r"
+                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
+        F = int(lead[-1])
+        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
+            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("SmoothLagState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
+                                 % (name, n, t.dtype, tuple(t.shape)))
+        if track.dtype != torch.int32 or tuple(track.shape) != lead + (N,) or not track.is_contiguous() or not track.is_cuda:
+            raise ValueError("SmoothLagState.push: track must be a contiguous int32 device tensor %r, got %s %r"
+                             % (lead + (N,), track.dtype, tuple(track.shape)))
+        if (self.frames + F) * N > 2 ** 31 - 1:
+            raise ValueError("SmoothLagState.push: %d + %d frames of %d rows could meet more than 2**31 - 1 track ids; "
+                             "reset() the state (a new clip) first" % (self.frames, F, N))
+        self._lead = lead[:-1]
+        return self._launch(ids, scores, bboxes, track, lead[:-1], F, False)
+
+    def flush(self):
+        """-> (t0, sbox, slen) of the frames still waiting, smoothed against the last frame taken; the state is fresh afterwards"""
+        out = self._launch(None, None, None, None, self._lead, 0, True)
+        self.reset()                                  # the kernel zeroed the header; the bytes are a fresh stream's too
+        return out
+
+
 def temporal_pool(x, y, argmax, B, K, inner, type_):
     check(_lib().vd_temporal_pool(ptr(x), ptr(y), ptr(argmax), B, K, inner, type_, _s()), "vd_temporal_pool")
 

@@ -31,7 +31,10 @@ an interpolated box - and writes the rows after it beside everything else, under
 (vd_track_smooth, DESIGN.md 37: the Rauch-Tung-Striebel smoother of SORT's Kalman filter) and writes the rows with their smoothed
 boxes beside everything else, under pred_smo, pred_smo_trk and *_smo; not with --seq_nms or --tubelet, and with --live only
 beside `--track_smooth_lag L`: the live session then smooths in fixed-lag form itself, every frame L frames late
-(vd_track_smooth_push), and the same files are written with the session's boxes.
+(vd_track_smooth_push), and the same files are written with the session's boxes.  `--visualise [--display_gt]`
+(with --stream; detect_yolo3.py visualise_predictions) draws what every clip's call returns - rings, tags of class, score and
+track id, trails, the label rows in green underneath - onto the clip's frames on the device (vd_overlay) and writes
+every --vis_every-th frame as vis/<clip>/<frame>.ppm; everything else is written as without the flag.
 `--track_stitch` (with --track; no reference counterpart) re-links the track fragments of every tracked clip across gaps of up to
 --track_stitch_gap frames on the device (vd_track_stitch) and writes the rows under their stitched ids beside
 everything else, under pred_sti_trk, tracks_sti.txt and mot_sti.txt / hota_sti.txt - the detections do not change, so there is no
@@ -101,6 +104,12 @@ def parse_flags(argv=None):
     A("--per_frame_metric", type=_bool, nargs="?", const=True, default=False)
     A("--worst_video_path", default=None)
     A("--display_gt", type=_bool, nargs="?", const=True, default=True)
+    A("--vis_thickness", type=int, default=None,
+      help="(no reference counterpart) with --visualise: the pixels of a box outline and of a trail (default 2, as cv2.rectangle(.., 2))")
+    A("--vis_scale", type=int, default=None, help="(no reference counterpart) with --visualise: the text scale, 1..4 (default 1)")
+    A("--vis_trail", type=int, default=None,
+      help="(no reference counterpart) with --visualise --track: the frames a track's trail reaches back, 0..16 (default 8)")
+    A("--vis_every", type=int, default=None, help="(no reference counterpart) with --visualise: every n-th frame of a clip is written (default 1)")
     A("--model_agnostic", type=_bool, nargs="?", const=True, default=False)
     A("--metric_agnostic", type=_bool, nargs="?", const=True, default=False)
     A("--gpus", type=_list, default=["0"])
@@ -449,7 +458,7 @@ def live_clip(net, frames, step, chunk, push, track=None, smooth=None):
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
                   seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None, track_online=False,
-                  smooth_lag=None):
+                  smooth_lag=None, visualise=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
@@ -464,7 +473,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     with live and smooth_lag (--track_smooth_lag) the live session smooths in fixed-lag form itself and the same
     six elements come from its rows, the track ids finalize_tracks' as ever.
     stitch (a dict, with track, without the four): handed to detect_video likewise; the tracker's ids are the ones it keeps in
-    net.last_pre_stitch, the fifth element is None and the sixth holds the stitched ids of the plain rows."""
+    net.last_pre_stitch, the fifth element is None and the sixth holds the stitched ids of the plain rows.
+    visualise (visualise_args' dict, not with live): detect_video draws what it returns onto every clip's frames on the device
+    (its `overlay`) and write_overlay writes every `every`-th one as a PPM file; nothing else changes."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
@@ -479,6 +490,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
         sidxs = [dataset.sample_index(v, t) for t in range(x.shape[0])]
         W = data_shape if device_resize else x.shape[-2]
         trk_kw = {} if track is None else dict(track=dict(track, clip=W))  # the tracker sees the boxes as they are saved too
+        if visualise is not None:
+            trk_kw = dict(trk_kw, overlay=dict(visualise["params"], gt=clip_labels(dataset, sidxs, data_shape)
+                                               if visualise["display_gt"] else None))
         if live is not None:
             live_trk = trk_kw.get("track")
             if track_online and live_trk is not None:                      # the session carries the method's own tracker
@@ -523,6 +537,8 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
                 plain = link_rows(ids, scores, bboxes.clamp(0, W), track, num_class=1 if net.agnostic else net.num_class)
                 _collect_tracks(tracks, dataset, ids, plain, sidxs)
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        if visualise is not None:
+            write_overlay(visualise, v, net.last_overlay[0])
         c += x.shape[0]
         if c > max_do:
             break
@@ -533,6 +549,50 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     if track is not None:
         return (boxes, boxes_seq, tracks, tracks_seq) if seq_nms is not None else (boxes, None, tracks, None)
     return boxes if seq_nms is None else (boxes, boxes_seq)
+
+
+def visualise_args(FLAGS, dataset=None):
+    """--visualise: the dict detect_stream takes, None without the flag - `params` for detect_video's overlay (rows are drawn
+    from --detection_threshold on, as the reference's visualise_predictions does, detect_yolo3.py:561; class names cut
+    to the 15 characters a tag holds), `dir` <save_dir>/<save_prefix>/vis, `every`, `display_gt`, `yuv` (matrix, range) where
+    the frames are NV12"""
+    if not getattr(FLAGS, "visualise", False):
+        return None
+    params = dict(thresh=float(FLAGS.detection_threshold), thickness=2 if FLAGS.vis_thickness is None else FLAGS.vis_thickness,
+                  scale=1 if FLAGS.vis_scale is None else FLAGS.vis_scale, trail=8 if FLAGS.vis_trail is None else FLAGS.vis_trail)
+    if dataset is not None and not FLAGS.model_agnostic:
+        params["class_names"] = tuple("".join(ch if 32 <= ord(ch) <= 126 else "?" for ch in str(n))[:15] for n in dataset.classes)
+    return dict(params=params, dir=os.path.join(FLAGS.save_dir, FLAGS.save_prefix, "vis"),
+                every=1 if FLAGS.vis_every is None else FLAGS.vis_every, display_gt=bool(FLAGS.display_gt),
+                yuv=(FLAGS.yuv_matrix, FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else None)
+
+
+def clip_labels(dataset, sidxs, data_shape):
+    """--display_gt: the label rows of a clip's frames as detect_video's overlay takes them - (T,G,5) float32 x1, y1, x2, y2,
+    class in the predictions' coordinates (the data_shape square), padded with rows of -1"""
+    w0, h0 = dataset.frame_size
+    rows = [np.asarray(dataset[int(i)][1], np.float64).reshape(-1, 6)[:128] for i in sidxs]
+    gt = np.full((len(rows), max(1, max(len(r) for r in rows)), 5), -1.0, np.float32)
+    for t, r in enumerate(rows):
+        gt[t, :len(r), :4] = r[:, :4] * (data_shape / w0, data_shape / h0, data_shape / w0, data_shape / h0)
+        gt[t, :len(r), 4] = r[:, 4]
+    return gt
+
+
+def write_overlay(visualise, v, frames):
+    """--visualise: every `every`-th painted frame of clip v as binary PPM vis/<clip %04d>/<frame %06d>.ppm; NV12 frames
+    are converted on the host (video.nv12_to_rgb) first"""
+    out = os.path.join(visualise["dir"], "%04d" % v)
+    os.makedirs(out, exist_ok=True)
+    every = visualise["every"]
+    picked = frames[::every].cpu().numpy()
+    if visualise["yuv"] is not None:
+        from viddet_amd.video import nv12_to_rgb
+        picked = nv12_to_rgb(np.ascontiguousarray(picked), *visualise["yuv"])
+    for k, img in enumerate(picked):
+        with open(os.path.join(out, "%06d.ppm" % (k * every)), "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+            f.write(np.ascontiguousarray(img).tobytes())
 
 
 def pred_dir(save_dir, save_prefix, agnostic=False, seq=False, trk=False, tub=False):
@@ -722,9 +782,27 @@ def check_flags(FLAGS):
         for flag in ("track_stitch_gap", "track_stitch_iou"):
             if getattr(FLAGS, flag, None) is not None:
                 raise NotImplementedError("--%s needs --track_stitch: it is a parameter of that pass" % flag)
+    if getattr(FLAGS, "visualise", False):
+        # the overlay is drawn by net.detect_video on a clip's own frames
+        if not getattr(FLAGS, "stream", False):
+            raise NotImplementedError("--visualise needs --stream: the overlay is drawn by net.detect_video on a clip's frames; "
+                                      "the windowed path hands out windows, not frames")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--visualise does not combine with --live: a live session gives its frames back before "
+                                      "their rows are final, it would have to hold them")
+        if len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--visualise takes one --dataset name: the combined set has no clips")
+        for flag, lo, hi in (("vis_thickness", 1, 8), ("vis_scale", 1, 4), ("vis_trail", 0, 16), ("vis_every", 1, 1 << 30)):
+            v = getattr(FLAGS, flag, None)
+            if v is not None and not lo <= int(v) <= hi:
+                raise NotImplementedError("--%s must lie in [%d, %d], got %r" % (flag, lo, hi, v))
+    else:
+        for flag in ("vis_thickness", "vis_scale", "vis_trail", "vis_every"):
+            if getattr(FLAGS, flag, None) is not None:
+                raise NotImplementedError("--%s needs --visualise: it is a parameter of the overlay" % flag)
     # accepted for command-line compatibility, refused when they would change the result (never silently ignored):
-    # research variants, visualisation, the VID metric's options, evaluation on another dataset's class list
-    for flag in ("temp", "mult_out", "new_model", "motion_stream", "visualise", "offset", "per_frame_metric",
+    # research variants, the VID metric's options, evaluation on another dataset's class list
+    for flag in ("temp", "mult_out", "new_model", "motion_stream", "offset", "per_frame_metric",
                  "worst_video_path", "trained_on"):
         v = getattr(FLAGS, flag)
         if v and not (isinstance(v, str) and not v.strip()):
@@ -936,7 +1014,7 @@ def main(argv=None):
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
                               live=FLAGS.live_push if FLAGS.live else None, track_online=FLAGS.track_online,
-                              smooth_lag=FLAGS.track_smooth_lag, **seq_kw)
+                              smooth_lag=FLAGS.track_smooth_lag, visualise=visualise_args(FLAGS, dataset), **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None

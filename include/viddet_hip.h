@@ -1064,6 +1064,54 @@ int vd_hota_match(const float* gt_boxes, const int32_t* gt_cls, const int32_t* g
                   int num_class, int agnostic, int32_t* match, float* msim, int32_t* mscore, void* ws, int64_t ws_bytes,
                   void* stream);
 
+/* ---- Detections, tracks and ground truth drawn onto video frames (vd_overlay.hip): what
+ * viddet_amd.overlay.overlay_host paints, bit for bit, on the frames and on `painted`.  frames / out: F uint8 frames, frame f
+ * at byte f * frame_stride, rows `pitch` bytes apart.  fmt 0: packed RGB, H0 rows of W0 pixels (pitch >= 3 * W0; uv_offset is
+ * not read).  fmt 1: NV12 as vd_resize_nv12_nchw takes it - H0 rows of luma, from uv_offset bytes into the frame H0 / 2 rows of
+ * interleaved chroma pairs, H0 and W0 even, pitch >= W0, uv_offset >= pitch * H0.  frame_stride covers a frame's last byte.
+ * out == frames paints in place: only threads with a painted pixel write.  Otherwise every pixel of out is written (the source
+ * where nothing is painted; bytes between rows and planes are not touched) and the two ranges must not overlap.
+ * ids, scores [F][N] fp32, bboxes [F][N][4] fp32 in the coordinates of a network input of Hn x Wn; track [F][N] int32 (NULL:
+ * no row is tracked); gt (NULL with G == 0) [F][G][gt_stride] fp32 rows x1, y1, x2, y2, class, .., a class < 0 padding;
+ * clip_start [V + 1] int32 (NULL with V == 1): a trail of frame f reaches back to the largest offset <= f at most.
+ * Row (f, i) is drawn iff ids >= 0, scores >= thresh, the four box values are finite, x1 <= x2 and y1 <= y2.  Its pixel box:
+ * sx = (float)W0 / (float)Wn, px0 = (int)clamp(floorf(x1 * sx), 0, W0 - 1), and so on, in single fp32 operations.  Its colour:
+ * palette word (class & 255), with by_track and track >= 0 (track & 255); ground truth takes word 256.  Its tag: "#<track> "
+ * where tracked, the class name (names [n_names][16] uint8, NUL padded; the decimal class id where names is NULL or the class
+ * is beyond it), a space, and q / 100 . q % 100 of q = min(999, (int)(score * 100.0f + 0.5f)); ground truth: the name alone;
+ * cut to 32 characters, in the 5 x 7 font `font` ([95][8] uint8: seven row bytes, bit 4 the left column, and a pad byte) at
+ * `scale` pixels a font pixel, above the box (inside it where there is no room).  Its trail (tracked rows): the centres of
+ * the row and of the lowest drawn row of the same track in each of the `trail` frames before it, joined by segments of
+ * `thickness` pixels, a thickness x thickness square on every vertex.  Layers, bottom to top: ground truth, trails, rings of
+ * `thickness` pixels growing inward, tags; inside a layer the lower row is on top.  palette [259] uint32: c0 | c1 << 8 |
+ * c2 << 16 - (R, G, B), or for NV12 (Y, U, V), no colour arithmetic is done on the device - and bit 24: glyphs on this colour
+ * are white (word 258), else black (257).  An NV12 chroma pair (cy, cx) is painted iff luma pixel (2 cy, 2 cx) is, with that
+ * pixel's colour.  painted [F] int32: the pixels of each frame that took a colour (NV12: luma pixels).
+ * Two launches.  Primitives (stage 1): a workgroup per frame writes one record of VD_OVERLAY_WS_PER_ROW bytes per row and
+ * per ground-truth row into ws (overlay.REC_DTYPE: rows [F][N], then ground truth [F][G]) and sets painted to 0; no atomics.
+ * Paint (stage 2): a workgroup per (frame, tile of 64 x 16 pixels), a thread per 4 pixels, walks the frame's records top
+ * layer first in batches through LDS; nothing limits the primitives of a tile; one integer atomicAdd on painted per workgroup
+ * (bit-reproducible).  Where W0, pitch, frame_stride (and uv_offset) are multiples of 4 and frames / out are 4-byte aligned the
+ * pixels move as dwords, else byte by byte: frames and out need no alignment.  1 <= N <= 128, 0 <= G <= 128, F >= 1,
+ * 1 <= thickness <= 8, 1 <= scale <= 4, 0 <= trail <= 16, H0, W0 <= 8192; bboxes and ws 16-byte, every other table 4-byte
+ * aligned.  The rows are never written.  vd_overlay_ws_bytes: the bytes ws must hold, -1 for sizes that are not taken. */
+#define VD_OVERLAY_WS_PER_ROW 128
+int64_t vd_overlay_ws_bytes(int F, int N, int G);
+int vd_overlay(const uint8_t* frames, uint8_t* out, int64_t frame_stride, int64_t pitch, int64_t uv_offset, int fmt, int F, int H0,
+               int W0, const float* ids, const float* scores, const float* bboxes, const int32_t* track, const float* gt,
+               int gt_stride, const int32_t* clip_start, int V, int N, int G, int Hn, int Wn, float thresh, int thickness, int scale,
+               int trail, int by_track, const uint8_t* names, int n_names, const uint32_t* palette, const uint8_t* font,
+               int32_t* painted, void* ws, int64_t ws_bytes, void* stream);
+/* the same with a mask of the launches to make (tests, tools/overlay_probe.py): 1 (primitives), 2 (paint); vd_overlay is stages
+ * 3.  Stage 2 alone paints whatever records ws holds: a vertex count is clamped and every pixel address is formed from
+ * coordinates checked against the frame, so nothing outside the frames is touched; painted is added to, not reset. */
+int vd_overlay_stages(const uint8_t* frames, uint8_t* out, int64_t frame_stride, int64_t pitch, int64_t uv_offset, int fmt, int F,
+                      int H0, int W0, const float* ids, const float* scores, const float* bboxes, const int32_t* track,
+                      const float* gt, int gt_stride, const int32_t* clip_start, int V, int N, int G, int Hn, int Wn, float thresh,
+                      int thickness, int scale, int trail, int by_track, const uint8_t* names, int n_names,
+                      const uint32_t* palette, const uint8_t* font, int32_t* painted, void* ws, int64_t ws_bytes, int stages,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ MOT_MAX_ROWS = 128                                 # vd_mot_match: label rows an
 MOT_WS_PER_ROW = 4                                  # vd_mot_match: workspace bytes per (frame, row) of either side (VD_MOT_WS_PER_ROW)
 HOTA_MAX_GT_IDS = 1024                              # vd_hota_match: dense ground-truth ids per clip (vd_hota_eval.hip)
 HOTA_MAX_FRAMES = 1 << 22                           # vd_hota_match: frames of one call
+OVERLAY_MAX_ROWS = 128                              # vd_overlay: rows and ground-truth rows per frame (vd_overlay.hip)
+OVERLAY_WS_PER_ROW = 128                            # vd_overlay: workspace bytes per (frame, row) of either kind (VD_OVERLAY_WS_PER_ROW)
 VD_MAX_TAPS = 27
 EPI_AFFINE, EPI_LEAKY, EPI_RESIDUAL = 1, 2, 4
 MATH_SPLIT = 16        # vd_conv_desc.flags / vd_wgrad_desc.flags: split-operand fp32 products (include/viddet_hip.h)
@@ -241,6 +243,12 @@ SIGNATURES = {
     # the per-frame matching of the HOTA tracking metric on the device (vd_hota_eval.hip)
     "vd_hota_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_hota_match": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p]),
+    # detections, tracks and ground truth drawn onto video frames (vd_overlay.hip)
+    "vd_overlay_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_overlay": (_i, [_p, _p, _i64, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i,
+                        _p, _i, _p, _p, _p, _p, _i64, _p]),
+    "vd_overlay_stages": (_i, [_p, _p, _i64, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _i,
+                               _i, _i, _p, _i, _p, _p, _p, _p, _i64, _i, _p]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@ smoother on the device as well (ops.SmoothLagState, vd_track_smooth_push, DESIGN
 import torch
 
 from . import ops
+from .overlay import parse_option as parse_overlay
 from .seq_nms import parse_option as parse_seq_nms
 from .smooth import parse_option as parse_smooth
 from .smooth_lag import parse_option as parse_smooth_lag
@@ -125,10 +126,33 @@ def _follow(rows, perm):
     return torch.where(perm >= 0, old, torch.full_like(old, -1))
 
 
-def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None):
+def _draw(net, frames, res, ovl, track, hw):
+    """detect_video's `overlay`: the rows the call returns drawn onto a copy of the caller's frames (ops.overlay),
+    or with inplace onto the device frames themselves -> (frames_out, painted)"""
+    kw = {k: v for k, v in ovl.items() if k not in ("inplace", "gt")}
+    if net._dev_nv12 is not None:                                 # the frames are NV12: the session's matrix and range
+        from .video import NV12_MATRICES
+        matrix, rng = next(k for k, v in NV12_MATRICES.items() if v == tuple(net._dev_nv12))
+        kw.update(fmt="nv12", matrix=matrix, range=rng)
+    rgb = kw.get("fmt") != "nv12"                                 # (RGB goes contiguous; an NV12 surface keeps its strides)
+    if not frames.is_cuda:
+        src = frames.to(net.device)
+        src = out = src.contiguous() if rgb else src              # the upload is the copy: painted in place
+    elif ovl.get("inplace"):
+        src = out = frames
+    else:
+        src, out = (frames.contiguous() if rgb else frames), None
+    gt = ovl.get("gt")
+    if gt is not None:
+        gt = torch.as_tensor(gt, dtype=torch.float32).to(net.device).contiguous()
+    return ops.overlay(src, res[0].contiguous(), res[1].contiguous(), res[2].contiguous(), track=track, gt=gt, out=out,
+                       net_size=tuple(hw), **kw)
+
+
+def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None, overlay=None):
     """YOLOV3.detect_video (its docstring is the description): a clip whose end is known is one push and one flush of the
     planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> stitch -> smooth ->
-    tubelet on the finished clip."""
+    tubelet on the finished clip, and the overlay of what is returned."""
     why = net._stream_refusal()
     if why is not None:
         raise NotImplementedError("detect_video with " + why)
@@ -140,6 +164,14 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
     tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
     smo_kw = parse_smooth(smooth, trk is not None, "detect_video")
     sti_kw = parse_stitch(stitch, trk is not None, "detect_video")
+    ovl = parse_overlay(overlay, "detect_video")
+    if ovl is not None:
+        if frames.dtype != torch.uint8:
+            raise ValueError("detect_video: overlay needs uint8 frames (the pixels it draws on), got %s: float frames are "
+                             "already normalised" % frames.dtype)
+        if ovl.get("inplace") and not frames.is_cuda:
+            raise ValueError("detect_video: overlay's inplace needs frames on the device; host frames are painted on their upload")
+    net.last_overlay = None
     net.last_tracks = net.last_track_boxes = None
     net.last_tubelet = net.last_pre_tubelet = None
     net.last_smooth = net.last_pre_smooth = None
@@ -187,6 +219,9 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
             net.last_rows = _follow(net.last_rows, out_t[3])
             net.last_tubelet = out_t[3], out_t[4], out_t[5]
             res = out_t[0], out_t[1], out_t[2]
+    if ovl is not None:                                           # what the call returns, with the final track table
+        table = None if trk is None else net.last_tubelet[1] if net.last_tubelet is not None else net.last_tracks[0]
+        net.last_overlay = _draw(net, frames, res, ovl, table, (H, W))
     return res
 
 

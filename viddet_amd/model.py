@@ -2241,7 +2241,8 @@ class YOLOV3(object):
         if n < dst.shape[0]:
             dst[n:].copy_(dst[n - 1:n].expand(dst.shape[0] - n, -1, -1, -1))
 
-    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None):
+    def detect_video(self, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None,
+                     overlay=None):
         """Detect on every frame of ONE clip: frames (T,3,H,W) float or (T,H,W,3) uint8 -> ids (T,post_nms,1), scores
         (T,post_nms,1), bboxes (T,post_nms,4), what net(windows) returns on the T windows the VID dataset would build
         (stream_window_slots: imgnetvid.py:486-506) - with the per-frame part of the network run ONCE per frame.
@@ -2290,9 +2291,19 @@ class YOLOV3(object):
         tracks).  The order is Seq-NMS -> track -> stitch -> smooth -> tubelet, so the later passes take the stitched table.
         last_pre_stitch holds the tracker's (track, tlen, tscore), last_tracks the stitched triple, last_stitch = (stitches,
         overflow), each (1,); last_track_boxes stays the tracker's.  A call without it sets last_stitch and last_pre_stitch to
-        None.  open_video takes no such argument: a fragment's successor is known only later."""
+        None.  open_video takes no such argument: a fragment's successor is known only later.
+
+        overlay: None (the default), True, or a dict of thresh / thickness / scale / trail / color_by / class_names / palette /
+        gt / inplace; needs uint8 frames - what the call returns is drawn onto the frames on the device (ops.overlay, DESIGN.md
+        41): rings, tags of class, score and track id, trails along the final track table (last_tubelet[1] where the tubelet
+        pass ran, else last_tracks[0]; none without `track`), ground truth `gt` (T,G,>=5) in green underneath.  The boxes are
+        in the network's coordinates (set_device_resize's target, else the frames' own size) and the frames keep their source
+        size; NV12 frames follow set_device_resize(source='nv12')'s matrix and range.  last_overlay = (frames_out, painted):
+        a painted copy of the frames on the device (with inplace, device frames only: the caller's tensor itself) and the
+        painted pixels of every frame; None after a call without it.  The three returned tensors are those of the call without
+        it.  open_video takes no such argument: a session gives its frames back before their rows."""
         from .live import detect_video
-        return detect_video(self, frames, step, chunk, seq_nms, track, tubelet, smooth, stitch)
+        return detect_video(self, frames, step, chunk, seq_nms, track, tubelet, smooth, stitch, overlay)
 
     def open_video(self, step=1, chunk=8, track=None, smooth=None):
         """A live.VideoSession on this net: detect_video(step, chunk, track) on a clip whose frames arrive a few at a time and

@@ -1038,6 +1038,140 @@ def hota_ws_bytes(V, num_gt_id, num_track):
     return V * (8 * A * P + 4 * A + 4 * P)
 
 
+_OVERLAY_TABLES = {}     # (kind, device, value) -> the device tensor: the font, and every distinct palette and class-name table
+
+
+def _overlay_table(kind, device, value, make):
+    """a constant table of vd_overlay on `device`, uploaded once per distinct value"""
+    key = (kind, str(device), value)
+    if key not in _OVERLAY_TABLES:
+        _OVERLAY_TABLES[key] = torch.from_numpy(make()).to(device, non_blocking=True)
+    return _OVERLAY_TABLES[key]
+
+
+def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, out=None, ws=None, stages=None, H0=None, W0=None,
+            pitch=None, uv_offset=None, frame_stride=None, **params):
+    """vd_overlay (viddet_amd/overlay.py::overlay_host on the device, bit for bit, DESIGN.md 41): detections, tracks and ground
+    truth drawn onto video frames.  frames: a uint8 device tensor (F,H0,W0,3), contiguous; with fmt='nv12' (F,H0*3/2,W0) whose
+    last stride is 1 (a contiguous tensor, or the view [..., :W0] of a pitched surface: its strides are the pitch and the frame
+    stride), or a 1-D surface with H0, W0 and pitch given (uv_offset: the chroma plane's byte offset in a frame, pitch * H0
+    where it is not given; frame_stride: uv_offset + pitch * H0 / 2).  ids, scores (F,N[,1]) and bboxes (F,N,4): contiguous fp32
+    device tensors in net_size coordinates, N <= 128; track (F,N) int32 or None; gt (F,G,>=5) fp32 or None, G <= 128;
+    clip_start as ops.seq_nms takes it.  out: None (a new tensor of the frames' layout: every pixel is written, bytes between
+    rows and planes are not), or `frames` itself (in place: only painted pixels are written), or a tensor of the frames' layout
+    that does not overlap them.  params: those of overlay.check_params.  Returns (out, painted (F,) int32).  Launches on the
+    current stream; nothing is downloaded and nothing waits.  The font, the palette and the class-name table are uploaded once
+    per distinct value.  ws: a uint8 device tensor of >= 128*F*(N+G) bytes to reuse.  stages (a mask of 1, 2;
+    tools/overlay_probe.py): only those launches are made (vd_overlay_stages)."""
+    from . import overlay as O
+    p = O.check_params(tracked=track is not None, who="overlay", **params)
+    nv12 = p["fmt"] == "nv12"
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise ValueError("overlay: frames must be a uint8 tensor, got %s" % (getattr(frames, "dtype", type(frames)),))
+    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("overlay: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > L.OVERLAY_MAX_ROWS:
+        raise ValueError("overlay: N=%d rows per frame, vd_overlay takes at most %d" % (N, L.OVERLAY_MAX_ROWS))
+    if nv12 and frames.dim() == 1:
+        if H0 is None or W0 is None or pitch is None:
+            raise ValueError("overlay: a 1-D NV12 surface needs H0, W0 and pitch")
+        h0, w0, pitch = int(H0), int(W0), int(pitch)
+        if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2 or h0 > O.MAX_SIZE or w0 > O.MAX_SIZE:
+            raise ValueError("overlay: NV12 needs an even frame size of at most %d pixels a side, got H0=%d W0=%d"
+                             % (O.MAX_SIZE, h0, w0))
+        uv_offset = pitch * h0 if uv_offset is None else int(uv_offset)
+        span = uv_offset + pitch * (h0 // 2 - 1) + w0
+        frame_stride = uv_offset + pitch * (h0 // 2) if frame_stride is None else int(frame_stride)
+        if pitch < w0 or uv_offset < pitch * h0 or frame_stride < span or frames.numel() < (F - 1) * frame_stride + span \
+                or not frames.is_contiguous():
+            raise ValueError("overlay: a surface of %d bytes does not hold F=%d NV12 frames of %dx%d with pitch=%d uv_offset=%d "
+                             "frame_stride=%d" % (frames.numel(), F, h0, w0, pitch, uv_offset, frame_stride))
+    else:
+        if (H0, W0, pitch, uv_offset, frame_stride) != (None,) * 5:
+            raise ValueError("overlay: H0, W0, pitch, uv_offset and frame_stride describe a 1-D NV12 surface, got frames %r"
+                             % (tuple(frames.shape),))
+        f_, h0, w0 = O.frame_size(tuple(frames.shape), p["fmt"])
+        if f_ != F:
+            raise ValueError("overlay: %d frames but rows of %d" % (f_, F))
+        if nv12:
+            pitch, frame_stride = int(frames.stride(1)), int(frames.stride(0))
+            uv_offset = pitch * h0
+            if frames.stride(2) != 1 or pitch < w0 or (F > 1 and frame_stride < uv_offset + pitch * (h0 // 2 - 1) + w0):
+                raise ValueError("overlay: NV12 frames need a last stride of 1, rows at least W0 and frames at least a frame "
+                                 "apart, got strides %r" % (tuple(frames.stride()),))
+            frame_stride = max(frame_stride, uv_offset + pitch * (h0 // 2 - 1) + w0)
+        else:
+            if not frames.is_contiguous():
+                raise ValueError("overlay: RGB frames must be contiguous, got strides %r" % (tuple(frames.stride()),))
+            pitch, uv_offset = 3 * w0, 0
+            frame_stride = h0 * pitch
+    if not frames.is_cuda:
+        raise ValueError("overlay: frames must be a device tensor")
+    dev = frames.device
+    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
+                           ("bboxes", bboxes, F * N * 4, torch.float32)) + \
+            ((("track", track, F * N, torch.int32),) if track is not None else ()):
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("overlay: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    G, gt_stride = 0, 0
+    if gt is not None:
+        if not torch.is_tensor(gt) or gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[0] != F or gt.shape[2] < 5 \
+                or not gt.is_contiguous() or not gt.is_cuda:
+            raise ValueError("overlay: gt must be a contiguous fp32 device tensor (F,G,>=5) with F=%d, got %s %r"
+                             % (F, getattr(gt, "dtype", type(gt)), tuple(getattr(gt, "shape", ()))))
+        G, gt_stride = int(gt.shape[1]), int(gt.shape[2])
+        if G > L.OVERLAY_MAX_ROWS:
+            raise ValueError("overlay: G=%d ground-truth rows per frame, vd_overlay takes at most %d" % (G, L.OVERLAY_MAX_ROWS))
+        if G == 0:
+            gt = None
+    V = 1
+    if clip_start is not None:
+        if torch.is_tensor(clip_start) and clip_start.is_cuda:
+            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+                raise ValueError("overlay: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                                 % (clip_start.dtype, tuple(clip_start.shape)))
+        else:
+            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+                raise ValueError("overlay: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
+            clip_start = torch.tensor(cs, dtype=torch.int32).to(dev, non_blocking=True)
+        V = int(clip_start.numel()) - 1
+    if out is None:
+        out = torch.empty_strided(tuple(frames.shape), tuple(frames.stride()), dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != tuple(frames.shape) \
+            or tuple(out.stride()) != tuple(frames.stride()):
+        raise ValueError("overlay: out must be a uint8 tensor of the frames' shape and strides on their device (or `frames` itself)")
+    need = L.OVERLAY_WS_PER_ROW * F * (N + G)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("overlay: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    # (the primitives launch resets the count; the paint launch alone adds to it)
+    painted = (torch.empty if stages is None or int(stages) & 1 else torch.zeros)(F, dtype=torch.int32, device=dev)
+    if F == 0 or N == 0:
+        if out.data_ptr() != frames.data_ptr():
+            out.copy_(frames)
+        return out, painted.zero_()
+    net = p["net_size"] or (h0, w0)
+    font = _overlay_table("font", dev, None, lambda: O.font_table())
+    pal = _overlay_table("palette", dev, (p["palette"].tobytes(), p["fmt"], p["matrix"], p["range"]),
+                         lambda: O.palette_words(p["palette"], p["fmt"], p["matrix"], p["range"]).view("int32"))
+    names = None
+    if p["class_names"]:
+        names = _overlay_table("names", dev, p["class_names"], lambda: O.names_table(p["class_names"]))
+    args = (ptr(frames), ptr(out), frame_stride, pitch, uv_offset, 1 if nv12 else 0, F, h0, w0, ptr(ids), ptr(scores), ptr(bboxes),
+            ptr(track), ptr(gt), gt_stride, ptr(clip_start), V, N, G, net[0], net[1], p["thresh"], p["thickness"], p["scale"],
+            p["trail"], 1 if p["color_by"] == "track" else 0, ptr(names), 0 if names is None else int(names.shape[0]), ptr(pal),
+            ptr(font), ptr(painted), ptr(ws), int(ws.numel()))
+    if stages is None:
+        check(_lib().vd_overlay(*args, _s()), "vd_overlay")
+    else:
+        check(_lib().vd_overlay_stages(*args, int(stages), _s()), "vd_overlay_stages")
+    return out, painted
+
+
 class TrackState:
     """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
     device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -

@@ -41,13 +41,6 @@ constexpr int kMaxFrames = 1 << 22;                   // pm << 20 stays inside i
 constexpr long long kInf = 1ll << 62;                 // a forbidden cell, a column that no path reaches
 constexpr int kQOne = 1 << 20;
 
-__device__ inline void clip_of(const int32_t* __restrict__ clip_start, int v, int F, int& t0, int& t1) {
-    t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[v], t1 = clip_start[v + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
-}
-
 // the quantised similarity of two boxes: a NaN counts as 0
 __device__ inline int quant(const float4 a, const float4 b) {
     const float s = iou(a, b);

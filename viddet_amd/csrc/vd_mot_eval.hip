@@ -42,20 +42,6 @@ constexpr long long kInf = 1ll << 62;                 // a forbidden cell, a col
 constexpr long long kDummy = 1ll << 27;
 constexpr int kQOne = 1 << 20;
 
-// the class of a prediction row, -1 where seq_nms.row_classes makes it no candidate
-__device__ inline int row_class(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return -1;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class ? c : -1;
-}
-
-__device__ inline void clip_of(const int32_t* __restrict__ clip_start, int v, int F, int& t0, int& t1) {
-    t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[v], t1 = clip_start[v + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
-}
-
 __global__ void k_mot_clear(int64_t rows, int32_t* __restrict__ match, float* __restrict__ miou, int32_t* __restrict__ flags,
                             uint32_t* __restrict__ adm) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {

@@ -24,6 +24,8 @@
 
 #pragma clang fp contract(off)
 
+#include "vd_clip_rows.h"
+
 namespace {
 
 constexpr int kWave = 64;
@@ -41,13 +43,6 @@ __device__ inline float iou(const float4 a, const float4 b) {
     const float inter = iw * ih;
     const float aa = (a.z - a.x) * (a.w - a.y), ab = (b.z - b.x) * (b.w - b.y);
     return inter / ((aa + ab) - inter);
-}
-
-// the class of a row, -1 where it is no candidate: id >= 0 (NaN is not), a finite score, a class below num_class
-__device__ inline int row_class(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return -1;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class ? c : -1;
 }
 
 // the workspace: [F*N][4] link words, [F*N][4] same-frame words, [F*N] new scores, [F*N] classes, [F*N] states, [F*N] next rows
@@ -131,10 +126,8 @@ __global__ __launch_bounds__(kWave) void k_seq_sweep(const float* __restrict__ s
     const int lane = threadIdx.x;
     const int c = blockIdx.y;
     const Ws ws = ws_split(ws_, (int64_t)F * N);
-    int t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[blockIdx.x], t1 = clip_start[blockIdx.x + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
+    int t0, t1;
+    clip_of(clip_start, blockIdx.x, F, t0, t1);
     if (t0 >= t1) return;
 
     for (;;) {

@@ -28,14 +28,6 @@ namespace {
 constexpr int kWaves = 8;                             // wavefronts of a clip's workgroup
 constexpr int kThreads = kWaves * kWave;
 
-__global__ void k_track_fill(int64_t n, int32_t* __restrict__ out_track, int32_t* __restrict__ out_len, float* __restrict__ out_score) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        out_track[i] = -1;
-        out_len[i] = 0;
-        out_score[i] = -1.f;
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void k_track(const float* __restrict__ ids, const float* __restrict__ scores,
                                                     const float* __restrict__ bboxes, const int32_t* __restrict__ clip_start, int F,
                                                     int N, int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min,
@@ -53,10 +45,8 @@ __global__ __launch_bounds__(kThreads) void k_track(const float* __restrict__ id
     __shared__ int p_row[kMaxActive];
     __shared__ int s_nact;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[blockIdx.x], t1 = clip_start[blockIdx.x + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
+    int t0, t1;
+    clip_of(clip_start, blockIdx.x, F, t0, t1);
     if (t0 >= t1) return;                             // the whole workgroup alike
     // the clip's tracks: ids [0, (t1 - t0) * N), so its slice of the tables starts at its first row
     int32_t* __restrict__ w_len = (int32_t*)ws + (int64_t)t0 * N;
@@ -220,10 +210,7 @@ int vd_track(const float* ids, const float* scores, const float* bboxes, const i
                "vd_track: ids, scores, clip_start, out_track, out_len, out_score and ws must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (clip_start) {                                 // a frame that no clip covers comes out as rows of -1 / 0 / -1
-        const int64_t n = (int64_t)F * N;
-        const int64_t blocks = vd_cdiv(n, 256);
-        hipLaunchKernelGGL(k_track_fill, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, n, out_track, out_len,
-                           out_score);
+        fill_uncovered<false>(s, (int64_t)F * N, out_track, out_len, out_score);
         VD_CHECK_LAUNCH("vd_track");
     }
     hipLaunchKernelGGL(k_track, dim3((unsigned)V), dim3(kThreads), 0, s, ids, scores, bboxes, clip_start, F, N, num_class, sigma_l,

@@ -45,16 +45,6 @@
 
 namespace {
 
-__global__ void k_byte_fill(int64_t n, int32_t* __restrict__ out_track, int32_t* __restrict__ out_len, float* __restrict__ out_score,
-                            float4* __restrict__ out_tbox) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        out_track[i] = -1;
-        out_len[i] = 0;
-        out_score[i] = -1.f;
-        out_tbox[i] = make_float4(-1.f, -1.f, -1.f, -1.f);
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void k_track_byte(const float* __restrict__ ids, const float* __restrict__ scores,
                                                          const float* __restrict__ bboxes, const int32_t* __restrict__ clip_start,
                                                          int F, int N, int num_class, float sigma_l, float sigma_d, float sigma_new,
@@ -83,10 +73,8 @@ __global__ __launch_bounds__(kThreads) void k_track_byte(const float* __restrict
     __shared__ int s_cnt_new[2];                      // the high rows among them that start a track
     __shared__ int s_nact;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    int t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[blockIdx.x], t1 = clip_start[blockIdx.x + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
+    int t0, t1;
+    clip_of(clip_start, blockIdx.x, F, t0, t1);
     if (t0 >= t1) return;                             // the whole workgroup alike
     // the clip's tracks: ids [0, (t1 - t0) * N), so its slice of the two per-track tables starts at its first row
     const int64_t clip_rows = (int64_t)(t1 - t0) * N;
@@ -295,42 +283,23 @@ __global__ __launch_bounds__(kThreads) void k_track_byte(const float* __restrict
 
 extern "C" {
 
-int64_t vd_track_byte_ws_bytes(int V, int F, int N) {
-    if (V < 1 || F < 1 || N < 1 || N > kMaxN || (int64_t)F * N > 0x7fffffff) return -1;
-    return (int64_t)VD_TRACK_SORT_WS_PER_ROW * F * N + (int64_t)VD_TRACK_SORT_WS_PER_CLIP * V;
-}
+int64_t vd_track_byte_ws_bytes(int V, int F, int N) { return kalman_link_ws_bytes(V, F, N, kMaxN); }
 
 int vd_track_byte(const float* ids, const float* scores, const float* bboxes, const int32_t* clip_start, int V, int F, int N,
                   int num_class, float sigma_l, float sigma_d, float sigma_new, float sigma_h, float sigma_iou, float sigma_iou2,
                   int t_min, int max_age, int32_t* out_track, int32_t* out_len, float* out_score, float* out_tbox, void* ws,
                   int64_t ws_bytes, void* stream) {
     static_assert(VD_TRACK_SORT_WS_PER_CLIP == 2 * kStateFloats * kMaxActive * 4, "two state tables per clip");
-    VD_REQUIRE(ids && scores && bboxes, "vd_track_byte: ids, scores and bboxes must not be NULL");
-    VD_REQUIRE(out_track && out_len && out_score && out_tbox, "vd_track_byte: the four output pointers must not be NULL");
-    VD_REQUIRE(ws, "vd_track_byte: ws must not be NULL");
-    VD_REQUIRE(N >= 1 && N <= kMaxN, "vd_track_byte: N=%d rows per frame, 1 <= N <= %d are taken", N, kMaxN);
-    VD_REQUIRE(F >= 1 && V >= 1, "vd_track_byte: F >= 1 and V >= 1 needed, got F=%d V=%d", F, V);
-    VD_REQUIRE((int64_t)F * N <= 0x7fffffff, "vd_track_byte: F * N = %lld rows, at most 2^31 - 1 are taken", (long long)F * N);
-    VD_REQUIRE(clip_start || V == 1, "vd_track_byte: clip_start may be NULL only with V == 1 (one clip [0, F)), got V=%d", V);
-    VD_REQUIRE(num_class >= 1, "vd_track_byte: num_class >= 1 needed, got %d", num_class);
+    const KalmanLinkArgs a = {"vd_track_byte", ids, scores, bboxes, clip_start, V, F, N, num_class, t_min, max_age, out_track, out_len,
+                              out_score, out_tbox, ws, ws_bytes};
+    if (const int e = kalman_link_rows(a, kMaxN)) return e;
     VD_REQUIRE(sigma_l == sigma_l && sigma_d == sigma_d && sigma_new == sigma_new && sigma_h == sigma_h && sigma_iou == sigma_iou &&
                    sigma_iou2 == sigma_iou2,
                "vd_track_byte: sigma_l, sigma_d, sigma_new, sigma_h, sigma_iou and sigma_iou2 must not be NaN");
-    VD_REQUIRE(t_min >= 1, "vd_track_byte: t_min >= 1 needed, got %d", t_min);
-    VD_REQUIRE(max_age >= 0 && max_age <= kMaxAge, "vd_track_byte: max_age=%d, 0 <= max_age <= %d are taken", max_age, kMaxAge);
-    const int64_t need = vd_track_byte_ws_bytes(V, F, N);
-    VD_REQUIRE(ws_bytes >= need, "vd_track_byte: ws_bytes=%lld, %d * F * N + %d * V = %lld needed", (long long)ws_bytes,
-               VD_TRACK_SORT_WS_PER_ROW, VD_TRACK_SORT_WS_PER_CLIP, (long long)need);
-    VD_REQUIRE((((uintptr_t)bboxes | (uintptr_t)out_tbox) % 16) == 0, "vd_track_byte: bboxes and out_tbox must be 16-byte aligned");
-    VD_REQUIRE((((uintptr_t)ids | (uintptr_t)scores | (uintptr_t)clip_start | (uintptr_t)out_track | (uintptr_t)out_len |
-                 (uintptr_t)out_score | (uintptr_t)ws) % 4) == 0,
-               "vd_track_byte: ids, scores, clip_start, out_track, out_len, out_score and ws must be 4-byte aligned");
+    if (const int e = kalman_link_ws(a, kMaxN, kMaxAge)) return e;
     hipStream_t s = (hipStream_t)stream;
     if (clip_start) {                                 // a frame that no clip covers comes out as rows of -1 / 0 / -1 / -1
-        const int64_t n = (int64_t)F * N;
-        const int64_t blocks = vd_cdiv(n, 256);
-        hipLaunchKernelGGL(k_byte_fill, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, n, out_track, out_len,
-                           out_score, (float4*)out_tbox);
+        fill_uncovered<true>(s, (int64_t)F * N, out_track, out_len, out_score, out_tbox);
         VD_CHECK_LAUNCH("vd_track_byte");
     }
     hipLaunchKernelGGL(k_track_byte, dim3((unsigned)V), dim3(kThreads), 0, s, ids, scores, bboxes, clip_start, F, N, num_class,

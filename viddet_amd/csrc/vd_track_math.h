@@ -9,6 +9,8 @@
 
 #pragma clang fp contract(off)
 
+#include "vd_clip_rows.h"
+
 namespace {
 
 constexpr int kWave = 64;
@@ -30,10 +32,10 @@ __device__ inline float iou(const float4 a, const float4 b) {
     return (iw > 0.f && ih > 0.f) ? q : 0.f;
 }
 
-// the class of a row, -1 where it is no candidate: id >= 0 (NaN is not), a finite score >= sigma_l, a class below num_class
+// the class of a row for a tracker, -1 where it is no candidate: vd_clip_rows.h's rule, and a score >= sigma_l
 __device__ inline int row_class(float id, float score, int num_class, float sigma_l) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u || !(score >= sigma_l)) return -1;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
+    if (!(id >= 0.f) || not_finite(score) || !(score >= sigma_l)) return -1;
+    const int c = class_of(id);
     return c < num_class ? c : -1;
 }
 

@@ -81,13 +81,6 @@ __device__ inline void smo_store(float* st, int64_t rows, int64_t row, const Kf&
     st[16 * rows + row] = s.p;
 }
 
-__device__ inline void clip_of(const int32_t* __restrict__ clip_start, int v, int F, int& t0, int& t1) {
-    t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[v], t1 = clip_start[v + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
-}
-
 __global__ void k_smo_clear(int64_t rows, const float* __restrict__ bboxes, float* __restrict__ out_sbox,
                             int32_t* __restrict__ out_slen) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x) {

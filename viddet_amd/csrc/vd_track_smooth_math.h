@@ -1,5 +1,5 @@
-// vd_track_smooth_math.h — the backward step of the Rauch-Tung-Striebel smoother of vd_track_kf.h's filter and the two row
-// predicates beside it, stated once for the kernels that smooth boxes along tracks: vd_track_smooth.hip (k_smo_seg, a finished
+// vd_track_smooth_math.h — the backward step of the Rauch-Tung-Striebel smoother of vd_track_kf.h's filter and the test of a
+// finite box beside it, stated once for the kernels that smooth boxes along tracks: vd_track_smooth.hip (k_smo_seg, a finished
 // clip) and vd_track_smooth_live.hip (k_smo_push, a stream in fixed-lag form).  viddet_amd/smooth.py is the definition (rts_step;
 // DESIGN.md 37).
 //
@@ -38,15 +38,7 @@ __device__ inline void smo_back(Sm& S, const Kf& f, const Kf& p) {
 }
 
 __device__ inline bool finite4(const float4 b) {
-    return (__float_as_uint(b.x) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(b.y) & 0x7f800000u) != 0x7f800000u &&
-           (__float_as_uint(b.z) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(b.w) & 0x7f800000u) != 0x7f800000u;
-}
-
-// a row is present iff seq_nms.row_classes makes it a candidate: id >= 0 (NaN is not), a finite score, a class below num_class
-__device__ inline bool row_present(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return false;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class;
+    return !not_finite(b.x) && !not_finite(b.y) && !not_finite(b.z) && !not_finite(b.w);
 }
 
 }  // namespace

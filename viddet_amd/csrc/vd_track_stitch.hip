@@ -9,7 +9,7 @@
 // sigma_iou` and `s > m` the plain comparisons; q = int(iou * 2^20) is exact; the assignment is integers, its potentials and
 // slacks int64.
 //
-// Launches: k_sti_fill only with clip_start (every row as a frame that no clip covers has it: -1 / 0 / -1), then k_track_stitch,
+// Launches: vd_clip_rows.h's fill only with clip_start (every row as a frame that no clip covers has it: -1 / 0 / -1), then k_track_stitch,
 // ONE workgroup of 256 threads per clip; no communication between workgroups.  Per clip:
 //   members    the frames in order, a thread per row: k_smo_member's rule - a present row whose id is usable and that no lower
 //              row of its frame carries is the id's member in the frame.  A member's track lives in the clip's table in the
@@ -106,22 +106,6 @@ __device__ inline void sti_store(float* st, int64_t rows, int64_t e, const Kf& s
     }
     st[15 * rows + e] = s.r;
     st[16 * rows + e] = s.p;
-}
-
-// the class of a row, -1 where seq_nms.row_classes makes it no candidate: id >= 0 (NaN is not), a finite score, a class below
-// num_class
-__device__ inline int present_class(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return -1;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class ? c : -1;
-}
-
-__global__ void k_sti_fill(int64_t n, int32_t* __restrict__ out_track, int32_t* __restrict__ out_len, float* __restrict__ out_score) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        out_track[i] = -1;
-        out_len[i] = 0;
-        out_score[i] = -1.f;
-    }
 }
 
 // The participants of the clip, in LDS
@@ -270,10 +254,8 @@ __global__ __launch_bounds__(kThreads) void k_track_stitch(const float* __restri
     __shared__ int s_wcnt[kWaves];
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
     const int v = blockIdx.x;
-    int t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[v], t1 = clip_start[v + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
+    int t0, t1;
+    clip_of(clip_start, v, F, t0, t1);
     if (t0 >= t1) {                                   // the whole workgroup alike
         if (tid == 0) out_stitches[v] = 0, out_overflow[v] = 0;
         return;
@@ -296,7 +278,7 @@ __global__ __launch_bounds__(kThreads) void k_track_stitch(const float* __restri
         if (tid < N) {
             const int id = track[row];
             sc = scores[row];
-            cls = present_class(ids[row], sc, num_class);
+            cls = row_class(ids[row], sc, num_class);
             if (cls >= 0 && id >= 0 && id < clip_rows) u = id;
         }
         if (tid < kMaxN) s_uid[tid] = u;
@@ -492,10 +474,7 @@ int vd_track_stitch(const float* ids, const float* scores, const float* bboxes, 
                "vd_track_stitch: ids, scores, track, clip_start, the five outputs and ws must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (clip_start) {                                 // a frame that no clip covers comes out as rows of -1 / 0 / -1
-        const int64_t n = (int64_t)F * N;
-        const int64_t blocks = vd_cdiv(n, 256);
-        hipLaunchKernelGGL(k_sti_fill, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s, n, out_track, out_len,
-                           out_score);
+        fill_uncovered<false>(s, (int64_t)F * N, out_track, out_len, out_score);
         VD_CHECK_LAUNCH("vd_track_stitch");
     }
     hipLaunchKernelGGL(k_track_stitch, dim3((unsigned)V), dim3(kThreads), 0, s, ids, scores, bboxes, track, clip_start, F, N,

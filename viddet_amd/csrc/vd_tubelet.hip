@@ -29,6 +29,8 @@
 
 #pragma clang fp contract(off)
 
+#include "vd_clip_rows.h"
+
 namespace {
 
 constexpr int kWave = 64;
@@ -58,20 +60,6 @@ __device__ inline Ws ws_of(void* ws, int64_t rows) {
     w.mx = (float*)(w.cnt + rows);
     w.last = (int32_t*)(w.mx + rows);
     return w;
-}
-
-// a row is present iff seq_nms.row_classes makes it a candidate: id >= 0 (NaN is not), a finite score, a class below num_class
-__device__ inline bool row_present(float id, float score, int num_class) {
-    if (!(id >= 0.f) || (__float_as_uint(score) & 0x7f800000u) == 0x7f800000u) return false;
-    const int c = id >= 2147483648.f ? 0x7fffffff : (int)id;
-    return c < num_class;
-}
-
-__device__ inline void clip_of(const int32_t* __restrict__ clip_start, int v, int F, int& t0, int& t1) {
-    t0 = 0, t1 = F;
-    if (clip_start) t0 = clip_start[v], t1 = clip_start[v + 1];
-    if (t0 < 0) t0 = 0;                               // offsets that are no offsets index nothing
-    if (t1 > F) t1 = F;
 }
 
 __global__ void k_tub_clear(int64_t rows, int F, float* __restrict__ out_ids, float* __restrict__ out_scores,

@@ -566,6 +566,110 @@ def coco_match(det, gt, iou_thrs, area_rng, rec_rank, rec_bits, npig):
                                K, _s()), "vd_coco_match")
 
 
+# --------------------------------------------------------------------------------------------
+# the clip-row contract: what every binding that takes the rows of a clip asks of ids, scores, bboxes, track,
+# clip_start and ws, stated once.  `who` is the binding's name, the front of every message.
+# --------------------------------------------------------------------------------------------
+def _int_arg(who, name, v, lo, hi=None):
+    """v as an int in [lo, hi] (hi None: unbounded); a bool or anything without __index__ is no integer"""
+    if isinstance(v, bool) or not hasattr(v, "__index__") or int(v) < lo or (hi is not None and int(v) > hi):
+        if hi is None:
+            raise ValueError("%s: %s must be an integer >= %d, got %r" % (who, name, lo, v))
+        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
+    return int(v)
+
+
+def _rows_shape(who, vd, bboxes, max_rows):
+    """(F, N) of bboxes (F,N,4); the entry point `vd` takes at most max_rows rows per frame"""
+    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
+        raise ValueError("%s: bboxes must be (F,N,4), got %r" % (who, tuple(getattr(bboxes, "shape", ()))))
+    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
+    if N > max_rows:
+        raise ValueError("%s: N=%d rows per frame, %s takes at most %d" % (who, N, vd, max_rows))
+    return F, N
+
+
+def _match_shape(who, gt_boxes, bboxes, max_frames=None):
+    """(F, G, N) of a matcher's gt_boxes (F,G,4) and bboxes (F,N,4): the same frames, 1 to MOT_MAX_ROWS rows of either"""
+    for name, t, axis in (("gt_boxes", gt_boxes, "G"), ("bboxes", bboxes, "N")):
+        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[-1] != 4:
+            raise ValueError("%s: %s must be (F,%s,4), got %r" % (who, name, axis, tuple(getattr(t, "shape", ()))))
+    F, G, N = int(gt_boxes.shape[0]), int(gt_boxes.shape[1]), int(bboxes.shape[1])
+    if int(bboxes.shape[0]) != F:
+        raise ValueError("%s: gt_boxes holds %d frames, bboxes %d" % (who, F, int(bboxes.shape[0])))
+    if max_frames is not None and F > max_frames:
+        raise ValueError("%s: gt_boxes holds F=%d frames, vd_%s takes at most %d" % (who, F, who, max_frames))
+    if not 1 <= G <= L.MOT_MAX_ROWS:
+        raise ValueError("%s: gt_boxes holds G=%d label rows per frame, vd_%s takes 1 to %d" % (who, G, who, L.MOT_MAX_ROWS))
+    if not 1 <= N <= L.MOT_MAX_ROWS:
+        raise ValueError("%s: bboxes holds N=%d prediction rows per frame, vd_%s takes 1 to %d" % (who, N, who, L.MOT_MAX_ROWS))
+    return F, G, N
+
+
+def _row_specs(ids, scores, bboxes, n, *track):
+    """the (name, tensor, numel, dtype) of n rows for _row_tensors; track: the (n,) int32 track table where the binding has one"""
+    f32 = torch.float32
+    return (("ids", ids, n, f32), ("scores", scores, n, f32), ("bboxes", bboxes, n * 4, f32)) + \
+        tuple(("track", t, n, torch.int32) for t in track)
+
+
+def _row_tensors(who, specs):
+    """every (name, tensor, numel, dtype) of specs is a contiguous device tensor of that many elements of that type"""
+    for name, t, n, dt in specs:
+        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("%s: %s must be a contiguous %s device tensor of %d elements, got %s %r"
+                             % (who, name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+
+
+def _tracked_rows(who, vd, ids, scores, bboxes, track, clip_start, num_class):
+    """the checks of a pass along tracks (tubelet, smooth, stitch), in their order -> (F, N, num_class, clip_start, V)"""
+    F, N = _rows_shape(who, vd, bboxes, L.TUBELET_MAX_ROWS)
+    num_class = _int_arg(who, "num_class", num_class, 1)
+    _row_tensors(who, _row_specs(ids, scores, bboxes, F * N, track))
+    if tuple(track.shape) != (F, N):
+        raise ValueError("%s: track must be (F,N) = (%d,%d), got %r" % (who, F, N, tuple(track.shape)))
+    return (F, N, num_class) + _clip_offsets(who, clip_start, F, bboxes.device)
+
+
+def _match_rows(who, gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, F, G, N, clip_start):
+    """a matcher's label rows and prediction rows, then its clip offsets -> (clip_start, V)"""
+    f32, i32 = torch.float32, torch.int32
+    _row_tensors(who, (("gt_boxes", gt_boxes, F * G * 4, f32), ("gt_cls", gt_cls, F * G, i32), ("gt_id", gt_id, F * G, i32))
+                 + _row_specs(ids, scores, bboxes, F * N, track))
+    for name, t, shape in (("gt_cls", gt_cls, (F, G)), ("gt_id", gt_id, (F, G)), ("track", track, (F, N))):
+        if tuple(t.shape) != shape:
+            raise ValueError("%s: %s must be %r, got %r" % (who, name, shape, tuple(t.shape)))
+    return _clip_offsets(who, clip_start, F, bboxes.device)
+
+
+def _clip_offsets(who, clip_start, F, device):
+    """-> (clip_start on the device or None, V): None is one clip of the F frames; V+1 ascending host offsets from 0 to F are
+    checked here, then uploaded; an int32 device vector of them is taken as it is"""
+    if clip_start is None:
+        return None, 1
+    if torch.is_tensor(clip_start) and clip_start.is_cuda:
+        if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
+            raise ValueError("%s: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
+                             % (who, clip_start.dtype, tuple(clip_start.shape)))
+    else:
+        cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
+        if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
+            raise ValueError("%s: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (who, F, cs))
+        clip_start = torch.tensor(cs, dtype=torch.int32).to(device, non_blocking=True)
+    return clip_start, int(clip_start.numel()) - 1
+
+
+def _workspace(who, ws, need, device, align=1, at_least=0):
+    """ws None: a new workspace of max(need, at_least) bytes on `device`; else ws itself, checked to hold need bytes"""
+    if ws is None:
+        return torch.empty(max(need, at_least), dtype=torch.uint8, device=device)
+    if not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda \
+            or ws.data_ptr() % align:
+        raise ValueError("%s: ws must be a contiguous%s uint8 device tensor of >= %d bytes"
+                         % (who, ", %d-byte aligned" % align if align > 1 else "", need))
+    return ws
+
+
 def seq_nms(ids, scores, bboxes, clip_start=None, num_class=1, link_thresh=0.5, nms_thresh=0.3, rescore="avg", ws=None, stages=None):
     """vd_seq_nms (viddet_amd/seq_nms.py::seq_nms_host on the device, bit for bit): ids (F,N[,1]), scores (F,N[,1]) and bboxes
     (F,N,4) are contiguous fp32 device tensors, N <= 128; clip_start: None (one clip), V+1 ascending host offsets from 0 to F
@@ -576,32 +680,10 @@ def seq_nms(ids, scores, bboxes, clip_start=None, num_class=1, link_thresh=0.5, 
     from .seq_nms import RESCORE
     if rescore not in RESCORE:
         raise ValueError("seq_nms: rescore must be 'avg' or 'max', got %r" % (rescore,))
-    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("seq_nms: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.SEQ_NMS_MAX_ROWS:
-        raise ValueError("seq_nms: N=%d rows per frame, vd_seq_nms takes at most %d" % (N, L.SEQ_NMS_MAX_ROWS))
-    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("seq_nms: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                             % (name, n, t.dtype, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("seq_nms: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("seq_nms: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.SEQ_NMS_WS_PER_ROW * F * N
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("seq_nms: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    F, N = _rows_shape("seq_nms", "vd_seq_nms", bboxes, L.SEQ_NMS_MAX_ROWS)
+    _row_tensors("seq_nms", _row_specs(ids, scores, bboxes, F * N))
+    clip_start, V = _clip_offsets("seq_nms", clip_start, F, bboxes.device)
+    ws = _workspace("seq_nms", ws, L.SEQ_NMS_WS_PER_ROW * F * N, bboxes.device)
     out_ids, out_scores, out_bboxes = torch.empty_like(ids), torch.empty_like(scores), torch.empty_like(bboxes)
     perm = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
     if F == 0 or N == 0:
@@ -623,32 +705,10 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
     one is allocated."""
     from .track import check_params
     sl, sh, si, t_min, max_age = check_params(sigma_l, sigma_h, sigma_iou, t_min, max_age, "track")
-    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("track: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TRACK_MAX_ROWS:
-        raise ValueError("track: N=%d rows per frame, vd_track takes at most %d" % (N, L.TRACK_MAX_ROWS))
-    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("track: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                             % (name, n, t.dtype, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("track: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("track: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TRACK_WS_PER_ROW * F * N
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("track: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    F, N = _rows_shape("track", "vd_track", bboxes, L.TRACK_MAX_ROWS)
+    _row_tensors("track", _row_specs(ids, scores, bboxes, F * N))
+    clip_start, V = _clip_offsets("track", clip_start, F, bboxes.device)
+    ws = _workspace("track", ws, L.TRACK_WS_PER_ROW * F * N, bboxes.device)
     out_track = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
     out_len = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
     out_score = torch.empty(F, N, dtype=torch.float32, device=bboxes.device)
@@ -663,32 +723,10 @@ def track(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, sigma_
 def _kalman_link_args(who, ids, scores, bboxes, clip_start, ws):
     """The tensor checks, clip offsets, workspace and outputs that ops.track_sort and ops.track_byte share ->
     (V, F, N, clip_start on the device or None, ws, (out_track, out_len, out_score, out_tbox))"""
-    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("%s: bboxes must be (F,N,4), got %r" % (who, tuple(bboxes.shape)))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TRACK_MAX_ROWS:
-        raise ValueError("%s: N=%d rows per frame, vd_%s takes at most %d" % (who, N, who, L.TRACK_MAX_ROWS))
-    for name, t, n in (("ids", ids, F * N), ("scores", scores, F * N), ("bboxes", bboxes, F * N * 4)):
-        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("%s: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                             % (who, name, n, t.dtype, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("%s: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (who, clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("%s: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (who, F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_WS_PER_CLIP * V
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("%s: ws must be a contiguous uint8 device tensor of >= %d bytes" % (who, need))
+    F, N = _rows_shape(who, "vd_" + who, bboxes, L.TRACK_MAX_ROWS)
+    _row_tensors(who, _row_specs(ids, scores, bboxes, F * N))
+    clip_start, V = _clip_offsets(who, clip_start, F, bboxes.device)
+    ws = _workspace(who, ws, L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_WS_PER_CLIP * V, bboxes.device)
     outs = (torch.empty(F, N, dtype=torch.int32, device=bboxes.device), torch.empty(F, N, dtype=torch.int32, device=bboxes.device),
             torch.empty(F, N, dtype=torch.float32, device=bboxes.device), torch.empty(F, N, 4, dtype=torch.float32, device=bboxes.device))
     return V, F, N, clip_start, ws, outs
@@ -742,37 +780,8 @@ def tubelet(ids, scores, bboxes, track, clip_start=None, num_class=1, rescore="a
     (vd_tubelet_stages) and the outputs may stay unwritten."""
     from .tubelet import RESCORE, check_params
     rescore, max_gap, drop_untracked = check_params(rescore, max_gap, drop_untracked, "tubelet")
-    if bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("tubelet: bboxes must be (F,N,4), got %r" % (tuple(bboxes.shape),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TUBELET_MAX_ROWS:
-        raise ValueError("tubelet: N=%d rows per frame, vd_tubelet takes at most %d" % (N, L.TUBELET_MAX_ROWS))
-    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
-        raise ValueError("tubelet: num_class must be an integer >= 1, got %r" % (num_class,))
-    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
-                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("tubelet: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if tuple(track.shape) != (F, N):
-        raise ValueError("tubelet: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("tubelet: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("tubelet: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TUBELET_WS_PER_ROW * F * N
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("tubelet: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    F, N, num_class, clip_start, V = _tracked_rows("tubelet", "vd_tubelet", ids, scores, bboxes, track, clip_start, num_class)
+    ws = _workspace("tubelet", ws, L.TUBELET_WS_PER_ROW * F * N, bboxes.device)
     dev = bboxes.device
     out_ids, out_scores, out_bboxes = torch.empty_like(ids), torch.empty_like(scores), torch.empty_like(bboxes)
     perm = torch.empty(F, N, dtype=torch.int32, device=dev)
@@ -801,37 +810,8 @@ def smooth(ids, scores, bboxes, track, clip_start=None, num_class=1, max_gap=7, 
     stay unwritten."""
     from .smooth import check_params
     max_gap = check_params(max_gap, "smooth")
-    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("smooth: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TUBELET_MAX_ROWS:
-        raise ValueError("smooth: N=%d rows per frame, vd_track_smooth takes at most %d" % (N, L.TUBELET_MAX_ROWS))
-    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
-        raise ValueError("smooth: num_class must be an integer >= 1, got %r" % (num_class,))
-    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
-                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("smooth: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if tuple(track.shape) != (F, N):
-        raise ValueError("smooth: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("smooth: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("smooth: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TRACK_SMOOTH_WS_PER_ROW * F * N
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("smooth: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    F, N, num_class, clip_start, V = _tracked_rows("smooth", "vd_track_smooth", ids, scores, bboxes, track, clip_start, num_class)
+    ws = _workspace("smooth", ws, L.TRACK_SMOOTH_WS_PER_ROW * F * N, bboxes.device)
     sbox = torch.empty_like(bboxes)
     slen = torch.empty(F, N, dtype=torch.int32, device=bboxes.device)
     if F == 0 or N == 0:
@@ -855,37 +835,8 @@ def stitch(ids, scores, bboxes, track, clip_start=None, num_class=1, max_gap=30,
     is downloaded and nothing waits.  ws: a uint8 device tensor of >= 100*F*N bytes to reuse, else one is allocated."""
     from .stitch import check_params
     max_gap, sigma_iou = check_params(max_gap, sigma_iou, "stitch")
-    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("stitch: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.TUBELET_MAX_ROWS:
-        raise ValueError("stitch: N=%d rows per frame, vd_track_stitch takes at most %d" % (N, L.TUBELET_MAX_ROWS))
-    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
-        raise ValueError("stitch: num_class must be an integer >= 1, got %r" % (num_class,))
-    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
-                           ("bboxes", bboxes, F * N * 4, torch.float32), ("track", track, F * N, torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("stitch: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if tuple(track.shape) != (F, N):
-        raise ValueError("stitch: track must be (F,N) = (%d,%d), got %r" % (F, N, tuple(track.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("stitch: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("stitch: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.TRACK_STITCH_WS_PER_ROW * F * N
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("stitch: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    F, N, num_class, clip_start, V = _tracked_rows("stitch", "vd_track_stitch", ids, scores, bboxes, track, clip_start, num_class)
+    ws = _workspace("stitch", ws, L.TRACK_STITCH_WS_PER_ROW * F * N, bboxes.device)
     dev = bboxes.device
     strack = torch.empty(F, N, dtype=torch.int32, device=dev)
     tlen = torch.empty(F, N, dtype=torch.int32, device=dev)
@@ -912,46 +863,11 @@ def mot_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, clip_start=No
     thr = check_iou_thresh(iou_thresh, "mot_match")
     if type(agnostic).__name__ not in ("bool", "bool_"):
         raise ValueError("mot_match: agnostic must be a bool, got %r" % (agnostic,))
-    for name, t in (("gt_boxes", gt_boxes), ("bboxes", bboxes)):
-        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[-1] != 4:
-            raise ValueError("mot_match: %s must be (F,%s,4), got %r" % (name, "G" if name == "gt_boxes" else "N", tuple(getattr(t, "shape", ()))))
-    F, G, N = int(gt_boxes.shape[0]), int(gt_boxes.shape[1]), int(bboxes.shape[1])
-    if int(bboxes.shape[0]) != F:
-        raise ValueError("mot_match: gt_boxes holds %d frames, bboxes %d" % (F, int(bboxes.shape[0])))
-    if not 1 <= G <= L.MOT_MAX_ROWS:
-        raise ValueError("mot_match: gt_boxes holds G=%d label rows per frame, vd_mot_match takes 1 to %d" % (G, L.MOT_MAX_ROWS))
-    if not 1 <= N <= L.MOT_MAX_ROWS:
-        raise ValueError("mot_match: bboxes holds N=%d prediction rows per frame, vd_mot_match takes 1 to %d" % (N, L.MOT_MAX_ROWS))
-    if isinstance(num_class, bool) or not hasattr(num_class, "__index__") or int(num_class) < 1:
-        raise ValueError("mot_match: num_class must be an integer >= 1, got %r" % (num_class,))
-    f32, i32 = torch.float32, torch.int32
-    for name, t, n, dt in (("gt_boxes", gt_boxes, F * G * 4, f32), ("gt_cls", gt_cls, F * G, i32), ("gt_id", gt_id, F * G, i32),
-                           ("ids", ids, F * N, f32), ("scores", scores, F * N, f32), ("bboxes", bboxes, F * N * 4, f32),
-                           ("track", track, F * N, i32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("mot_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    for name, t, shape in (("gt_cls", gt_cls, (F, G)), ("gt_id", gt_id, (F, G)), ("track", track, (F, N))):
-        if tuple(t.shape) != shape:
-            raise ValueError("mot_match: %s must be %r, got %r" % (name, shape, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("mot_match: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("mot_match: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = L.MOT_WS_PER_ROW * F * (G + N)
-    if ws is None:
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=bboxes.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("mot_match: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
-    dev = bboxes.device
+    F, G, N = _match_shape("mot_match", gt_boxes, bboxes)
+    num_class = _int_arg("mot_match", "num_class", num_class, 1)
+    clip_start, V = _match_rows("mot_match", gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, F, G, N, clip_start)
+    ws = _workspace("mot_match", ws, L.MOT_WS_PER_ROW * F * (G + N), bboxes.device, at_least=1)
+    dev, f32, i32 = bboxes.device, torch.float32, torch.int32
     match = torch.empty(F, G, dtype=i32, device=dev)
     miou = torch.empty(F, G, dtype=f32, device=dev)
     flags = torch.empty(F, G, dtype=i32, device=dev)
@@ -974,51 +890,13 @@ def hota_match(gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, num_gt_id, n
     (whatever it holds), else one is allocated."""
     if type(agnostic).__name__ not in ("bool", "bool_"):
         raise ValueError("hota_match: agnostic must be a bool, got %r" % (agnostic,))
-    for name, t in (("gt_boxes", gt_boxes), ("bboxes", bboxes)):
-        if not torch.is_tensor(t) or t.dim() != 3 or t.shape[-1] != 4:
-            raise ValueError("hota_match: %s must be (F,%s,4), got %r" % (name, "G" if name == "gt_boxes" else "N", tuple(getattr(t, "shape", ()))))
-    F, G, N = int(gt_boxes.shape[0]), int(gt_boxes.shape[1]), int(bboxes.shape[1])
-    if int(bboxes.shape[0]) != F:
-        raise ValueError("hota_match: gt_boxes holds %d frames, bboxes %d" % (F, int(bboxes.shape[0])))
-    if F > L.HOTA_MAX_FRAMES:
-        raise ValueError("hota_match: gt_boxes holds F=%d frames, vd_hota_match takes at most %d" % (F, L.HOTA_MAX_FRAMES))
-    if not 1 <= G <= L.MOT_MAX_ROWS:
-        raise ValueError("hota_match: gt_boxes holds G=%d label rows per frame, vd_hota_match takes 1 to %d" % (G, L.MOT_MAX_ROWS))
-    if not 1 <= N <= L.MOT_MAX_ROWS:
-        raise ValueError("hota_match: bboxes holds N=%d prediction rows per frame, vd_hota_match takes 1 to %d" % (N, L.MOT_MAX_ROWS))
-    for name, v, hi in (("num_gt_id", num_gt_id, L.HOTA_MAX_GT_IDS), ("num_track", num_track, 2 ** 31 - 1), ("num_class", num_class, 2 ** 31 - 1)):
-        if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
-            raise ValueError("hota_match: %s must be an integer in [1, %d], got %r" % (name, hi, v))
-    A, P = int(num_gt_id), int(num_track)
-    f32, i32 = torch.float32, torch.int32
-    for name, t, n, dt in (("gt_boxes", gt_boxes, F * G * 4, f32), ("gt_cls", gt_cls, F * G, i32), ("gt_id", gt_id, F * G, i32),
-                           ("ids", ids, F * N, f32), ("scores", scores, F * N, f32), ("bboxes", bboxes, F * N * 4, f32),
-                           ("track", track, F * N, i32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("hota_match: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    for name, t, shape in (("gt_cls", gt_cls, (F, G)), ("gt_id", gt_id, (F, G)), ("track", track, (F, N))):
-        if tuple(t.shape) != shape:
-            raise ValueError("hota_match: %s must be %r, got %r" % (name, shape, tuple(t.shape)))
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("hota_match: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("hota_match: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(bboxes.device, non_blocking=True)
-        V = int(clip_start.numel()) - 1
-    need = hota_ws_bytes(V, A, P)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda \
-            or ws.data_ptr() % 8:
-        raise ValueError("hota_match: ws must be a contiguous, 8-byte aligned uint8 device tensor of >= %d bytes" % need)
-    dev = bboxes.device
+    F, G, N = _match_shape("hota_match", gt_boxes, bboxes, L.HOTA_MAX_FRAMES)
+    A = _int_arg("hota_match", "num_gt_id", num_gt_id, 1, L.HOTA_MAX_GT_IDS)
+    P = _int_arg("hota_match", "num_track", num_track, 1, 2 ** 31 - 1)
+    num_class = _int_arg("hota_match", "num_class", num_class, 1, 2 ** 31 - 1)
+    clip_start, V = _match_rows("hota_match", gt_boxes, gt_cls, gt_id, ids, scores, bboxes, track, F, G, N, clip_start)
+    ws = _workspace("hota_match", ws, hota_ws_bytes(V, A, P), bboxes.device, align=8)
+    dev, f32, i32 = bboxes.device, torch.float32, torch.int32
     match = torch.empty(F, G, dtype=i32, device=dev)
     msim = torch.empty(F, G, dtype=f32, device=dev)
     mscore = torch.empty(F, G, dtype=i32, device=dev)
@@ -1068,11 +946,7 @@ def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, o
     nv12 = p["fmt"] == "nv12"
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
         raise ValueError("overlay: frames must be a uint8 tensor, got %s" % (getattr(frames, "dtype", type(frames)),))
-    if not torch.is_tensor(bboxes) or bboxes.dim() != 3 or bboxes.shape[-1] != 4:
-        raise ValueError("overlay: bboxes must be (F,N,4), got %r" % (tuple(getattr(bboxes, "shape", ())),))
-    F, N = int(bboxes.shape[0]), int(bboxes.shape[1])
-    if N > L.OVERLAY_MAX_ROWS:
-        raise ValueError("overlay: N=%d rows per frame, vd_overlay takes at most %d" % (N, L.OVERLAY_MAX_ROWS))
+    F, N = _rows_shape("overlay", "vd_overlay", bboxes, L.OVERLAY_MAX_ROWS)
     if nv12 and frames.dim() == 1:
         if H0 is None or W0 is None or pitch is None:
             raise ValueError("overlay: a 1-D NV12 surface needs H0, W0 and pitch")
@@ -1109,12 +983,7 @@ def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, o
     if not frames.is_cuda:
         raise ValueError("overlay: frames must be a device tensor")
     dev = frames.device
-    for name, t, n, dt in (("ids", ids, F * N, torch.float32), ("scores", scores, F * N, torch.float32),
-                           ("bboxes", bboxes, F * N * 4, torch.float32)) + \
-            ((("track", track, F * N, torch.int32),) if track is not None else ()):
-        if not torch.is_tensor(t) or t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError("overlay: %s must be a contiguous %s device tensor of %d elements, got %s %r"
-                             % (name, str(dt).split(".")[-1], n, getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    _row_tensors("overlay", _row_specs(ids, scores, bboxes, F * N, *(() if track is None else (track,))))
     G, gt_stride = 0, 0
     if gt is not None:
         if not torch.is_tensor(gt) or gt.dtype != torch.float32 or gt.dim() != 3 or gt.shape[0] != F or gt.shape[2] < 5 \
@@ -1126,28 +995,13 @@ def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, o
             raise ValueError("overlay: G=%d ground-truth rows per frame, vd_overlay takes at most %d" % (G, L.OVERLAY_MAX_ROWS))
         if G == 0:
             gt = None
-    V = 1
-    if clip_start is not None:
-        if torch.is_tensor(clip_start) and clip_start.is_cuda:
-            if clip_start.dtype != torch.int32 or clip_start.dim() != 1 or clip_start.numel() < 2 or not clip_start.is_contiguous():
-                raise ValueError("overlay: a device clip_start must be a contiguous int32 vector of V+1 offsets, got %s %r"
-                                 % (clip_start.dtype, tuple(clip_start.shape)))
-        else:
-            cs = [int(v) for v in (clip_start.tolist() if hasattr(clip_start, "tolist") else clip_start)]
-            if len(cs) < 2 or cs[0] != 0 or cs[-1] != F or any(b < a for a, b in zip(cs, cs[1:])):
-                raise ValueError("overlay: clip_start must be V+1 ascending offsets from 0 to F=%d, got %r" % (F, cs))
-            clip_start = torch.tensor(cs, dtype=torch.int32).to(dev, non_blocking=True)
-        V = int(clip_start.numel()) - 1
+    clip_start, V = _clip_offsets("overlay", clip_start, F, dev)
     if out is None:
         out = torch.empty_strided(tuple(frames.shape), tuple(frames.stride()), dtype=torch.uint8, device=dev)
     elif not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != tuple(frames.shape) \
             or tuple(out.stride()) != tuple(frames.stride()):
         raise ValueError("overlay: out must be a uint8 tensor of the frames' shape and strides on their device (or `frames` itself)")
-    need = L.OVERLAY_WS_PER_ROW * F * (N + G)
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not torch.is_tensor(ws) or ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or not ws.is_cuda:
-        raise ValueError("overlay: ws must be a contiguous uint8 device tensor of >= %d bytes" % need)
+    ws = _workspace("overlay", ws, L.OVERLAY_WS_PER_ROW * F * (N + G), dev)
     # (the primitives launch resets the count; the paint launch alone adds to it)
     painted = (torch.empty if stages is None or int(stages) & 1 else torch.zeros)(F, dtype=torch.int32, device=dev)
     if F == 0 or N == 0:
@@ -1172,7 +1026,46 @@ def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, o
     return out, painted
 
 
-class TrackState:
+class _StreamState:
+    """What the live-state classes share: V streams of N rows per frame, a zeroed uint8 state tensor (V, bytes) - all zero is
+    a fresh stream -, the frames pushed since the last reset, and the checks of a push."""
+
+    _IDS = "hand out"                                 # what a push does with track ids, in the refusal of too many frames
+
+    def _open(self, V, N, num_class, state_bytes, device):
+        who = type(self).__name__
+        self.V = _int_arg(who, "V", V, 1, 2 ** 31 - 1)
+        self.N = _int_arg(who, "N", N, 1, L.TRACK_MAX_ROWS)
+        self.num_class = _int_arg(who, "num_class", num_class, 1, 2 ** 31 - 1)
+        self.state = torch.zeros(self.V, state_bytes, dtype=torch.uint8, device=device)
+        self.frames = 0                               # pushed to every stream since the last reset
+
+    def reset(self):
+        self.state.zero_()
+        self.frames = 0
+
+    def _push_rows(self, ids, scores, bboxes, *track):
+        """the checks of push(ids, scores, bboxes[, track]) -> (lead, F): the outputs' leading shape (V,F) or (F,), the frames"""
+        who, V, N = type(self).__name__ + ".push", self.V, self.N
+        lead = tuple(getattr(bboxes, "shape", ())[:-2])
+        if not torch.is_tensor(bboxes) or bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N \
+                or (lead[:-1] or (1,)) != (V,):
+            raise ValueError("%s: bboxes must be (%d,F,%d,4)%s, got %r"
+                             % (who, V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(getattr(bboxes, "shape", ()))))
+        F = int(lead[-1])
+        _row_tensors(who, _row_specs(ids, scores, bboxes, V * F * N))
+        for t in track:
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != lead + (N,) or not t.is_contiguous() \
+                    or not t.is_cuda:
+                raise ValueError("%s: track must be a contiguous int32 device tensor %r, got %s %r"
+                                 % (who, lead + (N,), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+        if (self.frames + F) * N > 2 ** 31 - 1:
+            raise ValueError("%s: %d + %d frames of %d rows could %s more than 2**31 - 1 track ids; reset() the state (a new clip) "
+                             "first" % (who, self.frames, F, N, self._IDS))
+        return lead, F
+
+
+class TrackState(_StreamState):
     """The tracker on V streams that never say where they end (vd_track_push; viddet_amd/track.py::track_online_host on the
     device, bit for bit): owns the state tensor (V, VD_TRACK_STATE_BYTES) uint8 - all zero is a fresh stream -
     and the fixed parameters.  push(ids, scores, bboxes) runs the next F frames of every stream: ids (V,F,N[,1]), scores
@@ -1185,31 +1078,11 @@ class TrackState:
     def __init__(self, V=1, N=100, num_class=1, sigma_l=0.0, sigma_iou=0.5, max_age=0, device="cuda"):
         from .track import check_params
         self.sigma_l, _, self.sigma_iou, _, self.max_age = check_params(sigma_l, 0.5, sigma_iou, 1, max_age, "TrackState")
-        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
-            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
-                raise ValueError("TrackState: %s must be an integer in [1, %d], got %r" % (name, hi, v))
-        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
-        self.state = torch.zeros(self.V, L.TRACK_STATE_BYTES, dtype=torch.uint8, device=device)
-        self.frames = 0                               # pushed to every stream since the last reset
-
-    def reset(self):
-        self.state.zero_()
-        self.frames = 0
+        self._open(V, N, num_class, L.TRACK_STATE_BYTES, device)
 
     def push(self, ids, scores, bboxes):
         V, N = self.V, self.N
-        lead = tuple(bboxes.shape[:-2])
-        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
-            raise ValueError("TrackState.push: bboxes must be (%d,F,%d,4)%s, got %r"
-                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
-        F = int(lead[-1])
-        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
-            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError("TrackState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                                 % (name, n, t.dtype, tuple(t.shape)))
-        if (self.frames + F) * N > 2 ** 31 - 1:
-            raise ValueError("TrackState.push: %d + %d frames of %d rows could hand out more than 2**31 - 1 track ids; reset() "
-                             "the state (a new clip) first" % (self.frames, F, N))
+        lead, F = self._push_rows(ids, scores, bboxes)
         dev = bboxes.device
         out_track = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
         out_len = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
@@ -1223,7 +1096,7 @@ class TrackState:
         return out_track, out_len, out_score
 
 
-class KalmanTrackState:
+class KalmanTrackState(_StreamState):
     """SORT or BYTE on V streams that never say where they end (vd_track_kf_push; viddet_amd/sort.py::sort_online_host and
     viddet_amd/byte.py::byte_online_host on the device, bit for bit, DESIGN.md 39): owns the state tensor
     (V, VD_TRACK_KF_STATE_BYTES) uint8 - the tracks' words and their filter states; all zero is a fresh stream - and the fixed
@@ -1258,34 +1131,14 @@ class KalmanTrackState:
         else:
             from .byte import check_byte_params
             sl, sd, sn, si, si2, _, _, age = check_byte_params(sigma_h=0.5, t_min=1, who=who, **kw)
-        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
-            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
-                raise ValueError("%s: %s must be an integer in [1, %d], got %r" % (who, name, hi, v))
+        self._open(V, N, num_class, L.TRACK_KF_STATE_BYTES, device)
         self.method, self.params = method, kw
         self.sigma_l, self.sigma_d, self.sigma_new, self.sigma_iou, self.sigma_iou2 = (float(v) for v in (sl, sd, sn, si, si2))
         self.max_age = age
-        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
-        self.state = torch.zeros(self.V, L.TRACK_KF_STATE_BYTES, dtype=torch.uint8, device=device)
-        self.frames = 0                               # pushed to every stream since the last reset
-
-    def reset(self):
-        self.state.zero_()
-        self.frames = 0
 
     def push(self, ids, scores, bboxes):
         V, N = self.V, self.N
-        lead = tuple(bboxes.shape[:-2])
-        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
-            raise ValueError("KalmanTrackState.push: bboxes must be (%d,F,%d,4)%s, got %r"
-                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
-        F = int(lead[-1])
-        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
-            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError("KalmanTrackState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                                 % (name, n, t.dtype, tuple(t.shape)))
-        if (self.frames + F) * N > 2 ** 31 - 1:
-            raise ValueError("KalmanTrackState.push: %d + %d frames of %d rows could hand out more than 2**31 - 1 track ids; "
-                             "reset() the state (a new clip) first" % (self.frames, F, N))
+        lead, F = self._push_rows(ids, scores, bboxes)
         dev = bboxes.device
         out_track = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
         out_len = torch.empty(lead + (N,), dtype=torch.int32, device=dev)
@@ -1301,7 +1154,7 @@ class KalmanTrackState:
         return out_track, out_len, out_score, out_tbox
 
 
-class SmoothLagState:
+class SmoothLagState(_StreamState):
     """Fixed-lag smoothing of the boxes of V streams along their tracks (vd_track_smooth_push;
     viddet_amd/smooth_lag.py::smooth_lag_host on the device, bit for bit, DESIGN.md 40): owns the state tensor
     (V, VD_TRACK_SMOOTH_LIVE_STATE_BYTES) uint8 - the last 16 frames' members, boxes, posterior states and links; all zero is a
@@ -1314,28 +1167,21 @@ class SmoothLagState:
     Every stream takes the same frames, so m is one number, counted on the host: launches on the current stream, nothing is
     downloaded and nothing waits.  A push that could take frames * N past 2**31 - 1 is refused."""
 
+    _IDS = "meet"                                     # this pass is handed the ids of a tracker
+
     def __init__(self, V=1, N=100, num_class=1, lag=None, max_gap=7, device="cuda"):
         from .smooth_lag import check_params
         who = "SmoothLagState"
         if lag is None:
             raise ValueError("%s: lag must be given: a frame comes out `lag` frames late, an integer in [0, 15]" % who)
         self.lag, self.max_gap = check_params(lag, max_gap, who)
-        for name, v, hi in (("V", V, 2 ** 31 - 1), ("N", N, L.TRACK_MAX_ROWS), ("num_class", num_class, 2 ** 31 - 1)):
-            if isinstance(v, bool) or not hasattr(v, "__index__") or not 1 <= int(v) <= hi:
-                raise ValueError("%s: %s must be an integer in [1, %d], got %r" % (who, name, hi, v))
-        self.V, self.N, self.num_class = int(V), int(N), int(num_class)
-        self.state = torch.zeros(self.V, L.TRACK_SMOOTH_LIVE_STATE_BYTES, dtype=torch.uint8, device=device)
-        self.frames = 0                               # taken from every stream since the last reset
+        self._open(V, N, num_class, L.TRACK_SMOOTH_LIVE_STATE_BYTES, device)
         self._lead = (self.V,) if self.V > 1 else ()  # the outputs' leading shape: the last push's
 
     @property
     def emitted(self):
         """the frames given out since the last reset"""
         return max(0, self.frames - self.lag)
-
-    def reset(self):
-        self.state.zero_()
-        self.frames = 0
 
     def _launch(self, ids, scores, bboxes, track, lead, F, flush):
         V, N = self.V, self.N
@@ -1353,22 +1199,7 @@ class SmoothLagState:
         return t0, sbox, slen
 
     def push(self, ids, scores, bboxes, track):
-        V, N = self.V, self.N
-        lead = tuple(bboxes.shape[:-2])
-        if bboxes.dim() not in (3, 4) or bboxes.shape[-1] != 4 or bboxes.shape[-2] != N or (lead[:-1] or (1,)) != (V,):
-            raise ValueError("SmoothLagState.push: bboxes must be (%d,F,%d,4)%s, got %r"
-                             % (V, N, " or (F,%d,4)" % N if V == 1 else "", tuple(bboxes.shape)))
-        F = int(lead[-1])
-        for name, t, n in (("ids", ids, V * F * N), ("scores", scores, V * F * N), ("bboxes", bboxes, V * F * N * 4)):
-            if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
-                raise ValueError("SmoothLagState.push: %s must be a contiguous float32 device tensor of %d elements, got %s %r"
-                                 % (name, n, t.dtype, tuple(t.shape)))
-        if track.dtype != torch.int32 or tuple(track.shape) != lead + (N,) or not track.is_contiguous() or not track.is_cuda:
-            raise ValueError("SmoothLagState.push: track must be a contiguous int32 device tensor %r, got %s %r"
-                             % (lead + (N,), track.dtype, tuple(track.shape)))
-        if (self.frames + F) * N > 2 ** 31 - 1:
-            raise ValueError("SmoothLagState.push: %d + %d frames of %d rows could meet more than 2**31 - 1 track ids; "
-                             "reset() the state (a new clip) first" % (self.frames, F, N))
+        lead, F = self._push_rows(ids, scores, bboxes, track)
         self._lead = lead[:-1]
         return self._launch(ids, scores, bboxes, track, lead[:-1], F, False)
 

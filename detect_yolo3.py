@@ -179,6 +179,19 @@ def parse_flags(argv=None):
            "tracker from push to push on the device (net.open_video(track={..., 'online': True}), vd_track_kf_push, DESIGN.md "
            "39); the files and results are those of the --stream run byte for byte.  Not without --live and not with "
            "--track_method iou, whose tracker is always online")
+    A("--track_app", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --stream --track --track_method sort: appearance association (DESIGN.md 43) - every "
+           "row gets an int8 descriptor pooled from the backbone's own route tensor under its box (vd_roi_embed) and SORT links on "
+           "the fused cost of geometry and appearance (vd_track_sort_app): a box joins a track where its IoU to the predicted box "
+           "is at least --track_iou, or at least --track_app_prox with a descriptor cosine of at least --track_app_cos.  The files "
+           "are those --track_method sort writes.  Not with --live, --seq_nms, a late join or without --stream")
+    A("--track_app_cos", type=float, default=None,
+      help="--track_app: the least cosine of the descriptors of a box and a track that admits the pair, 0 to 1 (default 0.8, "
+           "provisional)")
+    A("--track_app_prox", type=float, default=None,
+      help="--track_app: the least IoU to the predicted box at which appearance may admit a pair, 0 to 1 (default 0.1, provisional)")
+    A("--track_app_level", type=int, default=None,
+      help="--track_app: the stride of the route tensor the descriptors are pooled from, 8 (256 channels, the default), 16 or 32")
     A("--track_iou", type=float, default=None,
       help="--track: a box joins a track where its IoU to the track's last box (sort, byte: its predicted box) is at least this "
            "(default: iou 0.5, sort 0.3, byte 0.2)")
@@ -294,7 +307,21 @@ def track_args(FLAGS):
                 t_min=FLAGS.track_min_len, max_age=given("track_max_age", "max_age"))
     if method == "byte":
         args.update({key: given(flag, key) for flag, key in _BYTE_FLAGS})
+    if getattr(FLAGS, "track_app", False):
+        args["appearance"] = app_args(FLAGS)
     return dict(args, method=method) if method != "iou" else args
+
+
+_APP_FLAGS = (("track_app_cos", "sigma_app"), ("track_app_prox", "sigma_prox"), ("track_app_level", "level"))   # --track_app's own
+
+
+def app_args(FLAGS):
+    """the `appearance` dict of detect_video's track option, None without --track_app; a flag left out takes
+    viddet_amd.appearance's default"""
+    if not getattr(FLAGS, "track_app", False):
+        return None
+    from viddet_amd.appearance import OPTION_DEFAULTS
+    return {key: OPTION_DEFAULTS[key] if getattr(FLAGS, flag, None) is None else getattr(FLAGS, flag) for flag, key in _APP_FLAGS}
 
 
 def link_rows(ids, scores, bboxes, track, **kw):
@@ -695,7 +722,7 @@ def check_flags(FLAGS):
         from viddet_amd.byte import check_byte_params
         from viddet_amd.track import check_params
         try:
-            params = {k: v for k, v in track_args(FLAGS).items() if k != "method"}
+            params = {k: v for k, v in track_args(FLAGS).items() if k not in ("method", "appearance")}
             (check_byte_params if getattr(FLAGS, "track_method", "iou") == "byte" else check_params)(who="--track", **params)
         except ValueError as e:
             names = dict(sigma_iou2="--track_iou2", sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high",
@@ -706,6 +733,36 @@ def check_flags(FLAGS):
             raise NotImplementedError(msg)
     elif getattr(FLAGS, "track_online", False):
         raise NotImplementedError("--track_online needs --track: it chooses how a live session carries the tracker")
+    if getattr(FLAGS, "track_app", False):
+        # appearance association is detect_video's, on SORT's cost: refused elsewhere, never ignored
+        if not getattr(FLAGS, "track", False) or getattr(FLAGS, "track_method", "iou") != "sort":
+            raise NotImplementedError("--track_app needs --track --track_method sort: the fused cost of geometry and appearance is "
+                                      "defined for SORT's association alone")
+        if not getattr(FLAGS, "stream", False):
+            raise NotImplementedError("--track_app needs --stream: the descriptors are pooled from the feature maps net.detect_video "
+                                      "holds on the device; the windowed path keeps none")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_app does not combine with --live: a live session does not carry the descriptors of "
+                                      "its frames from push to push")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--track_app does not combine with --seq_nms: Seq-NMS permutes the rows ahead of the tracker, "
+                                      "the descriptors belong to the rows as detected")
+        if int(FLAGS.window[0]) > 1 and FLAGS.k_join_pos == "late":
+            raise NotImplementedError("--track_app does not combine with --k_join_pos %s: the ring of a late join holds the neck's "
+                                      "tips, not the backbone's route tensors the descriptor is pooled from" % FLAGS.k_join_pos)
+        from viddet_amd.appearance import LEVELS, check_app_params
+        a = app_args(FLAGS)
+        if isinstance(a["level"], bool) or a["level"] not in LEVELS:
+            raise NotImplementedError("--track_app_level must be 8, 16 or 32, got %r" % (a["level"],))
+        try:
+            check_app_params(a["sigma_app"], a["sigma_prox"], who="--track_app")
+        except ValueError as e:
+            raise NotImplementedError(str(e).replace("--track_app: sigma_app", "--track_app_cos")
+                                      .replace("--track_app: sigma_prox", "--track_app_prox"))
+    else:
+        for flag, _ in _APP_FLAGS:
+            if getattr(FLAGS, flag, None) is not None:
+                raise NotImplementedError("--%s needs --track_app: it is a parameter of appearance association" % flag)
     if getattr(FLAGS, "tubelet", False):
         # the tubelet pass runs over the tracks of a finished clip
         if not getattr(FLAGS, "track", False):

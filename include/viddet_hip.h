@@ -989,6 +989,41 @@ int vd_track_sort(const float* ids, const float* scores, const float* bboxes, co
                   int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age, int32_t* out_track,
                   int32_t* out_len, float* out_score, float* out_tbox, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- The appearance descriptor of detected rows, pooled from a route tensor of the backbone (vd_appearance.hip, DESIGN.md
+ * 43): what viddet_amd.appearance.embed_host computes, bit for bit.  fmap [S][Hf][Wf][ld]: S NHWC maps of C channels at a pixel
+ * pitch of ld >= C elements, fp32 or (is_bf16 = 1) bf16, upcast exactly; ids [B][N], bboxes [B][N][4] in network-input pixels;
+ * image b reads map map_index[b] (b itself where map_index is NULL), cut to [0, S); stride: the map's, 8, 16 or 32;
+ * emb [B][N][C] int8, written in full.  Every step is one fp32 operation, nothing contracted, `/` correctly rounded.  A row
+ * whose id is not >= 0 or that holds a coordinate that is not finite has no descriptor: zeros.  Else, with bw = x2 - x1 and
+ * k = (.125, .375, .625, .875): cx_i = (x1 + bw * k_i) * (1 / stride) - 0.5, below 0 (or NaN) -> 0, above Wf - 1 -> Wf - 1;
+ * x0 = min(floor(cx), max(Wf - 2, 0)), x1i = min(x0 + 1, Wf - 1), ax = cx - x0; y alike; per channel the sample
+ * t = f[y0][x0] + ax * (f[y0][x1i] - f[y0][x0]), u alike on row y1i, v = t + ay * (u - t); the 16 samples summed one after the
+ * other, y outer and x inner, times 0.0625 = p; m = hsum(p) / C with hsum the halving sum (p[:n/2] + p[n/2:n] until one is
+ * left); d = p - m; a = max |d| (a NaN travels); a == 0 or not finite: zeros; else q = int8(rint((d / a) * 127)), ties to even.
+ * One workgroup per row, four channels a thread.  C a power of two in [8, 1024], ld a multiple of 4, 1 <= N <= 128, B >= 1;
+ * fmap aligned to four of its elements, bboxes to 16 bytes, every other pointer to 4.  The inputs are never written. */
+int vd_roi_embed(const void* fmap, int is_bf16, int S, int Hf, int Wf, int C, int ld, const float* ids, const float* bboxes,
+                 const int32_t* map_index, int B, int N, int stride, int8_t* emb, void* stream);
+
+/* ---- SORT with appearance association (vd_track_sort_app.hip): what viddet_amd.appearance.app_sort_host
+ * computes, bit for bit, on all four outputs.  Everything is vd_track_sort's - the arguments, the candidates, the filter, the
+ * assignment, the update, the decision, the outputs, the limits and the alignment - but the cost of a cell.  emb [F][N][C] int8
+ * (vd_roi_embed's, C a power of two in [8, 1024], 4-byte aligned): the descriptor of every row, zeros: none.  A track's
+ * descriptor is that of its most recent matched row that had one (the row that started it counts).  For row i and track k of
+ * equal classes, with dot, na, nb the exact dot product and squared norms of the two descriptors: cos_q = 0 when dot <= 0 or a
+ * norm is 0, else floor(double(dot) * 2^20 / sqrt(double(na) * double(nb))); adm = iou >= sigma_iou; app = iou >= sigma_prox
+ * and both norms > 0 and cos_q >= int(sigma_app * 2^20); the cell is admissible iff adm or app and costs
+ * 2^20 - max(int(iou * 2^20) if adm else 0, cos_q if app else 0).  sigma_app and sigma_prox lie in [0, 1].  With emb all zero
+ * the outputs are vd_track_sort's.  The cells of a frame are written once into a table of 128 x 1024 int32 per clip and read by
+ * the assignment: ws holds vd_track_sort's words, VD_TRACK_SORT_WS_PER_ROW bytes per (frame, row), and
+ * VD_TRACK_SORT_APP_WS_PER_CLIP bytes per clip.  vd_track_sort_app_ws_bytes: the bytes ws must hold, -1 for sizes not taken. */
+#define VD_TRACK_SORT_APP_WS_PER_CLIP 663552
+int64_t vd_track_sort_app_ws_bytes(int V, int F, int N);
+int vd_track_sort_app(const float* ids, const float* scores, const float* bboxes, const int8_t* emb, int C, const int32_t* clip_start,
+                      int V, int F, int N, int num_class, float sigma_l, float sigma_h, float sigma_iou, int t_min, int max_age,
+                      float sigma_app, float sigma_prox, int32_t* out_track, int32_t* out_len, float* out_score, float* out_tbox,
+                      void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- The detections of video clips linked into tracks by BYTE (vd_track_byte.hip): what
  * viddet_amd.byte.byte_host computes, bit for bit, on all four outputs - Zhang et al., "ByteTrack: Multi-Object Tracking by
  * Associating Every Detection Box" (ECCV 2022).  Everything is vd_track_sort's - the arguments, the candidates (score >=

@@ -21,6 +21,8 @@ TRACK_WS_PER_ROW = 8                                # vd_track: workspace bytes 
 TRACK_STATE_BYTES = 36880                           # vd_track_push: bytes of one stream's state (VD_TRACK_STATE_BYTES)
 TRACK_SORT_WS_PER_ROW = 8                           # vd_track_sort: workspace bytes per (frame, row) (VD_TRACK_SORT_WS_PER_ROW)
 TRACK_SORT_WS_PER_CLIP = 139264                     # vd_track_sort: and per clip, two tables of 17 x 1024 state floats
+TRACK_SORT_APP_WS_PER_CLIP = 663552                 # vd_track_sort_app: per clip, the state tables and 128 x 1024 int32 cells
+EMBED_MIN_C, EMBED_MAX_C, EMBED_MAX_ROWS = 8, 1024, 128   # vd_roi_embed: channels (a power of two), rows per image (vd_appearance.hip)
 TRACK_KF_STATE_BYTES = 159760                       # vd_track_kf_push: bytes of one stream's state (VD_TRACK_KF_STATE_BYTES)
 TRACK_SMOOTH_LIVE_STATE_BYTES = 221264              # vd_track_smooth_push: bytes of one stream's state (VD_TRACK_SMOOTH_LIVE_STATE_BYTES)
 TUBELET_MAX_ROWS = 128                              # vd_tubelet: rows per frame (vd_tubelet.hip)
@@ -219,6 +221,11 @@ SIGNATURES = {
     # the detections of video clips linked into tracks by SORT: Kalman prediction, optimal assignment (vd_track_sort.hip)
     "vd_track_sort_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_track_sort": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),
+    # the appearance descriptor of detected rows, pooled from a route tensor of the backbone (vd_appearance.hip)
+    "vd_roi_embed": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _i, _p, _p]),
+    # SORT with appearance association: the fused cost of a cell, read from a table (vd_track_sort_app.hip)
+    "vd_track_sort_app_ws_bytes": (_i64, [_i, _i, _i]),
+    "vd_track_sort_app": (_i, [_p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _f, _f, _f, _i, _i, _f, _f, _p, _p, _p, _p, _p, _i64, _p]),
     # ... and by BYTE: a second association of the low-score rows (vd_track_byte.hip); the workspace is vd_track_sort's
     "vd_track_byte_ws_bytes": (_i64, [_i, _i, _i]),
     "vd_track_byte": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _i, _p, _p, _p, _p, _p, _i64, _p]),

@@ -13,6 +13,9 @@ smoother on the device as well (ops.SmoothLagState, vd_track_smooth_push, DESIGN
 import torch
 
 from . import ops
+from .appearance import LEVELS as APP_LEVELS
+from .appearance import parse_option as parse_appearance
+from .appearance import split_appearance
 from .overlay import parse_option as parse_overlay
 from .seq_nms import parse_option as parse_seq_nms
 from .smooth import parse_option as parse_smooth
@@ -48,13 +51,17 @@ class StreamEngine:
     suffix program runs (K = 1: the plain plan at batch `chunk`, a shorter last chunk padded with repeats of its last frame).
     Returns the dict of emitted tensors - ids, scores, bboxes, rows, overflow - as new tensors over the m >= 0 frames of the
     suffix actions.  `stats` counts the frames through each part; with keep_heads, `heads` collects the three raw head
-    tensors of every K > 1 suffix launch."""
+    tensors of every K > 1 suffix launch.  With `appearance` (appearance.parse_option's dict) every suffix action
+    is followed by ops.roi_embed on the route tensor of that level - the plain plan's buffer (K = 1) or the feature ring of
+    the early join, read in place through the frames' slots - with the program's own ids and bboxes; `embs` collects the
+    descriptors of the emitted frames and, with keep_maps, `app_maps` a clone of the maps every launch read, in frame order."""
 
-    def __init__(self, net, step, chunk):
+    def __init__(self, net, step, chunk, appearance=None):
         self.net, self.chunk = net, chunk
         self.plan = StreamPlanner(net._k, step, chunk)
         self.stats = dict(prefix_frames=0, suffix_frames=0, chunks=0)
         self.heads = []
+        self.app, self.embs, self.app_maps = appearance, [], []
 
     def _programs(self, H, W):
         """the two programs at this clip's size, current (K > 1)"""
@@ -84,6 +91,15 @@ class StreamEngine:
                 ring[:m - m0].copy_(src[m0:m])
         self.stats['prefix_frames'] += m
 
+    def _embed(self, fmap, o, map_index, n):
+        """the descriptors of a suffix launch's rows off `fmap` (the level's route tensor: the plan's buffer or the ring)"""
+        from .model import ROUTE_TENSORS
+        _, c, stride = ROUTE_TENSORS[APP_LEVELS[self.app["level"]]]
+        maps = fmap[..., :c]                                      # the plans pad a pixel's pitch: a view, read in place
+        self.embs.append(ops.roi_embed(maps, o['ids'], o['bboxes'], stride, map_index=map_index)[:n])
+        if self.app["keep_maps"]:                                 # tests: what the launch read, in frame order
+            self.app_maps.append((maps[:n] if map_index is None else maps[map_index[:n].long()]).clone())
+
     def _suffix(self, sp, frames, base, t0, n, T, hw, keep_heads):
         net = self.net
         if net._k == 1:
@@ -92,16 +108,27 @@ class StreamEngine:
             if n < self.chunk:
                 x = torch.cat([x, x[-1:].expand((self.chunk - n,) + tuple(x.shape[1:]))], dim=0)
             net._forward_infer(x)
-            o = net._programs[('infer_bf16' if net.precision == 'bf16' else 'infer', self.chunk) + tuple(hw)][2]
+            prog = net._programs[('infer_bf16' if net.precision == 'bf16' else 'infer', self.chunk) + tuple(hw)]
+            o = prog[2]
+            if self.app is not None:
+                self._embed(prog[1][self._app_name()], o, None, n)
         else:
             sp['slots'].copy_(torch.from_numpy(self.plan.slots(t0, n, T)))
             sp['suf'].run()
             o = sp['o']
             if keep_heads:                                        # tests: the raw head tensors of every chunk
                 self.heads.append([sp['sb'][h][:n].clone() for h in net.head_names])
+            if self.app is not None:                              # frame t lives in slot t % S; a padded row repeats the last
+                S = self.plan.S
+                slot = [min(t0 + i, t0 + n - 1) % S for i in range(self.chunk)]
+                self._embed(sp['sb']['ring:' + self._app_name()], o, torch.tensor(slot, dtype=torch.int32).to(net.device), n)
         self.stats['suffix_frames'] += n
         self.stats['chunks'] += 1
         return {k: o[k][:n].clone() for k in ('ids', 'scores', 'bboxes', 'rows', 'overflow')}
+
+    def _app_name(self):
+        from .model import ROUTE_TENSORS
+        return ROUTE_TENSORS[APP_LEVELS[self.app["level"]]][0]
 
     def run(self, acts, frames, base, T, hw, keep_heads=False):
         net = self.net
@@ -160,7 +187,13 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         raise RuntimeError("detect_video: %r has frames in flight on this net (they share the feature ring): flush() it first"
                            % (net._live,))
     seq = parse_seq_nms(seq_nms, net.post_nms, "detect_video")
+    track, app = split_appearance(track)
     trk = parse_track(track, net.post_nms, "detect_video")
+    app = parse_appearance(app, None if trk is None else trk[2], seq is not None, "detect_video")
+    if app is not None and net._k > 1 and net._k_join_pos != 'early':
+        raise NotImplementedError("detect_video with track's appearance and k_join_pos %r: the ring of the late join holds the "
+                                  "neck's tips, not the backbone's route tensors the descriptor is pooled from"
+                                  % (net._k_join_pos,))
     tub_kw = parse_tubelet(tubelet, trk is not None, "detect_video")
     smo_kw = parse_smooth(smooth, trk is not None, "detect_video")
     sti_kw = parse_stitch(stitch, trk is not None, "detect_video")
@@ -173,6 +206,7 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
             raise ValueError("detect_video: overlay's inplace needs frames on the device; host frames are painted on their upload")
     net.last_overlay = None
     net.last_tracks = net.last_track_boxes = None
+    net.last_embeddings = net.last_app_maps = None
     net.last_tubelet = net.last_pre_tubelet = None
     net.last_smooth = net.last_pre_smooth = None
     net.last_stitch = net.last_pre_stitch = None
@@ -183,13 +217,16 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         raise ValueError("detect_video needs step >= 1 and chunk >= 1, got step=%d chunk=%d" % (step, chunk))
     T, H, W = frame_shape(net, frames, "an NV12 clip", "a clip", "T")
     assert 0 < net.nms_thresh < 1, "nms_thresh outside (0,1) (NMS disabled) is not implemented"
-    eng = StreamEngine(net, step, chunk)
+    eng = StreamEngine(net, step, chunk, appearance=app)
     acts = eng.plan.push(T) + eng.plan.flush()
     out = eng.run(acts, frames, 0, T, (H, W), keep_heads=getattr(net, 'stream_keep_heads', False))
     net.stream_stats = eng.stats
     net.stream_heads = [torch.cat(h) for h in zip(*eng.heads)] if eng.heads else None
     net.last_rows, net.last_overflow = out['rows'], out['overflow']
     res = out['ids'], out['scores'], out['bboxes']
+    if app is not None:
+        net.last_embeddings = torch.cat(eng.embs)
+        net.last_app_maps = torch.cat(eng.app_maps) if app["keep_maps"] else None
     num_class = 1 if net.agnostic else net.num_class
     if seq is not None:
         net.last_plain = res                                      # the rows ahead of Seq-NMS
@@ -199,7 +236,11 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         res = ids, scores, bboxes
     if trk is not None:
         boxes = res[2] if trk[1] is None else res[2].clamp(0, float(trk[1]))
-        if trk[2] in ("sort", "byte"):                            # SORT, BYTE: the triple as ever, the filtered boxes beside it
+        if app is not None:                                       # SORT on the fused cost of geometry and appearance
+            *links, net.last_track_boxes = ops.track_sort_app(res[0], res[1], boxes, net.last_embeddings, num_class=num_class,
+                                                              sigma_app=app["sigma_app"], sigma_prox=app["sigma_prox"], **trk[0])
+            net.last_tracks = tuple(links)
+        elif trk[2] in ("sort", "byte"):                          # SORT, BYTE: the triple as ever, the filtered boxes beside it
             link = ops.track_sort if trk[2] == "sort" else ops.track_byte
             *links, net.last_track_boxes = link(res[0], res[1], boxes, num_class=num_class, **trk[0])
             net.last_tracks = tuple(links)
@@ -283,7 +324,10 @@ class VideoSession:
         self.track_decide = None
         self._trk_kw = self._trk_clip = self._trk = None
         self._trk_method = "iou"
-        track, online = split_online(track, "open_video")
+        if split_appearance(track)[1] not in (None, False):
+            raise NotImplementedError("open_video with track's appearance: the descriptors of a session's frames are not carried "
+                                      "from push to push (run detect_video on the finished clip)")
+        track, online = split_online(split_appearance(track)[0], "open_video")
         trk = parse_track(track, net.post_nms, "open_video")
         if trk is not None:
             if trk[2] != "iou" and not online:

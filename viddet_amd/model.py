@@ -2268,7 +2268,14 @@ class YOLOV3(object):
         the missing parameters then take viddet_amd.sort's defaults, sigma_iou 0.3 and max_age 1) or 'byte' (BYTE: SORT with
         a second association of the low-score rows, ops.track_byte; it takes sigma_d, sigma_new and sigma_iou2
         as well, and the missing parameters take viddet_amd.byte's defaults); with 'sort' and 'byte' last_track_boxes
-        (T,post_nms,4) holds the filtered box of every tracked row, otherwise it is None.
+        (T,post_nms,4) holds the filtered box of every tracked row, otherwise it is None.  With 'sort', a further key
+        `appearance`: True or {'level': 8 | 16 | 32, 'sigma_app': a, 'sigma_prox': p} - every chunk's rows get an int8
+        descriptor pooled from the backbone's route tensor of that stride under their boxes (ops.roi_embed; the plain plan's
+        buffer with k = 1, the feature ring of an early join with k > 1) and the tracker links on the fused cost of geometry
+        and appearance (ops.track_sort_app).  last_embeddings (T,post_nms,C) int8 holds the descriptors and is
+        None after a call without the key; with 'keep_maps': True (tests) last_app_maps holds a clone of the maps every
+        launch read, in frame order.  Refused with 'iou' and 'byte', beside seq_nms (it permutes the rows ahead of the
+        tracker), with a late join (its ring holds neck tips, not routes) and by open_video.
 
         tubelet: None (the default), True, or a dict of rescore / max_gap / drop_untracked; needs `track` - the rows the tracker
         saw (those of Seq-NMS where that is on, clipped where track's `clip` is given) go through the tubelet pass on the device

@@ -750,6 +750,73 @@ def track_sort(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.0, s
     return outs
 
 
+def roi_embed(fmap, ids, bboxes, stride, map_index=None, out=None):
+    """vd_roi_embed (viddet_amd/appearance.py::embed_host on the device, bit for bit, DESIGN.md 43): the int8 appearance
+    descriptor of every row, pooled from a route tensor under the row's box.  fmap: a fp32 or bf16 device tensor (S,Hf,Wf,C) whose
+    last axis is dense and whose other axes are dense over a pixel pitch of ld >= C elements (a view [..., :C] of a padded plan
+    buffer is taken as it is); ids (B,N[,1]) and bboxes (B,N,4) contiguous fp32 device tensors, N <= 128; map_index: None (image
+    b reads map b) or an int32 device vector of B entries; out: an int8 device tensor (B,N,C) to write, else one is allocated.
+    Returns emb (B,N,C) int8.  Launches on the current stream; nothing is downloaded and nothing waits."""
+    from .appearance import check_embed_shape
+    if not torch.is_tensor(fmap) or fmap.dim() != 4 or not fmap.is_cuda or fmap.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("roi_embed: fmap must be a fp32 or bf16 device tensor (S,Hf,Wf,C), got %s %r"
+                         % (getattr(fmap, "dtype", type(fmap)), tuple(getattr(fmap, "shape", ()))))
+    S, Hf, Wf, Cn = (int(v) for v in fmap.shape)
+    Cn, stride = check_embed_shape(Cn, stride, "roi_embed")
+    if S < 1 or Hf < 1 or Wf < 1:
+        raise ValueError("roi_embed: fmap must hold at least one map of one cell, got %r" % (tuple(fmap.shape),))
+    # the pitch of a pixel: what the innermost axis of more than one entry says; a single pixel has none to say
+    ld = int(fmap.stride(2)) if Wf > 1 else int(fmap.stride(1)) if Hf > 1 else int(fmap.stride(0)) if S > 1 else Cn
+    if fmap.stride(3) != 1 or ld < Cn or (Hf > 1 and fmap.stride(1) != Wf * ld) or (S > 1 and fmap.stride(0) != Hf * Wf * ld):
+        raise ValueError("roi_embed: fmap must be NHWC, dense over a pixel pitch >= C, got shape %r strides %r"
+                         % (tuple(fmap.shape), tuple(fmap.stride())))
+    F, N = _rows_shape("roi_embed", "vd_roi_embed", bboxes, L.EMBED_MAX_ROWS)
+    f32 = torch.float32
+    _row_tensors("roi_embed", (("ids", ids, F * N, f32), ("bboxes", bboxes, F * N * 4, f32)))
+    if map_index is not None:
+        _row_tensors("roi_embed", (("map_index", map_index, F, torch.int32),))
+    elif F > S:
+        raise ValueError("roi_embed: %d images and %d maps: map_index must say which map an image reads" % (F, S))
+    if out is None:
+        out = torch.empty(F, N, Cn, dtype=torch.int8, device=bboxes.device)
+    else:
+        _row_tensors("roi_embed", (("out", out, F * N * Cn, torch.int8),))
+    if F == 0 or N == 0:
+        return out
+    check(_lib().vd_roi_embed(ptr(fmap), int(fmap.dtype == torch.bfloat16), S, Hf, Wf, Cn, ld, ptr(ids), ptr(bboxes), ptr(map_index),
+                              F, N, stride, ptr(out), _s()), "vd_roi_embed")
+    return out
+
+
+def track_sort_app(ids, scores, bboxes, emb, clip_start=None, num_class=1, sigma_l=0.0, sigma_h=0.5, sigma_iou=0.3, t_min=2,
+                   max_age=1, sigma_app=0.8, sigma_prox=0.1, ws=None):
+    """vd_track_sort_app (viddet_amd/appearance.py::app_sort_host on the device, bit for bit, DESIGN.md 43): SORT with the fused
+    cost of geometry and appearance.  The inputs are ops.track_sort's and emb (F,N,C), a contiguous int8 device tensor,
+    ops.roi_embed's; the returned (track, tlen, tscore, tbox) are ops.track_sort's.  Launches on the current stream; nothing is
+    downloaded and nothing waits.  ws: a uint8 device tensor of >= 8*F*N + 663552*V bytes to reuse, else one is allocated."""
+    from .appearance import check_app_params, check_embed_shape
+    from .track import check_params
+    sl, sh, si, t_min, max_age = check_params(sigma_l, sigma_h, sigma_iou, t_min, max_age, "track_sort_app")
+    sa, sp = check_app_params(sigma_app, sigma_prox, "track_sort_app")
+    F, N = _rows_shape("track_sort_app", "vd_track_sort_app", bboxes, L.TRACK_MAX_ROWS)
+    _row_tensors("track_sort_app", _row_specs(ids, scores, bboxes, F * N))
+    if not torch.is_tensor(emb) or emb.dim() != 3 or tuple(emb.shape[:2]) != (F, N):
+        raise ValueError("track_sort_app: emb must be (F,N,C) = (%d,%d,C), got %r" % (F, N, tuple(getattr(emb, "shape", ()))))
+    Cn, _ = check_embed_shape(int(emb.shape[2]), 8, "track_sort_app")
+    _row_tensors("track_sort_app", (("emb", emb, F * N * Cn, torch.int8),))
+    clip_start, V = _clip_offsets("track_sort_app", clip_start, F, bboxes.device)
+    ws = _workspace("track_sort_app", ws, L.TRACK_SORT_WS_PER_ROW * F * N + L.TRACK_SORT_APP_WS_PER_CLIP * V, bboxes.device)
+    dev = bboxes.device
+    outs = (torch.empty(F, N, dtype=torch.int32, device=dev), torch.empty(F, N, dtype=torch.int32, device=dev),
+            torch.empty(F, N, dtype=torch.float32, device=dev), torch.empty(F, N, 4, dtype=torch.float32, device=dev))
+    if F == 0 or N == 0:
+        return outs
+    check(_lib().vd_track_sort_app(ptr(ids), ptr(scores), ptr(bboxes), ptr(emb), Cn, ptr(clip_start), V, F, N, int(num_class),
+                                   float(sl), float(sh), float(si), t_min, max_age, float(sa), float(sp), ptr(outs[0]),
+                                   ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), ptr(ws), int(ws.numel()), _s()), "vd_track_sort_app")
+    return outs
+
+
 def track_byte(ids, scores, bboxes, clip_start=None, num_class=1, sigma_l=0.1, sigma_d=0.5, sigma_new=0.6, sigma_iou=0.2,
                sigma_iou2=0.5, sigma_h=0.5, t_min=2, max_age=7, ws=None):
     """vd_track_byte (viddet_amd/byte.py::byte_host on the device, bit for bit, DESIGN.md 36): BYTE - SORT's filter and

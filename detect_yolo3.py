@@ -59,7 +59,7 @@ import numpy as np
 import torch
 
 from viddet_amd import dist as vdist
-from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticTracks, SyntheticVideo, \
+from viddet_amd.data import SyntheticDetection, SyntheticCombined, SyntheticPan, SyntheticTracks, SyntheticVideo, \
     YOLO3VideoInferenceTransform, Loader
 from viddet_amd.metrics import VOCMApMetric
 from viddet_amd.vid_metric import VIDDetectionMetric
@@ -192,6 +192,22 @@ def parse_flags(argv=None):
       help="--track_app: the least IoU to the predicted box at which appearance may admit a pair, 0 to 1 (default 0.1, provisional)")
     A("--track_app_level", type=int, default=None,
       help="--track_app: the stride of the route tensor the descriptors are pooled from, 8 (256 channels, the default), 16 or 32")
+    A("--track_gmc", type=_bool, nargs="?", const=True, default=False,
+      help="(no reference counterpart) with --stream --track: camera-motion compensation (DESIGN.md 44) - the translation of the "
+           "whole picture between consecutive frames is estimated on the device from the frames' luma (vd_motion_sig, "
+           "vd_motion_match), summed along the clip and taken off the boxes the tracker links (vd_motion_shift).  Every file of "
+           "the run without the flag is written, from the same detections; motion.txt beside them holds one line `clip frame dx "
+           "dy sad_best sad_zero` per frame.  Not with --live, --track_smooth, --tubelet or without --stream")
+    A("--track_gmc_cell", type=int, default=None,
+      help="--track_gmc: the side of a signature cell in source pixels, 2, 4, 8 or 16 (default 4): the unit of the motion")
+    A("--track_gmc_radius", type=int, default=None,
+      help="--track_gmc: the largest displacement searched per frame, in cells, 1 to 16 (default 8)")
+    A("--track_gmc_gate", type=float, default=None,
+      help="--track_gmc: the best displacement is taken where its SAD is at most this share of the SAD at no displacement, else "
+           "the frame counts as unmoved; above 0, at most 1 (default 0.75, provisional)")
+    A("--synthetic_pan", type=int, default=0,
+      help="(no reference counterpart) the dataset is SyntheticPan: SyntheticTracks' objects seen by a camera that steps by up to "
+           "this many pixels a frame over a textured canvas (default 0: the sets as before)")
     A("--track_iou", type=float, default=None,
       help="--track: a box joins a track where its IoU to the track's last box (sort, byte: its predicted box) is at least this "
            "(default: iou 0.5, sort 0.3, byte 0.2)")
@@ -309,7 +325,21 @@ def track_args(FLAGS):
         args.update({key: given(flag, key) for flag, key in _BYTE_FLAGS})
     if getattr(FLAGS, "track_app", False):
         args["appearance"] = app_args(FLAGS)
+    if getattr(FLAGS, "track_gmc", False):
+        args["gmc"] = gmc_args(FLAGS)
     return dict(args, method=method) if method != "iou" else args
+
+
+_GMC_FLAGS = (("track_gmc_cell", "cell"), ("track_gmc_radius", "radius"), ("track_gmc_gate", "gate"))           # --track_gmc's own
+
+
+def gmc_args(FLAGS):
+    """the `gmc` dict of detect_video's track option, None without --track_gmc; a flag left out takes viddet_amd.motion's
+    default"""
+    if not getattr(FLAGS, "track_gmc", False):
+        return None
+    from viddet_amd.motion import DEFAULTS
+    return {key: DEFAULTS[key] if getattr(FLAGS, flag, None) is None else getattr(FLAGS, flag) for flag, key in _GMC_FLAGS}
 
 
 _APP_FLAGS = (("track_app_cos", "sigma_app"), ("track_app_prox", "sigma_prox"), ("track_app_level", "level"))   # --track_app's own
@@ -485,7 +515,7 @@ def live_clip(net, frames, step, chunk, push, track=None, smooth=None):
 
 def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, world=1, device_resize=False, frame_format="rgb",
                   seq_nms=None, input_nms=0.45, track=None, live=None, tubelet=None, smooth=None, stitch=None, track_online=False,
-                  smooth_lag=None, visualise=None):
+                  smooth_lag=None, visualise=None, motion_log=None):
     """--stream: what detect() collects, one whole clip at a time through net.detect_video - whole clips are sharded over
     the ranks (a clip's feature ring lives on one GPU).  device_resize: the clip travels at its source size (frame_format
     'nv12': as NV12 frames).  seq_nms (a dict): handed to detect_video; returns (boxes, rescored), the plain rows being the
@@ -502,7 +532,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
     stitch (a dict, with track, without the four): handed to detect_video likewise; the tracker's ids are the ones it keeps in
     net.last_pre_stitch, the fifth element is None and the sixth holds the stitched ids of the plain rows.
     visualise (visualise_args' dict, not with live): detect_video draws what it returns onto every clip's frames on the device
-    (its `overlay`) and write_overlay writes every `every`-th one as a PPM file; nothing else changes."""
+    (its `overlay`) and write_overlay writes every `every`-th one as a PPM file; nothing else changes.
+    motion_log (a list, with a `gmc` key in track: --track_gmc): receives (clip, frame, dx, dy, sad_best, sad_zero)
+    for every frame, from net.last_motion."""
     net.set_nms(nms_thresh=input_nms, nms_topk=400)
     tf = YOLO3VideoInferenceTransform(data_shape, data_shape, device_normalize=True, device_resize=device_resize,
                                       frame_format=frame_format)
@@ -564,6 +596,9 @@ def detect_stream(net, dataset, data_shape, step, chunk, max_do=-1, rank=0, worl
                 plain = link_rows(ids, scores, bboxes.clamp(0, W), track, num_class=1 if net.agnostic else net.num_class)
                 _collect_tracks(tracks, dataset, ids, plain, sidxs)
         _collect(boxes, dataset, ids, scores, bboxes, sidxs, W)
+        if motion_log is not None and net.last_motion is not None:
+            motion, sad = (t.cpu().tolist() for t in net.last_motion)
+            motion_log.extend((v, t, m[0], m[1], s[0], s[1]) for t, (m, s) in enumerate(zip(motion, sad)))
         if visualise is not None:
             write_overlay(visualise, v, net.last_overlay[0])
         c += x.shape[0]
@@ -722,7 +757,7 @@ def check_flags(FLAGS):
         from viddet_amd.byte import check_byte_params
         from viddet_amd.track import check_params
         try:
-            params = {k: v for k, v in track_args(FLAGS).items() if k not in ("method", "appearance")}
+            params = {k: v for k, v in track_args(FLAGS).items() if k not in ("method", "appearance", "gmc")}
             (check_byte_params if getattr(FLAGS, "track_method", "iou") == "byte" else check_params)(who="--track", **params)
         except ValueError as e:
             names = dict(sigma_iou2="--track_iou2", sigma_iou="--track_iou", sigma_l="--track_low", sigma_h="--track_high",
@@ -763,6 +798,41 @@ def check_flags(FLAGS):
         for flag, _ in _APP_FLAGS:
             if getattr(FLAGS, flag, None) is not None:
                 raise NotImplementedError("--%s needs --track_app: it is a parameter of appearance association" % flag)
+    if getattr(FLAGS, "track_gmc", False):
+        # camera-motion compensation is detect_video's, on a finished clip: refused elsewhere, never ignored
+        if not getattr(FLAGS, "track", False):
+            raise NotImplementedError("--track_gmc needs --track: it stabilises the boxes the tracker links")
+        if not getattr(FLAGS, "stream", False):
+            raise NotImplementedError("--track_gmc needs --stream: the motion is estimated between the consecutive frames of a clip "
+                                      "net.detect_video holds; the windowed path sees windows")
+        if getattr(FLAGS, "live", False):
+            raise NotImplementedError("--track_gmc does not combine with --live: a live session does not carry the signature of "
+                                      "its last frame from push to push")
+        if getattr(FLAGS, "track_smooth", False):
+            raise NotImplementedError("--track_gmc does not combine with --track_smooth: the pass emits boxes, and their way through "
+                                      "the stabilised frame has no definition yet")
+        if getattr(FLAGS, "tubelet", False):
+            raise NotImplementedError("--track_gmc does not combine with --tubelet: the pass emits boxes, and their way through the "
+                                      "stabilised frame has no definition yet")
+        if getattr(FLAGS, "seq_nms", False):
+            raise NotImplementedError("--track_gmc does not combine with --seq_nms: net.detect_video composes the two, the script "
+                                      "links the plain rows by a call of its own that knows no camera motion")
+        from viddet_amd.motion import check_params as check_gmc
+        try:
+            check_gmc(who="--track_gmc", **gmc_args(FLAGS))
+        except ValueError as e:
+            msg = str(e)
+            for flag, key in _GMC_FLAGS:
+                msg = msg.replace("--track_gmc: " + key, "--" + flag)
+            raise NotImplementedError(msg)
+    else:
+        for flag, _ in _GMC_FLAGS:
+            if getattr(FLAGS, flag, None) is not None:
+                raise NotImplementedError("--%s needs --track_gmc: it is a parameter of camera-motion compensation" % flag)
+    if getattr(FLAGS, "synthetic_pan", 0):
+        if FLAGS.synthetic_pan < 0 or len(FLAGS.dataset) > 1:
+            raise NotImplementedError("--synthetic_pan takes a step of at least 0 pixels and one dataset, got %d and %d"
+                                      % (FLAGS.synthetic_pan, len(FLAGS.dataset)))
     if getattr(FLAGS, "tubelet", False):
         # the tubelet pass runs over the tracks of a finished clip
         if not getattr(FLAGS, "track", False):
@@ -1011,6 +1081,12 @@ def main(argv=None):
     fmt = dict(frame_format="nv12", yuv_matrix=FLAGS.yuv_matrix, yuv_range=FLAGS.yuv_range) if FLAGS.frame_format == "nv12" else {}
     if len(FLAGS.dataset) > 1:          # detect_yolo3.py:166-167: several datasets = the combined set with its class tree
         dataset = SyntheticCombined(FLAGS.dataset, num_samples=FLAGS.synthetic_samples, classes_per_set=FLAGS.synthetic_classes)
+    elif FLAGS.synthetic_pan > 0:
+        # SyntheticTracks under a moving camera: steps of up to --synthetic_pan pixels, multiples of --track_gmc_cell
+        cell = 4 if FLAGS.track_gmc_cell is None else FLAGS.track_gmc_cell
+        dataset = SyntheticPan(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
+                               frames_per_video=FLAGS.synthetic_samples, window=FLAGS.window[0],
+                               step=FLAGS.window[1] if len(FLAGS.window) > 1 else 1, pan=max(FLAGS.synthetic_pan, cell), cell=cell, **fmt)
     elif {"vid", "mot", "hota"} & {m.lower() for m in FLAGS.metrics}:
         # the vid, mot and hota metrics need tracks: clips as below, whose labels are moving objects with track ids and motion IoUs
         dataset = SyntheticTracks(name, num_videos=2 if FLAGS.synthetic_videos is None else FLAGS.synthetic_videos,
@@ -1067,11 +1143,12 @@ def main(argv=None):
     sti = stitch_args(FLAGS)
     if sti is not None:
         seq_kw = dict(seq_kw, stitch=sti)
+    motion_log = [] if trk is not None and "gmc" in trk else None
     if FLAGS.stream:
         boxes = detect_stream(net, dataset, FLAGS.data_shape, FLAGS.window[1] if len(FLAGS.window) > 1 else 1, FLAGS.batch_size,
                               FLAGS.max_do, rank, world, device_resize=FLAGS.device_resize, frame_format=FLAGS.frame_format,
                               live=FLAGS.live_push if FLAGS.live else None, track_online=FLAGS.track_online,
-                              smooth_lag=FLAGS.track_smooth_lag, visualise=visualise_args(FLAGS, dataset), **seq_kw)
+                              smooth_lag=FLAGS.track_smooth_lag, visualise=visualise_args(FLAGS, dataset), motion_log=motion_log, **seq_kw)
     else:
         boxes = detect(net, dataset, loader, FLAGS.max_do, FLAGS.data_shape if FLAGS.device_resize else None, **seq_kw)
     boxes_seq = tracks = tracks_seq = boxes_tub = tracks_tub = None
@@ -1104,9 +1181,16 @@ def main(argv=None):
                         merged.update(part)
                 gathered.append(merged)
             tracks, tracks_seq, boxes_tub, tracks_tub = gathered
+        if motion_log is not None:
+            motion_log = sorted(row for part in vdist.all_gather_objects(motion_log) for row in part)
         if rank != 0:
             return None
     result = save_and_evaluate(FLAGS, dataset, boxes, save_dir)
+    if motion_log is not None:
+        # --track_gmc: the camera's motion beside everything the run without it writes
+        with open(os.path.join(FLAGS.save_dir, FLAGS.save_prefix, "motion.txt"), "w") as f:
+            for row in motion_log:
+                f.write("%d %d %d %d %d %d\n" % row)
     if boxes_seq is not None:
         # the rescored predictions and their results beside the plain ones: pred_seq, vid_seq.txt, coco_seq.txt, ...
         save_and_evaluate(FLAGS, dataset, boxes_seq, pred_dir(FLAGS.save_dir, FLAGS.save_prefix, FLAGS.model_agnostic, seq=True),

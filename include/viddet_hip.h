@@ -1147,6 +1147,34 @@ int vd_overlay_stages(const uint8_t* frames, uint8_t* out, int64_t frame_stride,
                       const uint32_t* palette, const uint8_t* font, int32_t* painted, void* ws, int64_t ws_bytes, int stages,
                       void* stream);
 
+/* ---- Camera-motion compensation of the clip trackers (vd_motion.hip): what viddet_amd.motion defines, bit for
+ * bit.  All three launch on `stream`, download nothing, wait for nothing and never write their inputs.
+ * vd_motion_sig: frames as vd_overlay takes them - F uint8 frames, frame f at byte f * frame_stride, rows `pitch` bytes apart;
+ * fmt 0: packed RGB (pitch >= 3 * W0), luma (77 R + 150 G + 29 B + 128) >> 8; fmt 1: the luma plane of NV12 (pitch >= W0; the
+ * chroma plane is never read, frame_stride only has to cover the luma rows).  sig [F][Gh][Gw] uint16, Gh = H0 / cell, Gw = W0 /
+ * cell: the luma summed over every cell x cell block; the pixels right of Gw * cell and below Gh * cell are not read.  cell
+ * is 2, 4, 8 or 16; cell <= H0, W0 <= 16384.  Where frames, pitch and frame_stride are multiples of 16 the pixels move as
+ * 16-byte loads, else byte by byte, with the same result; frames need no alignment.
+ * vd_motion_match: sig [F][Gh][Gw] of F frames in V clips, clip_start [V + 1] int32 (NULL with V == 1; cut to [0, F)).  For
+ * every frame t that is not the first of its clip and every (dx, dy) in [-radius, radius]^2, SAD(dx, dy) = the sum over gy in
+ * [radius, Gh - radius), gx in [radius, Gw - radius) of |sig[t][gy][gx] - sig[t-1][gy-dy][gx-dx]|; the winner is the least
+ * (SAD, dx*dx + dy*dy, dy, dx); sad [F][2] int64 = (SAD(winner), SAD(0,0)); motion [F][2] int32 = (dx * cell, dy * cell) iff
+ * SAD(winner) * 256 <= SAD(0,0) * (int)(gate * 256.0f), else (0, 0); cum [F][2] int32 the running sum of motion inside the
+ * clip.  First frames of clips and frames that no clip covers get zeros.  1 <= radius <= 16, 0 < gate <= 1, 2 * radius < Gh,
+ * Gw <= 4096.  ws: vd_motion_match_ws_bytes(F, radius) = 8 * F * (2 * radius + 1)^2 bytes, 8-byte aligned (-1: sizes that are not
+ * taken).  Two launches, no atomics.
+ * vd_motion_shift: out [F][N][4] = boxes [F][N][4] with (float)cum[t].x * sx added to x1 and x2 and (float)cum[t].y * sy to
+ * y1 and y2 (sign +1) or subtracted (sign -1), one fp32 multiply and one fp32 add or subtract each, on the rows whose key is
+ * >= 0 - key [F][N] fp32 ids (a NaN is not >= 0) with key_is_track 0, int32 track ids with 1; the other rows keep their bits.
+ * out must not be boxes; both 16-byte aligned. */
+int vd_motion_sig(const uint8_t* frames, int64_t frame_stride, int64_t pitch, int fmt, int F, int H0, int W0, int cell, uint16_t* sig,
+                  void* stream);
+int64_t vd_motion_match_ws_bytes(int F, int radius);
+int vd_motion_match(const uint16_t* sig, const int32_t* clip_start, int V, int F, int Gh, int Gw, int cell, int radius, float gate,
+                    int32_t* motion, int64_t* sad, int32_t* cum, void* ws, int64_t ws_bytes, void* stream);
+int vd_motion_shift(const void* key, int key_is_track, const float* boxes, const int32_t* cum, int F, int N, float sx, float sy, int sign,
+                    float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,75 @@ class SyntheticTracks(SyntheticVideo):
         return img, label
 
 
+class SyntheticPan(SyntheticTracks):
+    """SyntheticTracks seen by a moving camera, for camera-motion compensation (viddet_amd/motion.py).  Every clip
+    has a textured world canvas of its own, larger than the frame by `margin` = 4 * pan pixels a side (rounded up to `cell`):
+    8 x 8-pixel blocks of seeded colours with per-pixel noise of +-8 on top, drawn from a generator seeded by [seed, 104729, v].
+    The camera's path is a seeded random walk (generator [seed, 15485863, v]): it starts in the canvas's middle and steps by a
+    multiple of `cell` of at most `pan` pixels on each axis every frame; a step that would leave the canvas is taken the other
+    way.  Frame t is the crop of the canvas at the camera's position, so consecutive frames are exact translates of one
+    another.  The labels are SyntheticTracks' world tracks minus camera_path(v)[t], clipped to the frame; a row that falls
+    outside it is dropped.  camera_path(v) -> (T,2) int (x, y): the camera's position relative to frame 0, the truth that minus
+    the running sum of motion.match_host's `motion` should give."""
+
+    def __init__(self, name="synthetic", num_videos=2, frames_per_video=16, window=1, step=1, pan=24, cell=4, **kw):
+        pan, cell = int(pan), int(cell)
+        if cell < 1 or pan < cell:
+            raise ValueError("SyntheticPan needs cell >= 1 and pan >= cell, got pan=%d cell=%d" % (pan, cell))
+        super().__init__(name, num_videos=num_videos, frames_per_video=frames_per_video, window=window, step=step, **kw)
+        self.pan, self.cell = pan, cell
+        self.margin = -(-4 * pan // cell) * cell
+        self._world = self._labels
+        self._paths = [self._clip_path(v) for v in range(self.num_videos)]
+        self._labels = [[self._seen(self._world[v][t], self.camera_path(v)[t]) for t in range(self.frames_per_video)]
+                        for v in range(self.num_videos)]
+        self._canvas = {}
+
+    def _clip_path(self, v):
+        """(T,2) int: the camera's (x, y) in canvas pixels"""
+        rng = np.random.default_rng([self._seed, 15485863, v])
+        k = self.pan // self.cell
+        pos = np.full(2, self.margin // 2 // self.cell * self.cell, dtype=np.int64)
+        path = [pos.copy()]
+        for _ in range(1, self.frames_per_video):
+            s = rng.integers(-k, k + 1, 2) * self.cell
+            s = np.where((pos + s < 0) | (pos + s > self.margin), -s, s)
+            pos = pos + s
+            path.append(pos.copy())
+        return np.stack(path)
+
+    def camera_path(self, v):
+        """(T,2) int (x, y): the camera's position in every frame of clip v, relative to frame 0"""
+        self.sample_index(v, 0)
+        return self._paths[v] - self._paths[v][0]
+
+    def _seen(self, rows, cam):
+        W, H = self._size
+        r = rows.copy()
+        r[:, [0, 2]] = np.clip(r[:, [0, 2]] - float(cam[0]), 0.0, W - 1.0)
+        r[:, [1, 3]] = np.clip(r[:, [1, 3]] - float(cam[1]), 0.0, H - 1.0)
+        return r[(r[:, 2] > r[:, 0]) & (r[:, 3] > r[:, 1])]
+
+    def canvas(self, v):
+        """uint8 (h + margin, w + margin, 3): the world of clip v"""
+        self.sample_index(v, 0)
+        if v not in self._canvas:
+            W, H = self._size
+            rng = np.random.default_rng([self._seed, 104729, v])
+            ch, cw = H + self.margin, W + self.margin
+            blocks = rng.integers(8, 248, (-(-ch // 8), -(-cw // 8), 3))
+            c = np.kron(blocks, np.ones((8, 8, 1), dtype=np.int64))[:ch, :cw] + rng.integers(-8, 9, (ch, cw, 3))
+            self._canvas = {v: c.astype(np.uint8)}                                   # one clip's canvas is kept at a time
+        return self._canvas[v]
+
+    def _clip_frame(self, v, t):
+        W, H = self._size
+        x, y = (int(a) for a in self._paths[v][t])
+        label = self._labels[v][t].copy()
+        label[:, 5] = 0.0                                                            # the sample contract's `difficult`
+        return np.ascontiguousarray(self.canvas(v)[y:y + H, x:x + W]), label
+
+
 class SyntheticCombined(SyntheticDetection):
     """Stand-in for CombinedDetection(datasets, class_tree=True) (detect_yolo3.py:167, datasets/combined.py): the label set of
     several datasets arranged in a class tree - one group label per dataset under 'ROOT' (labels are ordered parents first,

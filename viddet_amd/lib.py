@@ -256,6 +256,11 @@ SIGNATURES = {
                         _p, _i, _p, _p, _p, _p, _i64, _p]),
     "vd_overlay_stages": (_i, [_p, _p, _i64, _i64, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _i,
                                _i, _i, _p, _i, _p, _p, _p, _p, _i64, _i, _p]),
+    # camera-motion compensation of the clip trackers: luma signatures, block matching, the box shift (vd_motion.hip)
+    "vd_motion_sig": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _i, _p, _p]),
+    "vd_motion_match_ws_bytes": (_i64, [_i, _i]),
+    "vd_motion_match": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _i64, _p]),
+    "vd_motion_shift": (_i, [_p, _i, _p, _p, _i, _i, _f, _f, _i, _p, _p]),
 }
 
 _lib = None

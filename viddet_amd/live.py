@@ -10,12 +10,18 @@ differently.  With `track`, the emitted rows go through a resumable tracker on t
 DESIGN.md 39) whose state survives from push to push.  With `smooth={'lag': L}` the tracked frames go through a fixed-lag
 smoother on the device as well (ops.SmoothLagState, vd_track_smooth_push) and come out L frames later.
 """
+import numpy as np
 import torch
 
 from . import ops
 from .appearance import LEVELS as APP_LEVELS
 from .appearance import parse_option as parse_appearance
 from .appearance import split_appearance
+from .motion import check_grid as check_motion_grid
+from .motion import frame_size as motion_frame_size
+from .motion import grid_size as motion_grid_size
+from .motion import parse_option as parse_gmc
+from .motion import split_gmc
 from .overlay import parse_option as parse_overlay
 from .seq_nms import parse_option as parse_seq_nms
 from .smooth import parse_option as parse_smooth
@@ -176,6 +182,21 @@ def _draw(net, frames, res, ovl, track, hw):
                        net_size=tuple(hw), **kw)
 
 
+def _camera_motion(net, frames, gmc, chunk, fmt):
+    """detect_video's `gmc`: the signature of the clip in slices of `chunk` frames - a host clip is uploaded
+    slice by slice and is never on the device as a whole - then one ops.motion_match over it -> (motion, sad, cum)"""
+    T, H0, W0 = motion_frame_size(tuple(frames.shape), fmt)
+    Gh, Gw = motion_grid_size(H0, W0, gmc["cell"])
+    sig = torch.empty(T, Gh, Gw, dtype=torch.uint16, device=net.device)
+    for a in range(0, T, chunk):
+        x = frames[a:a + chunk]
+        x = x if x.is_cuda else x.to(net.device)
+        if fmt == "rgb":
+            x = x.contiguous()
+        ops.motion_signature(x, cell=gmc["cell"], fmt=fmt, out=sig[a:a + x.shape[0]])
+    return ops.motion_match(sig, radius=gmc["radius"], gate=gmc["gate"], cell=gmc["cell"])
+
+
 def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet=None, smooth=None, stitch=None, overlay=None):
     """YOLOV3.detect_video (its docstring is the description): a clip whose end is known is one push and one flush of the
     planner, run on the engine with the caller's frames at base 0; then Seq-NMS -> track -> stitch -> smooth ->
@@ -187,8 +208,10 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         raise RuntimeError("detect_video: %r has frames in flight on this net (they share the feature ring): flush() it first"
                            % (net._live,))
     seq = parse_seq_nms(seq_nms, net.post_nms, "detect_video")
+    track, gmc = split_gmc(track)
     track, app = split_appearance(track)
     trk = parse_track(track, net.post_nms, "detect_video")
+    gmc = parse_gmc(gmc, trk is not None, smooth not in (None, False), tubelet not in (None, False), "detect_video")
     app = parse_appearance(app, None if trk is None else trk[2], seq is not None, "detect_video")
     if app is not None and net._k > 1 and net._k_join_pos != 'early':
         raise NotImplementedError("detect_video with track's appearance and k_join_pos %r: the ring of the late join holds the "
@@ -204,7 +227,16 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
                              "already normalised" % frames.dtype)
         if ovl.get("inplace") and not frames.is_cuda:
             raise ValueError("detect_video: overlay's inplace needs frames on the device; host frames are painted on their upload")
+    gmc_fmt = None
+    if gmc is not None:                                           # refused by name before any GPU work
+        if frames.dtype != torch.uint8:
+            raise ValueError("detect_video: gmc needs uint8 frames (the pixels the camera motion is read from), got %s: float "
+                             "frames are already normalised" % frames.dtype)
+        gmc_fmt = "nv12" if net._dev_nv12 is not None else "rgb"
+        _, h0, w0 = motion_frame_size(tuple(frames.shape), gmc_fmt)
+        check_motion_grid(*motion_grid_size(h0, w0, gmc["cell"]), gmc["radius"], "detect_video with gmc")
     net.last_overlay = None
+    net.last_motion = None
     net.last_tracks = net.last_track_boxes = None
     net.last_embeddings = net.last_app_maps = None
     net.last_tubelet = net.last_pre_tubelet = None
@@ -236,6 +268,12 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
         res = ids, scores, bboxes
     if trk is not None:
         boxes = res[2] if trk[1] is None else res[2].clamp(0, float(trk[1]))
+        if gmc is not None:                                       # the tracker and stitch link in the stabilised frame
+            motion, sad, cum = _camera_motion(net, frames, gmc, chunk, gmc_fmt)
+            net.last_motion = motion, sad
+            _, h0, w0 = motion_frame_size(tuple(frames.shape), gmc_fmt)
+            gsx, gsy = float(np.float32(W) / np.float32(w0)), float(np.float32(H) / np.float32(h0))
+            boxes = ops.motion_shift(res[0].contiguous(), boxes.contiguous(), cum, gsx, gsy, -1)
         if app is not None:                                       # SORT on the fused cost of geometry and appearance
             *links, net.last_track_boxes = ops.track_sort_app(res[0], res[1], boxes, net.last_embeddings, num_class=num_class,
                                                               sigma_app=app["sigma_app"], sigma_prox=app["sigma_prox"], **trk[0])
@@ -246,6 +284,8 @@ def detect_video(net, frames, step=1, chunk=8, seq_nms=None, track=None, tubelet
             net.last_tracks = tuple(links)
         else:
             net.last_tracks = ops.track(res[0], res[1], boxes, num_class=num_class, **trk[0])
+        if gmc is not None and net.last_track_boxes is not None:  # the filtered boxes back in image coordinates
+            net.last_track_boxes = ops.motion_shift(net.last_tracks[0], net.last_track_boxes, cum, gsx, gsy, 1)
         if sti_kw is not None:                                    # the fragments re-linked: the later passes take these ids
             net.last_pre_stitch = net.last_tracks
             *links, stitches, overflow = ops.stitch(res[0], res[1], boxes, net.last_tracks[0], num_class=num_class, **sti_kw)
@@ -324,6 +364,10 @@ class VideoSession:
         self.track_decide = None
         self._trk_kw = self._trk_clip = self._trk = None
         self._trk_method = "iou"
+        if split_gmc(track)[1] not in (None, False):
+            raise NotImplementedError("open_video with track's gmc: the signature of the last frame is not carried from push to "
+                                      "push (run detect_video on the finished clip)")
+        track = split_gmc(track)[0]
         if split_appearance(track)[1] not in (None, False):
             raise NotImplementedError("open_video with track's appearance: the descriptors of a session's frames are not carried "
                                       "from push to push (run detect_video on the finished clip)")

@@ -2275,7 +2275,16 @@ class YOLOV3(object):
         and appearance (ops.track_sort_app).  last_embeddings (T,post_nms,C) int8 holds the descriptors and is
         None after a call without the key; with 'keep_maps': True (tests) last_app_maps holds a clone of the maps every
         launch read, in frame order.  Refused with 'iou' and 'byte', beside seq_nms (it permutes the rows ahead of the
-        tracker), with a late join (its ring holds neck tips, not routes) and by open_video.
+        tracker), with a late join (its ring holds neck tips, not routes) and by open_video.  With any method, a further key
+        `gmc`: True or {'cell': 2 | 4 | 8 | 16, 'radius': 1..16, 'gate': g} - camera-motion compensation: the
+        translation of the whole picture between consecutive frames is estimated from the uint8 frames' luma (RGB, or NV12
+        under set_device_resize(source='nv12'); ops.motion_signature in slices of `chunk` frames - a host clip is uploaded
+        a second time, slice by slice - then one ops.motion_match), summed along the clip and taken off the boxes the tracker
+        and `stitch` link (ops.motion_shift, after the `clip` clamp); last_track_boxes is put back into image coordinates.
+        The three returned tensors are those of the call without the key; last_motion = (motion (T,2) int32 in source
+        pixels, sad (T,2) int64) and is None after a call without it.  Composes with seq_nms (which runs ahead, on image
+        coordinates) and overlay; refused beside smooth and tubelet (they emit boxes), with float frames, with a frame too
+        small for `radius`, and by open_video.
 
         tubelet: None (the default), True, or a dict of rescore / max_gap / drop_untracked; needs `track` - the rows the tracker
         saw (those of Seq-NMS where that is on, clipped where track's `clip` is given) go through the tubelet pass on the device

@@ -1093,6 +1093,122 @@ def overlay(frames, ids, scores, bboxes, track=None, gt=None, clip_start=None, o
     return out, painted
 
 
+def motion_signature(frames, cell=4, fmt="rgb", H0=None, W0=None, pitch=None, frame_stride=None, out=None):
+    """vd_motion_sig (viddet_amd/motion.py::signature_host on the device, bit for bit, DESIGN.md 44): the luma of every frame
+    summed over cell x cell blocks.  frames: a uint8 device tensor with ops.overlay's surface conventions - (F,H0,W0,3)
+    contiguous; with fmt='nv12' (F,H0*3/2,W0) whose last stride is 1 (a contiguous tensor, or the view [..., :W0] of a pitched
+    surface), or a 1-D surface with H0, W0 and pitch given (frame_stride: pitch * H0 * 3 / 2 where it is not given; the frames it
+    holds are counted from its size).  out: a contiguous uint16 device tensor (F,Gh,Gw) to write, else one is allocated.  Returns
+    sig (F,Gh,Gw) uint16.  The frames are never written.  Launches on the current stream; nothing is downloaded and nothing
+    waits."""
+    from . import motion as M
+    cell, _, _ = M.check_params(cell=cell, who="motion_signature")
+    if fmt not in M.FORMATS:
+        raise ValueError("motion_signature: fmt must be 'rgb' or 'nv12', got %r" % (fmt,))
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise ValueError("motion_signature: frames must be a uint8 tensor, got %s" % (getattr(frames, "dtype", type(frames)),))
+    nv12 = fmt == "nv12"
+    if nv12 and frames.dim() == 1:
+        if H0 is None or W0 is None or pitch is None:
+            raise ValueError("motion_signature: a 1-D NV12 surface needs H0, W0 and pitch")
+        h0, w0, pitch = int(H0), int(W0), int(pitch)
+        if h0 < 2 or w0 < 2 or h0 % 2 or w0 % 2:
+            raise ValueError("motion_signature: NV12 needs an even frame size, got H0=%d W0=%d" % (h0, w0))
+        span = pitch * (h0 + h0 // 2 - 1) + w0
+        frame_stride = pitch * (h0 + h0 // 2) if frame_stride is None else int(frame_stride)
+        if pitch < w0 or frame_stride < span or frames.numel() < span or not frames.is_contiguous():
+            raise ValueError("motion_signature: a surface of %d bytes holds no NV12 frame of %dx%d with pitch=%d frame_stride=%d"
+                             % (frames.numel(), h0, w0, pitch, frame_stride))
+        F = (int(frames.numel()) - span) // frame_stride + 1
+    else:
+        if (H0, W0, pitch, frame_stride) != (None,) * 4:
+            raise ValueError("motion_signature: H0, W0, pitch and frame_stride describe a 1-D NV12 surface, got frames %r"
+                             % (tuple(frames.shape),))
+        F, h0, w0 = M.frame_size(tuple(frames.shape), fmt)
+        if nv12:
+            pitch, frame_stride = int(frames.stride(1)), int(frames.stride(0))
+            span = pitch * (h0 + h0 // 2 - 1) + w0
+            if frames.stride(2) != 1 or pitch < w0 or (F > 1 and frame_stride < span):
+                raise ValueError("motion_signature: NV12 frames need a last stride of 1, rows at least W0 and frames at least a "
+                                 "frame apart, got strides %r" % (tuple(frames.stride()),))
+            frame_stride = max(frame_stride, span)
+        else:
+            if not frames.is_contiguous():
+                raise ValueError("motion_signature: RGB frames must be contiguous, got strides %r" % (tuple(frames.stride()),))
+            pitch = 3 * w0
+            frame_stride = h0 * pitch
+    if not frames.is_cuda:
+        raise ValueError("motion_signature: frames must be a device tensor")
+    Gh, Gw = M.grid_size(h0, w0, cell)
+    if Gh < 1 or Gw < 1:
+        raise ValueError("motion_signature: frames of %d x %d hold no cell of %d pixels" % (h0, w0, cell))
+    if out is None:
+        out = torch.empty(F, Gh, Gw, dtype=torch.uint16, device=frames.device)
+    else:
+        _row_tensors("motion_signature", (("out", out, F * Gh * Gw, torch.uint16),))
+        if out.device != frames.device:
+            raise ValueError("motion_signature: out must be on the frames' device")
+    if F == 0:
+        return out
+    check(_lib().vd_motion_sig(ptr(frames), frame_stride, pitch, 1 if nv12 else 0, F, h0, w0, cell, ptr(out), _s()), "vd_motion_sig")
+    return out
+
+
+def motion_match(sig, clip_start=None, radius=8, gate=0.75, ws=None, cell=4):
+    """vd_motion_match (viddet_amd/motion.py::match_host on the device, bit for bit, DESIGN.md 44): the translation between
+    consecutive frames by block matching on their signatures.  sig: a contiguous uint16 device tensor (F,Gh,Gw),
+    ops.motion_signature's; clip_start as ops.seq_nms takes it; cell: the signature's, the unit of the result.  Returns device
+    tensors (motion (F,2) int32 in source pixels, sad (F,2) int64, cum (F,2) int32: the running sum of motion inside every clip).
+    Launches on the current stream; nothing is downloaded and nothing waits.  ws: a uint8 device tensor of >= 8 * F *
+    (2 * radius + 1)**2 bytes, 8-byte aligned, to reuse, else one is allocated."""
+    from . import motion as M
+    cell, radius, g = M.check_params(cell, radius, gate, "motion_match")
+    if not torch.is_tensor(sig) or sig.dtype != torch.uint16 or sig.dim() != 3 or not sig.is_contiguous() or not sig.is_cuda:
+        raise ValueError("motion_match: sig must be a contiguous uint16 device tensor (F,Gh,Gw), got %s %r"
+                         % (getattr(sig, "dtype", type(sig)), tuple(getattr(sig, "shape", ()))))
+    F, Gh, Gw = (int(v) for v in sig.shape)
+    M.check_grid(Gh, Gw, radius, "motion_match")
+    dev = sig.device
+    clip_start, V = _clip_offsets("motion_match", clip_start, F, dev)
+    motion = torch.empty(F, 2, dtype=torch.int32, device=dev)
+    sad = torch.empty(F, 2, dtype=torch.int64, device=dev)
+    cum = torch.empty(F, 2, dtype=torch.int32, device=dev)
+    if F == 0:
+        return motion, sad, cum
+    need = int(_lib().vd_motion_match_ws_bytes(F, radius))
+    if need < 0:
+        raise ValueError("motion_match: F=%d frames at radius=%d: vd_motion_match takes at most 2^31 - 1 table entries" % (F, radius))
+    ws = _workspace("motion_match", ws, need, dev, align=8)
+    check(_lib().vd_motion_match(ptr(sig), ptr(clip_start), V, F, Gh, Gw, cell, radius, float(g), ptr(motion), ptr(sad), ptr(cum),
+                                 ptr(ws), int(ws.numel()), _s()), "vd_motion_match")
+    return motion, sad, cum
+
+
+def motion_shift(ids_or_track, boxes, cum, sx, sy, sign):
+    """vd_motion_shift (viddet_amd/motion.py::stabilise_host with sign -1, restore_host with sign +1, on the device, bit for bit,
+    DESIGN.md 44).  ids_or_track: contiguous fp32 ids (F,N[,1]) - the rows with id >= 0 move - or an int32 track table (F,N) -
+    those with track >= 0 do; boxes (F,N,4) contiguous fp32; cum (F,2) int32, ops.motion_match's; sx, sy: the network's size over
+    the source's.  Returns a new tensor; the input is never written.  Launches on the current stream; nothing is downloaded and
+    nothing waits."""
+    if isinstance(sign, bool) or sign not in (1, -1):
+        raise ValueError("motion_shift: sign must be +1 (restore) or -1 (stabilise), got %r" % (sign,))
+    if not torch.is_tensor(boxes) or boxes.dim() != 3 or boxes.shape[-1] != 4:
+        raise ValueError("motion_shift: boxes must be (F,N,4), got %r" % (tuple(getattr(boxes, "shape", ())),))
+    F, N = int(boxes.shape[0]), int(boxes.shape[1])
+    if not torch.is_tensor(ids_or_track) or ids_or_track.dtype not in (torch.float32, torch.int32):
+        raise ValueError("motion_shift: ids_or_track must be fp32 ids or an int32 track table, got %s"
+                         % (getattr(ids_or_track, "dtype", type(ids_or_track)),))
+    is_track = ids_or_track.dtype == torch.int32
+    _row_tensors("motion_shift", (("track" if is_track else "ids", ids_or_track, F * N, ids_or_track.dtype),
+                                  ("boxes", boxes, F * N * 4, torch.float32), ("cum", cum, F * 2, torch.int32)))
+    out = torch.empty_like(boxes)
+    if F == 0 or N == 0:
+        return out
+    check(_lib().vd_motion_shift(ptr(ids_or_track), int(is_track), ptr(boxes), ptr(cum), F, N, float(sx), float(sy), int(sign), ptr(out),
+                                 _s()), "vd_motion_shift")
+    return out
+
+
 class _StreamState:
     """What the live-state classes share: V streams of N rows per frame, a zeroed uint8 state tensor (V, bytes) - all zero is
     a fresh stream -, the frames pushed since the last reset, and the checks of a push."""
